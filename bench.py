@@ -1,12 +1,19 @@
 #!/usr/bin/env python3
 """Benchmark of the stereo-matching hot path (the timed region of the reference's match.py:129-179).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--fast] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--fast] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-parity] [--no-bounds]]
 
 The benchmarked variant is the drop-in default of match.py: float32 throughout, every stage behind the conv features
 bit-identical to the reference's NumPy (`--fast` selects the tolerance-checked variants instead; their stated tolerance
-lives in src/tolerances.py).  The line carries a `parity` block measured on the very pair that was timed, and the
-script EXITS NON-ZERO when that block violates what `config.variant` states.
+lives in src/tolerances.py).
+
+A plain run sets up, warms up, times K pairs and prints the headline line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, ...).  `--dump-outputs DIR` also writes the final disparity map of the last
+timed step as DIR/disparity.npy (float32; rank r > 0: DIR/disparity_rank<r>.npy); the inputs are seeded, so two builds
+can be compared output for output.  `--full` adds everything else to the line: a `parity` block measured on the very
+pair that was timed (the script then EXITS NON-ZERO when that block violates what `config.variant` states), the other
+variant's time, per-stage times and rooflines, the side measurements and the CPU baseline.
 
 `--gpus N` with N > 1 may be started either by `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`
 (one rank per GPU, as the driver does) or directly as `python bench.py --gpus N ...`: without a WORLD_SIZE in the
@@ -55,6 +62,12 @@ def parse():
     ap.add_argument("--library-features", action="store_true",
                     help="conv features through the float32 library convolutions (MIOpen) instead of the hand-written "
                          "split-operand matrix-core kernels (which are as close to a float64 evaluation as the library)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the final disparity map of the last timed step to DIR/disparity.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the parity block (exit 3 on a violation), the other variant, per-stage "
+                         "times and rooflines, the side measurements and the CPU baseline (the --no-* options below "
+                         "switch parts of it off)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true",
                     help="skip the parity block (graph replay vs eager, benchmarked variant vs the bit-exact variant)")
@@ -236,6 +249,11 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     mgpu.barrier()
+    if args.dump_outputs:
+        # what the timed path handed its caller in the last step: the final disparity map [H, W], float32
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "disparity.npy" if rank == 0 else "disparity_rank%d.npy" % rank
+        np.save(os.path.join(args.dump_outputs, name), out.cpu().numpy().astype(np.float32))
 
     all_elapsed = mgpu.gather_elapsed(elapsed)
     elapsed_max = max(all_elapsed)
@@ -244,6 +262,48 @@ def main():
                                    "visible": os.environ.get("HIP_VISIBLE_DEVICES", os.environ.get("ROCR_VISIBLE_DEVICES")),
                                    "pci_bus_id": getattr(props, "pci_bus_id", None), "cus": props.multi_processor_count})
     if rank != 0:
+        mgpu.finalize()
+        return
+
+    voxels = H * W * D
+    value = world * voxels * args.steps / elapsed_max / 1e6
+    result = {
+        "metric": "Mdisparities/s (HxWxD / s) end-to-end match.py timed region, images resident in HBM",
+        "value": round(value, 2), "unit": "Mdisparities/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(elapsed_max / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32" if args.exact else
+        "f32 (split-f16 operands: 22-bit products, float32 accumulate, in the cost volume)",
+        "data": "synthetic",
+        "config": {"workload": "%s: %dx%d synthetic stereo pair, D=%d, one pair per GPU" % (args.config, W, H, D),
+                   "variant": "bit-exact (float32; every stage after the conv features bit-identical to the reference's "
+                              "NumPy on the same features; the features within 3e-7 of a float64 evaluation of the network)"
+                   if args.exact else
+                   "fast (split-f16 MFMA cost volume%s); stated tolerance against the "
+                   "bit-exact variant (src/tolerances.py, asserted on `parity` under --full): WTA flips <= 1e-4 of the "
+                   "pixels per view, >= 98 %% of the final map within 1e-3 px, 99th percentile <= 0.02 px"
+                   % (", separable float64-prefix CBCA on plane-major volumes" if args.separable_cbca
+                      else " in front of the bit-exact stages"),
+                   "features": "float32 library convolutions (MIOpen)" if lib_features else
+                   "hand-written matrix-core convolutions (float32 in/out; every operand as two f16 parts, 3 products per "
+                   "multiply, float32 accumulation with the cross terms in their own accumulator: 2.6e-7 .. 3.1e-7 from a "
+                   "float64 evaluation where the library path is 2.7e-7 .. 2.8e-7, profiles/parity_features_split_r04.json)",
+                   "launch": ("one hipGraph replay per pair" if use_graph else "kernel by kernel") +
+                   ("; each volume's aggregation -> SGM -> aggregation is one free-running chain of one-volume launches "
+                    "on its own stream (StereoMatcher's default since round 6), joined in front of the WTA-carrying "
+                    "last aggregation launch" if (matcher.free_chains and matcher.two_chains and matcher.pixel_major()) else ""),
+                   "weights": "converted reference checkpoint" if os.path.isfile(wpath) else "random init"},
+    }
+    ranks = {
+        "per_rank_ms_per_step": [round(e / args.steps * 1e3, 3) for e in all_elapsed],
+        "per_rank_device": devices,
+        "process_group": (torch.distributed.get_backend() + " x%d" % torch.distributed.get_world_size())
+        if torch.distributed.is_initialized() else None,
+    }
+    if not args.full:
+        # the plain run: the headline and nothing else (no parity, side measurements, rooflines or CPU baseline)
+        result.update(ranks)
+        print(json.dumps(result))
         mgpu.finalize()
         return
 
@@ -448,8 +508,6 @@ def main():
     host_io_ms = (time.perf_counter() - t2) / nside * 1e3
     del res
 
-    voxels = H * W * D
-    value = world * voxels * args.steps / elapsed_max / 1e6
     stages = {k: float(np.mean(v)) for k, v in timer.summary_ms().items()}          # mean ms per launch / stage
     counts = {k: len(v) // nside for k, v in timer.summary_ms().items()}
     # One-volume launches run as two concurrent chains (left volume on the main stream, right volume on a second one):
@@ -592,32 +650,7 @@ def main():
     sgm_span_ms = spans.get("sgm")     # the bracket around the four passes (free-running chains: one per chain, on its stream)
     if sgm_span_ms is not None and matcher.pixel_major():
         sgm_stage_ms = sgm_span_ms
-    result = {
-        "metric": "Mdisparities/s (HxWxD / s) end-to-end match.py timed region, images resident in HBM",
-        "value": round(value, 2), "unit": "Mdisparities/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(elapsed_max / args.steps * 1e3, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32" if args.exact else
-        "f32 (split-f16 operands: 22-bit products, float32 accumulate, in the cost volume)",
-        "data": "synthetic",
-        "config": {"workload": "%s: %dx%d synthetic stereo pair, D=%d, one pair per GPU" % (args.config, W, H, D),
-                   "variant": "bit-exact (float32; every stage after the conv features bit-identical to the reference's "
-                              "NumPy on the same features; the features within 3e-7 of a float64 evaluation of the network)"
-                   if args.exact else
-                   "fast (split-f16 MFMA cost volume%s); stated tolerance against the "
-                   "bit-exact variant (src/tolerances.py, asserted on `parity` below): WTA flips <= 1e-4 of the pixels per "
-                   "view, >= 98 %% of the final map within 1e-3 px, 99th percentile <= 0.02 px"
-                   % (", separable float64-prefix CBCA on plane-major volumes" if args.separable_cbca
-                      else " in front of the bit-exact stages"),
-                   "features": "float32 library convolutions (MIOpen)" if lib_features else
-                   "hand-written matrix-core convolutions (float32 in/out; every operand as two f16 parts, 3 products per "
-                   "multiply, float32 accumulation with the cross terms in their own accumulator: 2.6e-7 .. 3.1e-7 from a "
-                   "float64 evaluation where the library path is 2.7e-7 .. 2.8e-7, profiles/parity_features_split_r04.json)",
-                   "launch": ("one hipGraph replay per pair" if use_graph else "kernel by kernel") +
-                   ("; each volume's aggregation -> SGM -> aggregation is one free-running chain of one-volume launches "
-                    "on its own stream (StereoMatcher's default since round 6), joined in front of the WTA-carrying "
-                    "last aggregation launch" if (matcher.free_chains and matcher.two_chains and matcher.pixel_major()) else ""),
-                   "weights": "converted reference checkpoint" if os.path.isfile(wpath) else "random init"},
+    result.update({
         "roofline": dict(rooflines[dominant], kernel=dominant) if dominant else None,
         "rooflines": rooflines,
         # the two aggregations as stages (brackets around all their launches, both streams joined): what the chains of
@@ -664,11 +697,8 @@ def main():
         ("fast_variant_ms_per_step" if is_default else "exact_variant_ms_per_step"):
             round(other_ms, 3) if other_ms is not None else None,
         "fast_variant_parity": other_parity,
-        "per_rank_ms_per_step": [round(e / args.steps * 1e3, 3) for e in all_elapsed],
-        "per_rank_device": devices,
-        "process_group": (torch.distributed.get_backend() + " x%d" % torch.distributed.get_world_size())
-        if torch.distributed.is_initialized() else None,
-    }
+    })
+    result.update(ranks)
     if not args.no_cpu_baseline and world == 1:
         cores = args.cpu_cores if args.cpu_cores > 0 else max(1, min(16, (os.cpu_count() or 2) // 2))
         if not os.path.isfile(wpath):      # random-init run: hand the workers the same weights through a file

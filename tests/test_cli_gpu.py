@@ -66,6 +66,41 @@ def test_match_cli_writes_reference_outputs(tmp_path, net_layers, extra, thresho
         assert close >= threshold, "%s: only %.4f of pixels within 1e-3 px of the CPU checker" % (rel, close)
 
 
+def test_bench_plain_run_is_the_headline_and_dumps_the_timed_output(tmp_path, net_layers):
+    """bench.py without --full: set-up, warm-up, K timed pairs and the headline line only (no parity block, side
+    measurements or CPU baseline); --dump-outputs writes the last timed pair's final map, which is what the bit-exact
+    matcher returns for the same seeded pair."""
+    import json
+    import torch
+    import _hipabi as hip
+    import stereo_device as sd
+    import synthetic
+    from model import NET
+    out_dir = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--config",
+           "cfg1", "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["unit"] == "Mdisparities/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["metric"].startswith("Mdisparities/s") and d["steps"] == 3 and d["warmup"] == 1
+    want = 256 * 256 * 64 * 1e-6 / (d["ms_per_step"] * 1e-3)
+    assert abs(d["value"] - want) <= 0.02 * want
+    for key in ("parity", "roofline", "cpu_baseline", "stage_ms_per_step", "ms_per_step_kernel_by_kernel"):
+        assert key not in d, key
+    assert sorted(os.listdir(str(out_dir))) == ["disparity.npy"]
+    got = np.load(str(out_dir / "disparity.npy"))
+    assert got.shape == (256, 256) and got.dtype == np.float32
+    L, R, _, _, _ = synthetic.make_pair(256, 256, 64, seed=100)
+    net = NET(None, input_patch_size=11, batch_size=1, device="cuda").set_layers(net_layers)
+    matcher = sd.StereoMatcher(net, cv_mode=hip.MCCNN_CV_EXACT, cbca_order=hip.MCCNN_CBCA_REFERENCE_ORDER,
+                               features="split_f16", on_saturation="ignore")      # what bench.py constructs
+    ref = matcher.match(torch.from_numpy(L[:, :, 0]).cuda(), torch.from_numpy(R[:, :, 0]).cuda(), 64).cpu().numpy()
+    assert np.array_equal(got.view(np.int32), ref.view(np.int32))
+
+
 def test_bench_two_ranks_share_one_gpu():
     """bench.py's N > 1 path as the driver launches it (torch.distributed.run, one process per rank), on a one-GPU
     box: the two ranks share the GPU and rendezvous over gloo (MCCNN_BENCH_SHARED_GPU=1).  Rank 0 prints ONE JSON
@@ -74,7 +109,7 @@ def test_bench_two_ranks_share_one_gpu():
     env = dict(os.environ, MCCNN_BENCH_SHARED_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29631", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--config", "cfg1"]
+           "--warmup", "1", "--config", "cfg1", "--full"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, env=env)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
@@ -137,7 +172,7 @@ def test_bench_with_library_features():
     (same features) still agrees bit for bit."""
     import json
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--config", "cfg1",
-           "--library-features", "--no-cpu-baseline"]
+           "--library-features", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     d = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][0])
@@ -154,7 +189,7 @@ def test_bench_fast_variant_states_and_meets_its_tolerance(extra, kernels):
     measures them on the timed pair and the script would exit non-zero on a violation."""
     import json
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--config", "cfg1", "--fast",
-           "--no-cpu-baseline"] + extra
+           "--full", "--no-cpu-baseline"] + extra
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     d = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][0])
@@ -173,7 +208,7 @@ def test_bench_world_size_one_through_rccl():
     env = dict(os.environ, MCCNN_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29633", RANK="0",
                LOCAL_RANK="0", WORLD_SIZE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--config",
-           "cfg1", "--no-cpu-baseline"]
+           "cfg1", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, env=env)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]

@@ -10,7 +10,23 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_CKPT = "/root/reference/data/tensorboard_log/model_epoch2000.ckpt"
+# the reference's trained checkpoint (TF bundle: .index + .data), stored as a fixture; the .data file is kept in two
+# halves so that no committed file passes 1 MiB, and is joined again in a temporary directory by the tests that read it
+REF_CKPT_NAME = "model_epoch2000.ckpt"
+
+
+def _ref_ckpt(directory):
+    """Writes the fixture checkpoint's .index and joined .data file into `directory`; returns the bundle prefix."""
+    os.makedirs(str(directory), exist_ok=True)
+    prefix = os.path.join(str(directory), REF_CKPT_NAME)
+    stored = os.path.join(GOLDEN_DIR, REF_CKPT_NAME)
+    with open(stored + ".index", "rb") as f, open(prefix + ".index", "wb") as g:
+        g.write(f.read())
+    with open(prefix + ".data-00000-of-00001", "wb") as g:
+        for part in (".part0", ".part1"):
+            with open(stored + ".data-00000-of-00001" + part, "rb") as f:
+                g.write(f.read())
+    return prefix
 
 
 def test_checkpoint_npz_layers(net_layers):
@@ -20,23 +36,22 @@ def test_checkpoint_npz_layers(net_layers):
         assert w.shape == (3, 3, 64, 64) and b.shape == (64,) and w.dtype == np.float32
 
 
-@pytest.mark.skipif(not os.path.isfile(REF_CKPT + ".index"), reason="reference checkpoint only in the dev container")
-def test_tf_bundle_reader_matches_fixture(net_layers):
+def test_tf_bundle_reader_matches_fixture(net_layers, tmp_path):
     import tf_checkpoint
-    idx = tf_checkpoint.read_index(REF_CKPT)
+    ckpt = _ref_ckpt(tmp_path)
+    idx = tf_checkpoint.read_index(ckpt)
     assert len(idx) == 20 and idx["conv2/weights"]["shape"] == [3, 3, 64, 64]
     assert idx["conv1/weights"]["offset"] == 512 and idx["conv5/weights"]["size"] == 147456
-    layers = tf_checkpoint.load_fast_net_weights(REF_CKPT)     # CRC32C-verified
+    layers = tf_checkpoint.load_fast_net_weights(ckpt)     # CRC32C-verified
     for (w, b), (w2, b2) in zip(layers, net_layers):
         assert np.array_equal(w, w2) and np.array_equal(b, b2)
 
 
 def test_tf_bundle_reader_detects_corruption(tmp_path):
     import tf_checkpoint
-    if not os.path.isfile(REF_CKPT + ".index"):
-        pytest.skip("reference checkpoint only in the dev container")
+    ckpt = _ref_ckpt(tmp_path / "ref")
     for ext in (".index", ".data-00000-of-00001"):
-        data = bytearray(open(REF_CKPT + ext, "rb").read())
+        data = bytearray(open(ckpt + ext, "rb").read())
         if ext.startswith(".data"):
             data[600] ^= 0xFF
         open(str(tmp_path / ("bad.ckpt" + ext)), "wb").write(bytes(data))

@@ -6,7 +6,7 @@ for f in bench bench_fast bench_cfg1 bench_cfg3 bench_cfg4 bench_under_rocprof; 
   [ -s $S/$f.json ] && cp $S/$f.json $P/r06_$f.json
 done
 [ -s $S/prof/bench_kernel_stats.csv ] && cp $S/prof/bench_kernel_stats.csv $P/r06_bench_kernel_stats.csv && \
-  python tools/summarize_stats.py $P/r06_bench_kernel_stats.csv "rocprofv3 --kernel-trace --stats of bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-parity --no-bounds (round 6, cfg2, one MI355X)" > $P/r06_bench_kernel_stats_summary.md
+  python tools/summarize_stats.py $P/r06_bench_kernel_stats.csv "rocprofv3 --kernel-trace --stats of bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-parity --no-bounds (round 6, cfg2, one MI355X)" > $P/r06_bench_kernel_stats_summary.md
 for f in pmc_cbca_prog pmc_cbca_prog_skip pmc_cbca_prog_one_volume pmc_cbca_prog_skip_one_volume pmc_sgm_pass pmc_sgm_pass_one_volume pmc_cost_volume_exact_pairs pmc_conv3x3_split kernel_microbench; do
   [ -s $S/$f.txt ] && grep -v "amdgpu.ids" $S/$f.txt > $P/r06_$f.txt
 done

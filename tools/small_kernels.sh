@@ -1,6 +1,6 @@
 # On the GPU box: average duration of the small kernels of a pair (rocprofv3 kernel stats of a short bench run).
 export TMPDIR=/tmp; R=$PWD; rm -rf /tmp/p1; cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p1 -o b -- python $R/bench.py --steps 5 --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p1 -o b -- python $R/bench.py --full --steps 5 --no-cpu-baseline > /dev/null 2>&1
 python - <<'PY'
 import csv, glob
 f = glob.glob("/tmp/p1/**/*kernel_stats.csv", recursive=True)[0]
