@@ -362,7 +362,9 @@ def cbca_prog_build_pair(support_l, support_r, D, distance_threshold, progs, whi
     pair, after cross_arms_pair, for all iterations.  which: "full" (mccnn_cbca_prog_build_pair: what every iteration can
     run), "skip" (mccnn_cbca_prog_build_skip_pair: the second set in the same buffers, which second and later iterations
     run, cbca_prog_pair), "both" (mccnn_cbca_prog_build_both_pair: the two sets from one pass over the support words, one
-    launch of about the time of either of the others) or "both_two_launches" (the first two one after the other)."""
+    launch of about the time of either of the others) or "both_two_launches" (the first two one after the other).  The
+    buffers remember which sets they hold: cbca_prog_pair / cbca_prog_chain run the full programs in every iteration of
+    buffers built with which="full" alone."""
     H, W = support_l.shape
     _check_support(support_l, H, W, "cbca_prog_build_pair")
     _check_support(support_r, H, W, "cbca_prog_build_pair")
@@ -373,12 +375,29 @@ def cbca_prog_build_pair(support_l, support_r, D, distance_threshold, progs, whi
         hip.check(lib.mccnn_cbca_prog_build_both_pair(hip.ptr(support_l), hip.ptr(support_r), int(D), H, W,
                                                       int(distance_threshold), hip.ptr(progs[0]), hip.ptr(progs[1]),
                                                       hip.stream()), "mccnn_cbca_prog_build_both_pair")
+        _record_built(progs, ("full", "skip"))
         return progs
     for name, fn in (("full", lib.mccnn_cbca_prog_build_pair), ("skip", lib.mccnn_cbca_prog_build_skip_pair)):
         if which in (name, "both_two_launches"):
             hip.check(fn(hip.ptr(support_l), hip.ptr(support_r), int(D), H, W, int(distance_threshold), hip.ptr(progs[0]),
                          hip.ptr(progs[1]), hip.stream()), "mccnn_cbca_prog_build_%spair" % ("skip_" if name == "skip" else ""))
+    _record_built(progs, ("full", "skip") if which == "both_two_launches" else (which,))
     return progs
+
+
+def _record_built(progs, sets):
+    """Remembers on the program buffers which sets cbca_prog_build_pair has written into them.  A build of the full
+    programs forgets the skip set (it may have come from other support arms); a build of the skip set adds to what is
+    there."""
+    for p in progs:
+        p._cbca_prog_sets = (set(getattr(p, "_cbca_prog_sets", ())) | {"skip"}) if sets == ("skip",) else set(sets)
+
+
+def _skip_set_built(progs):
+    """False when cbca_prog_build_pair built these buffers without the skip set (which="full"): the aggregation then
+    runs the full programs in every iteration.  Buffers written through the C ABI alone carry no record and are
+    assumed complete (the library refuses a set that was never built)."""
+    return all("skip" in getattr(p, "_cbca_prog_sets", ("skip",)) for p in progs)
 
 
 _RIGHT_STREAMS = {}
@@ -459,7 +478,7 @@ def cbca_prog_pair(vol_l, tmp_l, support_l, vol_r, tmp_r, support_r, progs, D, i
     n = int(iterations)
     if wta_out is not None and (n < 1 or D > cbca_hwd_wta_max_d()):
         raise ValueError("cbca_prog_pair: the fused WTA needs at least one iteration and D <= %d" % cbca_hwd_wta_max_d())
-    kinds = skip_schedule(n, wta_out is not None, skip_unit_regions, refresh_first)
+    kinds = skip_schedule(n, wta_out is not None, skip_unit_regions and _skip_set_built(progs), refresh_first)
 
     def skips(it):
         return kinds[it] == "skip"
@@ -527,7 +546,7 @@ def cbca_prog_chain(vol, tmp, support, prog, D, iterations, distance_threshold, 
     H, W, Dp = vol.shape
     lib = hip.load()
     n = int(total if total is not None else iterations)
-    kinds = skip_schedule(n, fused_last, skip_unit_regions, refresh_first)
+    kinds = skip_schedule(n, fused_last, skip_unit_regions and _skip_set_built((prog,)), refresh_first)
     src, dst = vol, tmp
     waited = False
     timer = timer or _NO_TIMER

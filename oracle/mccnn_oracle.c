@@ -65,6 +65,9 @@ static float norm1(float x)
  * ========================================================================================================= */
 void orc_cost_volume(const float *fl, const float *fr, int H, int W, int C, int D, float *lcv, float *rcv)
 {
+    /* The border fills below index columns d - 1 and W - d - 3 .. W - d: outside [0, W) once D > W - 2, where the
+     * reference is degenerate too.  Such a call writes nothing (the Python wrapper refuses it before). */
+    if (D < 1 || D > W - 2) return;
     float *prod = (float *)malloc(sizeof(float) * (size_t)C);
     memset(lcv, 0, sizeof(float) * (size_t)D * H * W); /* pf:82 np.zeros */
     memset(rcv, 0, sizeof(float) * (size_t)D * H * W); /* pf:102 */

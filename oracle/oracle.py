@@ -84,8 +84,14 @@ def compute_features(left_image, right_image, patch_height, patch_width, layers)
 
 
 def compute_cost_volume(featuresl, featuresr, ndisp):
+    """pf:78-113.  Refuses ndisp > W - 2 (ValueError): the right volume's border fill (pf:105-106) reads and writes
+    columns left of 0 there, and orc_cost_volume writes nothing for that range."""
     fl, fr = _f32(featuresl), _f32(featuresr)
     H, W, C = fl.shape
+    if fr.shape != fl.shape:
+        raise ValueError("compute_cost_volume: features of different shapes %s and %s" % (fl.shape, fr.shape))
+    if not 1 <= int(ndisp) <= W - 2:
+        raise ValueError("compute_cost_volume: ndisp=%d outside [1, W - 2] = [1, %d]" % (int(ndisp), W - 2))
     lcv = np.empty((ndisp, H, W), dtype=np.float32)
     rcv = np.empty((ndisp, H, W), dtype=np.float32)
     lib().orc_cost_volume(_p(fl), _p(fr), H, W, C, int(ndisp), _p(lcv), _p(rcv))
@@ -227,16 +233,23 @@ def bilateral_filter(left_image, left_disparity_map, filter_height, filter_width
     return out
 
 
-def match_pair(left_image, right_image, ndisp, layers, args=None, return_all=False):
-    """The timed region of match.py:129-179 on standardised [H,W,1] images."""
-    a = dict(cbca_intensity=0.02, cbca_distance=14, cbca_num_iterations1=2, cbca_num_iterations2=16,
-             sgm_P1=2.3, sgm_P2=55.9, sgm_Q1=4, sgm_Q2=8, sgm_D=0.08, sgm_V=1.5, blur_sigma=6, blur_threshold=2,
-             patch_size=2 * len(layers) + 1)
+MATCH_DEFAULTS = dict(cbca_intensity=0.02, cbca_distance=14, cbca_num_iterations1=2, cbca_num_iterations2=16,
+                      sgm_P1=2.3, sgm_P2=55.9, sgm_Q1=4, sgm_Q2=8, sgm_D=0.08, sgm_V=1.5, blur_sigma=6, blur_threshold=2)
+"""match.py:32-43 (the same keys and values as stereo_device.DEFAULT_HP)."""
+
+
+def match_from_features(left_image, right_image, featuresl, featuresr, ndisp, args=None, return_all=False):
+    """The timed region of match.py:129-179 from the conv features on: cost volume, aggregation x
+    cbca_num_iterations1, SGM_average, aggregation x cbca_num_iterations2, WTA, interpolation, sub-pixel, median,
+    bilateral.  `args` overrides MATCH_DEFAULTS; return_all also returns {stage: result} (volumes as (left, right))."""
+    a = dict(MATCH_DEFAULTS)
     if args:
+        unknown = set(args) - set(a) - {"patch_size"}
+        if unknown:
+            raise ValueError("match_from_features: unknown arguments %s" % sorted(unknown))
         a.update(args)
     st = {}
-    fl, fr = compute_features(left_image, right_image, a["patch_size"], a["patch_size"], layers)
-    lcv, rcv = compute_cost_volume(fl, fr, ndisp)
+    lcv, rcv = compute_cost_volume(featuresl, featuresr, ndisp)
     st["cost_volume"] = (lcv.copy(), rcv.copy()) if return_all else None
     lcv, rcv = cost_volume_aggregation(left_image, right_image, lcv, rcv, a["cbca_intensity"], a["cbca_distance"],
                                        a["cbca_num_iterations1"])
@@ -258,3 +271,13 @@ def match_pair(left_image, right_image, ndisp, layers, args=None, return_all=Fal
     db = bilateral_filter(left_image, dm, 5, 5, 0, a["blur_sigma"], a["blur_threshold"])
     st["bilateral"] = db
     return (db, st) if return_all else db
+
+
+def match_pair(left_image, right_image, ndisp, layers, args=None, return_all=False):
+    """The timed region of match.py:129-179 on standardised [H,W,1] images: the conv features, then
+    match_from_features."""
+    a = dict(patch_size=2 * len(layers) + 1)
+    if args:
+        a.update(args)
+    fl, fr = compute_features(left_image, right_image, a["patch_size"], a["patch_size"], layers)
+    return match_from_features(left_image, right_image, fl, fr, ndisp, args=args, return_all=return_all)

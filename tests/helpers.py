@@ -85,3 +85,59 @@ def module_setting(module, name, value):
         yield
     finally:
         setattr(module, name, previous)
+
+
+def _host(a):
+    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+
+def stagewise(keep, L, R, D, o, hp=None, features=None):
+    """Feeds every stage output a matcher handed out through `keep` to the CPU checker's next stage (`o`: the oracle
+    module; `hp`: the matcher's hyper-parameters, default match.py's).  Returns {stage: max |gpu - cpu|} in stage order
+    (0.0 = all bits equal; a zero of the other sign counts as the smallest subnormal).  features=(fl, fr): the cost
+    volume is checked against the oracle's from these features too."""
+    a = dict(o.MATCH_DEFAULTS)
+    a.update(hp or {})
+    tau, dist = a["cbca_intensity"], a["cbca_distance"]
+    d = {}
+
+    def diff(x, y):
+        x = _host(x)
+        if bits_strict(x, y):
+            return 0.0
+        m = float(np.nanmax(np.abs(x.astype(np.float64) - y))) if x.shape == np.shape(y) else float("inf")
+        return m if m > 0.0 else float(np.spacing(np.float32(0)))     # a zero of the other sign: not 'all bits equal'
+
+    cv = [_host(t) for t in keep["cv"]]
+    if features is not None:
+        ocv = o.compute_cost_volume(_host(features[0]), _host(features[1]), D)
+        d["cost_volume"] = max(diff(cv[0], ocv[0]), diff(cv[1], ocv[1]))
+    c1 = o.cost_volume_aggregation(L, R, cv[0], cv[1], tau, dist, a["cbca_num_iterations1"])
+    d["cbca_x%d" % a["cbca_num_iterations1"]] = max(diff(keep["cbca1"][0], c1[0]), diff(keep["cbca1"][1], c1[1]))
+    g1 = [_host(t) for t in keep["cbca1"]]
+    s = o.SGM_average(g1[0].copy(), g1[1].copy(), L, R, a["sgm_P1"], a["sgm_P2"], a["sgm_Q1"], a["sgm_Q2"], a["sgm_D"],
+                      a["sgm_V"])
+    d["sgm"] = max(diff(keep["sgm"][0], s[0]), diff(keep["sgm"][1], s[1]))
+    gs = [_host(t) for t in keep["sgm"]]
+    n2 = a["cbca_num_iterations2"]
+    c2 = o.cost_volume_aggregation(L, R, gs[0], gs[1], tau, dist, n2)
+    d["cbca_x%d" % n2] = max(diff(keep["cbca2"][0], c2[0]), diff(keep["cbca2"][1], c2[1]))
+    d["cbca_x%d_spacings_of_max_input" % n2] = d["cbca_x%d" % n2] / float(np.spacing(np.float32(np.abs(gs[0]).max())))
+    g2 = [_host(t) for t in keep["cbca2"]]
+    dl, dr = o.disparity_prediction(g2[0], g2[1])
+    gdl, gdr = _host(keep["wta"][0]), _host(keep["wta"][1])
+    d["wta_mismatches"] = int((gdl != dl).sum() + (gdr != dr).sum())
+    di = o.interpolation(gdl, gdr, D)
+    d["interpolation"] = diff(keep["interp"], di)
+    ds = o.subpixel_enhance(_host(keep["interp"]), g2[0])
+    d["subpixel"] = diff(keep["subpixel"], ds)
+    dm = o.median_filter(_host(keep["subpixel"]), 5, 5)
+    d["median"] = diff(keep["median"], dm)
+    db = o.bilateral_filter(L, _host(keep["median"]), 5, 5, 0, a["blur_sigma"], a["blur_threshold"])
+    d["bilateral"] = diff(keep["bilateral"], db)
+    return d
+
+
+def first_differing_stage(d):
+    """The first stage of a stagewise() record whose output differs from the CPU checker's, or None."""
+    return next((k for k, v in d.items() if v != 0 and not k.endswith("_spacings_of_max_input")), None)

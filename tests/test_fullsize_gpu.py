@@ -16,7 +16,7 @@ import torch
 import tolerances as tol
 
 from conftest import ROOT
-from helpers import assert_bits, bits_strict, module_setting
+from helpers import assert_bits, module_setting, stagewise
 
 pytestmark = pytest.mark.gpu
 
@@ -35,44 +35,6 @@ def _dump():
             json.dump(RECORD, f, indent=1, sort_keys=True)
     except OSError:
         pass
-
-
-def _stagewise(keep, L, R, D, o, exact):
-    """Feeds every GPU stage output to the CPU checker's next stage; returns {stage: max |gpu - cpu|} (0.0 = all bits
-    equal) and the CPU results of the last stages."""
-    hp = dict(tau=0.02, dist=14)
-    d = {}
-
-    def diff(a, b):
-        a = a.cpu().numpy() if torch.is_tensor(a) else a
-        if bits_strict(a, b):
-            return 0.0
-        m = float(np.nanmax(np.abs(a.astype(np.float64) - b)))
-        return m if m > 0.0 else float(np.spacing(np.float32(0)))     # a zero of the other sign: not 'all bits equal'
-
-    cv = [t.cpu().numpy() for t in keep["cv"]]
-    c1 = o.cost_volume_aggregation(L, R, cv[0], cv[1], hp["tau"], hp["dist"], 2)
-    d["cbca_x2"] = max(diff(keep["cbca1"][0], c1[0]), diff(keep["cbca1"][1], c1[1]))
-    g1 = [t.cpu().numpy() for t in keep["cbca1"]]
-    s = o.SGM_average(g1[0].copy(), g1[1].copy(), L, R, 2.3, 55.9, 4, 8, 0.08, 1.5)
-    d["sgm"] = max(diff(keep["sgm"][0], s[0]), diff(keep["sgm"][1], s[1]))
-    gs = [t.cpu().numpy() for t in keep["sgm"]]
-    c2 = o.cost_volume_aggregation(L, R, gs[0], gs[1], hp["tau"], hp["dist"], 16)
-    d["cbca_x16"] = max(diff(keep["cbca2"][0], c2[0]), diff(keep["cbca2"][1], c2[1]))
-    d["cbca_x16_spacings_of_max_input"] = d["cbca_x16"] / float(np.spacing(np.float32(np.abs(gs[0]).max())))
-    g2 = [t.cpu().numpy() for t in keep["cbca2"]]
-    dl, dr = o.disparity_prediction(g2[0], g2[1])
-    d["wta_mismatches"] = int((keep["wta"][0].cpu().numpy() != dl).sum() + (keep["wta"][1].cpu().numpy() != dr).sum())
-    gdl, gdr = keep["wta"][0].cpu().numpy(), keep["wta"][1].cpu().numpy()
-    di = o.interpolation(gdl, gdr, D)
-    d["interpolation"] = diff(keep["interp"], di)
-    ds = o.subpixel_enhance(keep["interp"].cpu().numpy(), g2[0])
-    d["subpixel"] = diff(keep["subpixel"], ds)
-    dm = o.median_filter(keep["subpixel"].cpu().numpy(), 5, 5)
-    d["median"] = diff(keep["median"], dm)
-    db = o.bilateral_filter(L, keep["median"].cpu().numpy(), 5, 5, 0, 6, 2)
-    d["bilateral"] = diff(keep["bilateral"], db)
-    return d
 
 
 def test_cfg1_whole_pair_stage_by_stage(net_layers):
@@ -95,7 +57,7 @@ def test_cfg1_whole_pair_stage_by_stage(net_layers):
     ocv = o.compute_cost_volume(fl[0].cpu().numpy(), fl[1].cpu().numpy(), D)
     assert_bits(keep["cv"][0].cpu().numpy(), ocv[0], "cfg1 cost volume L")
     assert_bits(keep["cv"][1].cpu().numpy(), ocv[1], "cfg1 cost volume R")
-    d = _stagewise(keep, L, R, D, o, exact=True)
+    d = stagewise(keep, L, R, D, o)
     RECORD["cfg1_exact_stagewise_max_abs"] = d
     bad = {k: v for k, v in d.items() if v != 0}
     assert not bad, "bit-exact variants differ from the CPU checker: %s" % bad
@@ -110,7 +72,7 @@ def test_cfg1_whole_pair_stage_by_stage(net_layers):
     fast_map = m.match(dev(L), dev(R), D, keep=keep).cpu().numpy()
     cv_err = max(float(np.abs(keep["cv"][0].cpu().numpy() - ocv[0]).max()),
                  float(np.abs(keep["cv"][1].cpu().numpy() - ocv[1]).max()))
-    d = _stagewise(keep, L, R, D, o, exact=False)
+    d = stagewise(keep, L, R, D, o)
     d["cost_volume_mfma"] = cv_err
     flips = int((keep["wta"][0].cpu().numpy() != exact_wta).sum())
     close = float(np.isclose(fast_map, exact_map, atol=1e-3, equal_nan=True).mean())

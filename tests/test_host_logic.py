@@ -298,3 +298,42 @@ def test_shard_indices_cover_window_once():
         assert got == list(range(2, 10))                              # inclusive window, clipped to the list
         sizes = [len(shard_indices(2, 12, 10, r, world)) for r in range(world)]
         assert max(sizes) - min(sizes) <= 1
+
+
+def test_oracle_cost_volume_refuses_degenerate_disparity_range():
+    """pf:105-106 fills the right volume's border from columns W-d-3 .. W-d: for d > W - 2 those lie left of column 0,
+    where the CPU checker used to write outside its arrays (and abort later, in an unrelated call).  The Python wrapper
+    refuses that range, the C function writes nothing for it, and W - 2 still gives a finite volume."""
+    import ctypes
+    import oracle as o
+    rng = np.random.default_rng(0)
+    H, W, C = 4, 10, 8
+    f = rng.standard_normal((H, W, C)).astype(np.float32)
+    for nd in (W - 1, W, W + 5, 0):
+        with pytest.raises(ValueError):
+            o.compute_cost_volume(f, f, nd)
+    with pytest.raises(ValueError):
+        o.compute_cost_volume(np.zeros((H, W, C), np.float32), np.zeros((H, W, C), np.float32), 9)
+    lcv, rcv = o.compute_cost_volume(f, f[:, ::-1], W - 2)
+    assert lcv.shape == rcv.shape == (W - 2, H, W)
+    assert np.isfinite(lcv).all() and np.isfinite(rcv).all()
+    # the C entry point on its own: nothing written for D = W - 1 (a sentinel-filled output stays as it was)
+    nd = W - 1
+    sentinel = np.full((nd, H, W), 7.0, np.float32)
+    lo, ro = sentinel.copy(), sentinel.copy()
+    p = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))      # noqa: E731
+    o.lib().orc_cost_volume(p(f), p(f), H, W, C, nd, p(lo), p(ro))
+    assert np.array_equal(lo, sentinel) and np.array_equal(ro, sentinel)
+    # and the whole chain from features refuses it too
+    L = rng.standard_normal((H, W, 1)).astype(np.float32)
+    with pytest.raises(ValueError):
+        o.match_from_features(L, L, f, f, W - 1)
+
+
+def test_oracle_match_defaults_are_the_matchers():
+    """oracle.match_from_features / match_pair default to match.py's hyper-parameters, the ones StereoMatcher uses."""
+    import oracle as o
+    import stereo_device as sd
+    assert o.MATCH_DEFAULTS == sd.DEFAULT_HP
+    with pytest.raises(ValueError):
+        o.match_from_features(None, None, None, None, 4, args=dict(cbca_iterations=3))

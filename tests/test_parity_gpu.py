@@ -45,22 +45,19 @@ def dev(a):
 # (1) golden vectors
 # ---------------------------------------------------------------------------------------------------------------
 def test_golden_cost_volume_exact(pf, golden_cases):
-    pf.COST_VOLUME_MODE = "exact"
-    for name, g in golden_cases:
-        l, r = pf.compute_cost_volume(g["fl"], g["fr"], g["cv_l"].shape[0])
-        assert_bits(l, g["cv_l"], name + " cv_l")
-        assert_bits(r, g["cv_r"], name + " cv_r")
+    with module_setting(pf, "COST_VOLUME_MODE", "exact"):
+        for name, g in golden_cases:
+            l, r = pf.compute_cost_volume(g["fl"], g["fr"], g["cv_l"].shape[0])
+            assert_bits(l, g["cv_l"], name + " cv_l")
+            assert_bits(r, g["cv_r"], name + " cv_r")
 
 
 def test_golden_cost_volume_mfma(pf, golden_cases):
-    pf.COST_VOLUME_MODE = "mfma"
-    try:
+    with module_setting(pf, "COST_VOLUME_MODE", "mfma"):
         for name, g in golden_cases:
             l, r = pf.compute_cost_volume(g["fl"], g["fr"], g["cv_l"].shape[0])
             assert np.abs(l - g["cv_l"]).max() <= 2e-6, name
             assert np.abs(r - g["cv_r"]).max() <= 2e-6, name
-    finally:
-        pf.COST_VOLUME_MODE = "exact"
 
 
 def test_golden_cross_region(pf, sd, golden_cases):
@@ -296,15 +293,12 @@ def test_oracle_cost_volume(pf, H, W, D):
     fl /= np.linalg.norm(fl, axis=-1, keepdims=True)
     fr /= np.linalg.norm(fr, axis=-1, keepdims=True)
     ol, orr = o.compute_cost_volume(fl, fr, D)
-    pf.COST_VOLUME_MODE = "exact"
-    gl, gr = pf.compute_cost_volume(fl, fr, D)
+    with module_setting(pf, "COST_VOLUME_MODE", "exact"):
+        gl, gr = pf.compute_cost_volume(fl, fr, D)
     assert_bits(gl, ol, "cost volume L exact")
     assert_bits(gr, orr, "cost volume R exact")
-    pf.COST_VOLUME_MODE = "mfma"
-    try:
+    with module_setting(pf, "COST_VOLUME_MODE", "mfma"):
         ml, mr = pf.compute_cost_volume(fl, fr, D)
-    finally:
-        pf.COST_VOLUME_MODE = "exact"
     assert np.abs(ml - ol).max() <= 2e-6 and np.abs(mr - orr).max() <= 2e-6
 
 
@@ -601,15 +595,12 @@ def test_oracle_random_shapes_fast_and_exact_kernels(pf, sd, H, W, D):
     fl /= np.linalg.norm(fl, axis=-1, keepdims=True)
     fr /= np.linalg.norm(fr, axis=-1, keepdims=True)
     ol, orr = o.compute_cost_volume(fl, fr, D)
-    pf.COST_VOLUME_MODE = "exact"
-    gl, gr = pf.compute_cost_volume(fl, fr, D)
+    with module_setting(pf, "COST_VOLUME_MODE", "exact"):
+        gl, gr = pf.compute_cost_volume(fl, fr, D)
     assert_bits(gl, ol, "cost volume L exact %dx%dx%d" % (H, W, D))
     assert_bits(gr, orr, "cost volume R exact %dx%dx%d" % (H, W, D))
-    pf.COST_VOLUME_MODE = "mfma"
-    try:
+    with module_setting(pf, "COST_VOLUME_MODE", "mfma"):
         ml, mr = pf.compute_cost_volume(fl, fr, D)
-    finally:
-        pf.COST_VOLUME_MODE = "exact"
     assert np.abs(ml - ol).max() <= 2e-6 and np.abs(mr - orr).max() <= 2e-6, (H, W, D)
     # aggregation: reference order bit-exact, streaming kernel within the stated tolerance
     cl, cr = o.cost_volume_aggregation(L, R, ol, orr, 0.02, 14, 2)
