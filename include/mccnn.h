@@ -48,7 +48,7 @@ typedef void *mccnn_stream_t; /* hipStream_t */
 #define MCCNN_ABI_VERSION 7 /* 2: window-mask plane, *_hwd entry points; 3: saturation flags; 4: program-driven CBCA; 5: skip programs; 6: one-volume launches; 7: refresh launches, SGM flag planes as a call of their own */
 
 #define MCCNN_E_INVALID (-1)     /* bad argument (null pointer, non-positive size, unsupported shape) */
-#define MCCNN_E_UNSUPPORTED (-2) /* shape outside what the kernels were built for (e.g. D > 512 for SGM) */
+#define MCCNN_E_UNSUPPORTED (-2) /* shape outside what the kernels were built for (e.g. D > 1024 for SGM) */
 #define MCCNN_E_SCRATCH (-3)     /* scratch buffer too small */
 
 #define MCCNN_SIDE_LEFT 0  /* the reference's choice == "L" */
@@ -71,7 +71,7 @@ int mccnn_cost_volume(const float *fl, const float *fr, int H, int W, int C, int
 
 /* The same volumes written pixel-major ("HWD" [H][W][Dp], the layout the bit-exact variant keeps from here to WTA),
  * bit-identical to mccnn_cost_volume(mode) followed by mccnn_dhw_to_hwd for d < D (the Dp - D pad entries of a pixel
- * are not written), for MCCNN_CV_EXACT and (ABI 5) MCCNN_CV_MFMA alike; D <= 512. */
+ * are not written), for MCCNN_CV_EXACT and (ABI 5) MCCNN_CV_MFMA alike; D <= 1024. */
 int mccnn_cost_volume_hwd(const float *fl, const float *fr, int H, int W, int C, int D, float *lcv_hwd, float *rcv_hwd,
                           int mode, mccnn_stream_t stream);
 
@@ -258,7 +258,9 @@ int mccnn_hwd_to_dhw(const float *hwd, float *dhw, int D, int H, int W, mccnn_st
  * p1, p2, q1, q2, thr are the float32 roundings NumPy applies to the Python scalars (pass float(sgm_P1/sgm_V)
  * as p1 for the vertical directions, pf:204).  float32 add/min/sub only, un-fused: bit-exact vs the reference.
  * Up to two volumes (e.g. left + right) are advanced by one launch so the chip sees 2x the scanlines:
- * n_jobs in {1,2}; job j updates vol_hwd[j] as side[j].  scratch >= mccnn_sgm_scratch_bytes(H,W,D). 2<=D<=512. */
+ * n_jobs in {1,2}; job j updates vol_hwd[j] as side[j].  scratch >= mccnn_sgm_scratch_bytes(H,W,D). 2<=D<=1024.
+ * No limit on the volume's size: vertical scanlines of volumes of 4 GiB or more run a variant that rebases its buffer
+ * descriptor every few steps (same bits). */
 size_t mccnn_sgm_scratch_bytes(int H, int W, int D);
 int mccnn_sgm_pass(const float *image_left, const float *image_right, float *const *vol_hwd, const int *side,
                    int n_jobs, int D, int H, int W, int rh, int rw, float p1, float p2, float q1, float q2, float thr,
@@ -275,7 +277,8 @@ int mccnn_sgm_pass_flagged(float *const *vol_hwd, const int *side, int n_jobs, i
 
 /* The first direction of SGM_average, r = (0,1) (pf:194-195, 216-217), fused with the layout change: reads the
  * plane-major volumes vol_dhw[j] (left untouched) and writes the pixel-major vol_hwd[j], i.e. it replaces
- * mccnn_dhw_to_hwd + mccnn_sgm_pass(rh=0, rw=1) and saves one full read + write of every volume.  2 <= D <= 256. */
+ * mccnn_dhw_to_hwd + mccnn_sgm_pass(rh=0, rw=1) and saves one full read + write of every volume.  2 <= D <= 256.
+ * Volumes of 4 GiB or more (beyond the reach of the fused gather) run as exactly those two calls: same result. */
 int mccnn_sgm_first_pass(const float *image_left, const float *image_right, const float *const *vol_dhw,
                          float *const *vol_hwd, const int *side, int n_jobs, int D, int H, int W, float p1, float p2,
                          float q1, float q2, float thr, void *scratch, size_t scratch_bytes, mccnn_stream_t stream);

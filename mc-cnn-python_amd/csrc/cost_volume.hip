@@ -760,7 +760,12 @@ extern "C" int mccnn_cost_volume_hwd(const float *fl, const float *fr, int H, in
                   "beyond that), W=%d", D, W);
     MCCNN_REQUIRE(mode == MCCNN_CV_EXACT || mode == MCCNN_CV_MFMA, MCCNN_E_INVALID, "mccnn_cost_volume_hwd: unknown mode %d",
                   mode);
-    MCCNN_REQUIRE(D <= 512, MCCNN_E_UNSUPPORTED, "mccnn_cost_volume_hwd: D=%d > 512", D);
+#ifdef CV_FILL_FOUR_PER_LANE     // (its sweep holds at most two 256-disparity groups)
+    constexpr int kMaxD = 512;
+#else                            // the product kernels walk 64-disparity tiles, the fill kernel 64-disparity waves
+    constexpr int kMaxD = 1024;
+#endif
+    MCCNN_REQUIRE(D <= kMaxD, MCCNN_E_UNSUPPORTED, "mccnn_cost_volume_hwd: D=%d > %d", D, kMaxD);
     const int Dp = mccnn_hwd_pitch(D);
     MCCNN_REQUIRE((size_t)W * Dp * 4 < ((size_t)1 << 31), MCCNN_E_UNSUPPORTED,
                   "mccnn_cost_volume_hwd: a %d x %d row exceeds a buffer descriptor's reach", W, D);

@@ -130,10 +130,17 @@ typedef uint32_t sgm_u32x3 __attribute__((ext_vector_type(3)));
 template <int VPL> struct SgmVec {
     float v[VPL];
 };
-template <int NG, int PF, bool FULL, int VPL = 4>
+// FAR = true: the same recurrence on volumes whose scanline does not fit the 32-bit reach of one descriptor
+// (H*W*Dp*4 >= 4 GiB; only vertical scanlines get there, a row spans W*Dp*4 bytes).  The descriptor is rebuilt
+// from the 64-bit base of the line at the start of every block of PF steps and spans only the scan positions that block
+// touches: the PF steps it stores and the PF steps it prefetches (2 PF - 1 lines: at most 150 MB at W = 3072).
+// The per-lane voffset and the wave-uniform soffset stay 32-bit; soffset counts from the window's lowest scan position
+// (the descending direction's window starts at pos(tb)).  Loads in flight keep the descriptor they were issued with.
+template <int NG, int PF, bool FULL, int VPL = 4, bool FAR = false>
 __global__ __launch_bounds__(64) void sgm_pass_kernel(const SgmParams P)
 {
     static_assert(VPL == 4 || (VPL == 3 && NG == 1), "three disparities per lane: one group only");
+    static_assert(!FAR || VPL == 4, "far scanlines: four disparities per lane");
     typedef SgmVec<VPL> vec;
     const SgmJob J = P.job[blockIdx.y];
     const int lane = threadIdx.x;
@@ -147,9 +154,15 @@ __global__ __launch_bounds__(64) void sgm_pass_kernel(const SgmParams P)
     const unsigned fstride = horiz ? 1u : (unsigned)P.pitch;
     const size_t line_pix = horiz ? (size_t)line * P.W : (size_t)line;              // pixel at scan position 0
     const size_t line_flag = horiz ? (size_t)line * P.pitch + P.pad : (size_t)P.pad + line;
-    const unsigned span = (unsigned)min((size_t)0xFFFFFFFFu, (size_t)nsteps * vstride + (size_t)P.Dp * 4u);
-    const __amdgpu_buffer_rsrc_t rs_vol =
-        __builtin_amdgcn_make_buffer_rsrc(J.vol + line_pix * P.Dp, 0, (int)span, 0x00020000);
+    const unsigned span = FAR ? 0u : (unsigned)min((size_t)0xFFFFFFFFu, (size_t)nsteps * vstride + (size_t)P.Dp * 4u);
+    __amdgpu_buffer_rsrc_t rs_vol = __builtin_amdgcn_make_buffer_rsrc(J.vol + line_pix * P.Dp, 0, (int)span, 0x00020000);
+    unsigned vlo = 0;   // FAR: scan position at the base of rs_vol
+    auto window = [&](int ta, int tb) {   // FAR: rs_vol over the scan positions of steps ta <= tb
+        vlo = (unsigned)(fwd ? ta : nsteps - tb);
+        const size_t pstride = horiz ? (size_t)P.Dp : (size_t)P.W * P.Dp;   // floats between scan positions
+        rs_vol = __builtin_amdgcn_make_buffer_rsrc(J.vol + line_pix * P.Dp + vlo * pstride, 0,
+                                                   (int)((unsigned)(tb - ta) * vstride + (unsigned)P.Dp * 4u), 0x00020000);
+    };
     const unsigned fspan = (unsigned)((size_t)nsteps * fstride + 1u);
     // the B lookups reach up to pad bytes to either side of the pixel: base the descriptor pad bytes early
     const __amdgpu_buffer_rsrc_t rs_a =
@@ -188,18 +201,25 @@ __global__ __launch_bounds__(64) void sgm_pass_kernel(const SgmParams P)
         return r;
     };
     auto pos = [&](int t) { return (unsigned)(fwd ? t : nsteps - t); };
+    auto soff = [&](int t) {   // byte offset of step t's pixel from the base of rs_vol
+        if constexpr (FAR)
+            return (pos(t) - vlo) * vstride;
+        else
+            return pos(t) * vstride;
+    };
     auto load_vol = [&](int g, int t) {
         vec r;
         if constexpr (VPL == 4) {
-            const sgm_u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(rs_vol, voff[g], pos(t) * vstride, kNT);
+            const sgm_u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(rs_vol, voff[g], soff(t), kNT);
             r.v[0] = __uint_as_float(u.x); r.v[1] = __uint_as_float(u.y); r.v[2] = __uint_as_float(u.z); r.v[3] = __uint_as_float(u.w);
         } else {
-            const sgm_u32x3 u = __builtin_amdgcn_raw_buffer_load_b96(rs_vol, voff[g], pos(t) * vstride, kNT);
+            const sgm_u32x3 u = __builtin_amdgcn_raw_buffer_load_b96(rs_vol, voff[g], soff(t), kNT);
             r.v[0] = __uint_as_float(u.x); r.v[1] = __uint_as_float(u.y); r.v[2] = __uint_as_float(u.z);
         }
         return r;
     };
 
+    if constexpr (FAR) window(0, min(PF, nsteps));   // the seed line and the first PF steps
     vec prev[NG];
 #pragma unroll
     for (int g = 0; g < NG; ++g) prev[g] = mask_tail(load_vol(g, 0), g);
@@ -227,6 +247,7 @@ __global__ __launch_bounds__(64) void sgm_pass_kernel(const SgmParams P)
     for (int k = 0; k < PF; ++k) issue(k, min(1 + k, nsteps));
 
     for (int t0 = 1; t0 <= nsteps; t0 += PF) {
+        if constexpr (FAR) window(t0, min(t0 + 2 * PF - 1, nsteps));   // stores t0 .. t0+PF-1, prefetches .. t0+2PF-1
 #pragma unroll
         for (int k = 0; k < PF; ++k) {
             const int t = t0 + k;
@@ -267,11 +288,11 @@ __global__ __launch_bounds__(64) void sgm_pass_kernel(const SgmParams P)
                     sgm_u32x4 ou;
                     ou.x = __float_as_uint(o.v[0]); ou.y = __float_as_uint(o.v[1]);
                     ou.z = __float_as_uint(o.v[2]); ou.w = __float_as_uint(o.v[3]);
-                    buffer_store_b128<kNT>(ou, rs_vol, voff[g], pos(t) * vstride);
+                    buffer_store_b128<kNT>(ou, rs_vol, voff[g], soff(t));
                 } else {
                     sgm_u32x3 ou;
                     ou.x = __float_as_uint(o.v[0]); ou.y = __float_as_uint(o.v[1]); ou.z = __float_as_uint(o.v[2]);
-                    buffer_store_b96<kNT>(ou, rs_vol, voff[g], pos(t) * vstride);
+                    buffer_store_b96<kNT>(ou, rs_vol, voff[g], soff(t));
                 }
                 lm = vmin(lm, vec_min(o));
             }
@@ -527,6 +548,7 @@ __global__ __launch_bounds__(256) void transpose_f4_kernel(const float *__restri
     }
 }
 
+constexpr int kSgmMaxD = 1024;   // four 256-disparity groups per lane (sgm_pass_kernel<4, ...>)
 static inline int flag_pad(int D) { return (D + 3 + 15) & ~15; }  // >= D+3: the packed 4-byte read may start 3 early
 
 }  // namespace mccnn
@@ -556,10 +578,12 @@ extern "C" int mccnn_hwd_to_dhw(const float *hwd, float *dhw, int D, int H, int 
     MCCNN_REQUIRE(D > 0 && H > 0 && W > 0, MCCNN_E_INVALID, "mccnn_hwd_to_dhw: non-positive size");
     const long N = (long)H * W;
     const int Dp = mccnn_hwd_pitch(D);
-    if ((N & 3) == 0 && ((uintptr_t)dhw & 15) == 0 && ((uintptr_t)hwd & 15) == 0)   // in: [N][Dp], out: [D][N]
 #ifndef SGM_T_BACK
 #define SGM_T_BACK 128
 #endif
+    // in: [N][Dp], out: [D][N]; the 16-byte transpose puts pixels on grid.y, so past 65535 x SGM_T_BACK pixels the plain
+    // kernel takes over
+    if ((N & 3) == 0 && ((uintptr_t)dhw & 15) == 0 && ((uintptr_t)hwd & 15) == 0 && cdiv(N, SGM_T_BACK) <= 65535)
         hipLaunchKernelGGL(transpose_f4_kernel<SGM_T_BACK>, dim3(cdiv(Dp, 64), cdiv(N, SGM_T_BACK)), dim3(256), 0,
                            (hipStream_t)stream, hwd, dhw, N, (long)Dp, (long)Dp, N, (long)D, N);   // 512-byte runs
     else
@@ -582,8 +606,8 @@ static int sgm_launch_flags(const char *who, const float *image_left, const floa
     using namespace mccnn;
     MCCNN_REQUIRE(image_left && image_right && flags, MCCNN_E_INVALID, "%s: null pointer", who);
     MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "%s: non-positive size", who);
-    MCCNN_REQUIRE(D >= 2 && D <= 512, MCCNN_E_UNSUPPORTED,
-                  "%s: D=%d outside [2,512] (the reference itself needs D >= 2, pf:550)", who, D);
+    MCCNN_REQUIRE(D >= 2 && D <= kSgmMaxD, MCCNN_E_UNSUPPORTED,
+                  "%s: D=%d outside [2,%d] (the reference itself needs D >= 2, pf:550)", who, D, kSgmMaxD);
     MCCNN_REQUIRE((rh == 0 && (rw == 1 || rw == -1)) || (rw == 0 && (rh == 1 || rh == -1)), MCCNN_E_INVALID,
                   "%s: r=(%d,%d) is not an axis-aligned unit step (pf:484)", who, rh, rw);
     MCCNN_REQUIRE(flags_bytes >= mccnn_sgm_scratch_bytes(H, W, D), MCCNN_E_SCRATCH, "%s: scratch %zu < %zu bytes", who,
@@ -607,8 +631,8 @@ static int sgm_launch_pass(const char *who, float *const *vol_hwd, const int *si
     MCCNN_REQUIRE(vol_hwd && side && flags, MCCNN_E_INVALID, "%s: null pointer", who);
     MCCNN_REQUIRE(n_jobs == 1 || n_jobs == 2, MCCNN_E_INVALID, "%s: n_jobs=%d must be 1 or 2", who, n_jobs);
     MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "%s: non-positive size", who);
-    MCCNN_REQUIRE(D >= 2 && D <= 512, MCCNN_E_UNSUPPORTED,
-                  "%s: D=%d outside [2,512] (the reference itself needs D >= 2, pf:550)", who, D);
+    MCCNN_REQUIRE(D >= 2 && D <= kSgmMaxD, MCCNN_E_UNSUPPORTED,
+                  "%s: D=%d outside [2,%d] (the reference itself needs D >= 2, pf:550)", who, D, kSgmMaxD);
     MCCNN_REQUIRE((rh == 0 && (rw == 1 || rw == -1)) || (rw == 0 && (rh == 1 || rh == -1)), MCCNN_E_INVALID,
                   "%s: r=(%d,%d) is not an axis-aligned unit step (pf:484)", who, rh, rw);
     MCCNN_REQUIRE(flags_bytes >= mccnn_sgm_scratch_bytes(H, W, D), MCCNN_E_SCRATCH, "%s: scratch %zu < %zu bytes", who,
@@ -635,8 +659,6 @@ static int sgm_launch_pass(const char *who, float *const *vol_hwd, const int *si
     const int nlines = rh == 0 ? H : W;
     if ((rh == 0 ? W : H) < 2) return 0;  // nothing to scan
     const dim3 grid(nlines, n_jobs), block(64);
-    MCCNN_REQUIRE((size_t)H * W * P.Dp * 4 < ((size_t)1 << 32), MCCNN_E_UNSUPPORTED,
-                  "%s: %dx%dx%d volume exceeds the 4 GiB reach of a buffer descriptor", who, W, H, D);
     // steps in flight: 8, 12 and 16 measure the same at 750x500x256 (0.30 / 0.29 ms per pass: 1000-1500 scanline waves);
     // a 1242x375 pair has only 750 row scanlines - fewer waves than SIMDs - and its horizontal passes gain from 24 steps
     // (0.388 -> 0.342 ms); two disparity groups per lane (D > 256) take 12 (vertical 2.17 -> 2.06 ms at 1500x1000x400)
@@ -646,6 +668,39 @@ static int sgm_launch_pass(const char *who, float *const *vol_hwd, const int *si
 #ifndef SGM_PF_2G
 #define SGM_PF_2G 12
 #endif
+    // three and four groups (512 < D <= 1024): the step buffers cost 5 VGPRs per group and step (a 16-byte vector + the
+    // packed flags), so 24 group-steps in flight - the 2 x 12 of two groups - hold the kernels at 3 waves per SIMD
+    // (<= 168 VGPRs by the register-file table of the MI355X): 3 x 8 -> 160 VGPRs, 4 x 6 -> 168.  One more step (3 x 9, 4 x 7)
+    // needs 176 / 189 and drops to 2 waves.  Unmeasured: chosen from the register budget alone.
+#ifndef SGM_PF_3G
+#define SGM_PF_3G 8
+#endif
+#ifndef SGM_PF_4G
+#define SGM_PF_4G 6
+#endif
+    // vertical scanlines of volumes of 4 GiB or more: the rebasing variants (FAR = true); horizontal ones span a
+    // row and every shape below 4 GiB keeps the kernels above
+    if (rh != 0 && (size_t)H * W * P.Dp * 4 >= ((size_t)1 << 32)) {
+        const int ng = cdiv(P.Dp, 256);
+        const bool full = D == 256 * ng;
+        if (ng == 1 && full)
+            hipLaunchKernelGGL((sgm_pass_kernel<1, 16, true, 4, true>), grid, block, 0, s, P);
+        else if (ng == 1)
+            hipLaunchKernelGGL((sgm_pass_kernel<1, SGM_PF_PARTIAL, false, 4, true>), grid, block, 0, s, P);
+        else if (ng == 2 && full)
+            hipLaunchKernelGGL((sgm_pass_kernel<2, SGM_PF_2G, true, 4, true>), grid, block, 0, s, P);
+        else if (ng == 2)
+            hipLaunchKernelGGL((sgm_pass_kernel<2, SGM_PF_2G, false, 4, true>), grid, block, 0, s, P);
+        else if (ng == 3 && full)
+            hipLaunchKernelGGL((sgm_pass_kernel<3, SGM_PF_3G, true, 4, true>), grid, block, 0, s, P);
+        else if (ng == 3)
+            hipLaunchKernelGGL((sgm_pass_kernel<3, SGM_PF_3G, false, 4, true>), grid, block, 0, s, P);
+        else if (full)
+            hipLaunchKernelGGL((sgm_pass_kernel<4, SGM_PF_4G, true, 4, true>), grid, block, 0, s, P);
+        else
+            hipLaunchKernelGGL((sgm_pass_kernel<4, SGM_PF_4G, false, 4, true>), grid, block, 0, s, P);
+        return check_launch(who);
+    }
     if (D == 256)
         hipLaunchKernelGGL((sgm_pass_kernel<1, 16, true>), grid, block, 0, s, P);
     else if (D == 192)                                   // three disparities per lane: all 64 lanes, no tail masks
@@ -656,8 +711,16 @@ static int sgm_launch_pass(const char *who, float *const *vol_hwd, const int *si
         hipLaunchKernelGGL((sgm_pass_kernel<1, SGM_PF_PARTIAL, false>), grid, block, 0, s, P);
     else if (D == 512)
         hipLaunchKernelGGL((sgm_pass_kernel<2, SGM_PF_2G, true>), grid, block, 0, s, P);
-    else
+    else if (D < 512)
         hipLaunchKernelGGL((sgm_pass_kernel<2, SGM_PF_2G, false>), grid, block, 0, s, P);
+    else if (D == 768)
+        hipLaunchKernelGGL((sgm_pass_kernel<3, SGM_PF_3G, true>), grid, block, 0, s, P);
+    else if (D < 768)
+        hipLaunchKernelGGL((sgm_pass_kernel<3, SGM_PF_3G, false>), grid, block, 0, s, P);
+    else if (D == 1024)
+        hipLaunchKernelGGL((sgm_pass_kernel<4, SGM_PF_4G, true>), grid, block, 0, s, P);
+    else
+        hipLaunchKernelGGL((sgm_pass_kernel<4, SGM_PF_4G, false>), grid, block, 0, s, P);
     return check_launch(who);
 }
 
@@ -706,10 +769,19 @@ extern "C" int mccnn_sgm_first_pass(const float *image_left, const float *image_
     MCCNN_REQUIRE(H > 0 && W > 1, MCCNN_E_INVALID, "mccnn_sgm_first_pass: bad size");
     MCCNN_REQUIRE(D >= 2 && D <= 256, MCCNN_E_UNSUPPORTED,
                   "mccnn_sgm_first_pass: D=%d outside [2,256]; use mccnn_dhw_to_hwd + mccnn_sgm_pass", D);
-    MCCNN_REQUIRE((size_t)D * H * W * 4 < ((size_t)1 << 32), MCCNN_E_UNSUPPORTED,
-                  "mccnn_sgm_first_pass: volume exceeds the 4 GiB reach of a buffer descriptor");
     MCCNN_REQUIRE(scratch_bytes >= mccnn_sgm_scratch_bytes(H, W, D), MCCNN_E_SCRATCH,
                   "mccnn_sgm_first_pass: scratch %zu < %zu bytes", scratch_bytes, mccnn_sgm_scratch_bytes(H, W, D));
+    if ((size_t)D * H * W * 4 >= ((size_t)1 << 32)) {
+        // the tile gather addresses all D planes from one descriptor: past its 4 GiB reach the layout change and the
+        // pass run apart (same bits: the pass leaves the seed column as the layout change wrote it)
+        for (int j = 0; j < n_jobs; ++j) {
+            MCCNN_REQUIRE(vol_dhw[j] && vol_hwd[j], MCCNN_E_INVALID, "mccnn_sgm_first_pass: null volume");
+            const int rc = mccnn_dhw_to_hwd(vol_dhw[j], vol_hwd[j], D, H, W, stream);
+            if (rc) return rc;
+        }
+        return mccnn_sgm_pass(image_left, image_right, vol_hwd, side, n_jobs, D, H, W, 0, 1, p1, p2, q1, q2, thr, scratch,
+                              scratch_bytes, stream);
+    }
     hipStream_t s = (hipStream_t)stream;
     const int pad = flag_pad(D);
     const int pitch = W + 2 * pad;

@@ -161,6 +161,7 @@ def main(argv=None):
     streams = [torch.cuda.Stream() for _ in range(in_flight)] if in_flight > 1 else [None]
     pending = []          # pairs launched and not yet written: (device map, done event, start time, output paths)
     launched = 0
+    last_shape = None
 
     redo = {"left": 0, "matcher": None}
 
@@ -203,6 +204,12 @@ def main(argv=None):
 
         height, width, ndisp = util.parseCalib(calib_path)
         print("[{}] pair {}: {} | {}  ({}x{}, ndisp {})".format(rank, index, left_path, right_path, width, height, ndisp))
+        # refuses a shape outside what the kernels serve (ValueError naming the limit); each matcher checks its own
+        # workspace against the free device memory before it allocates it
+        footprint = sd.workspace_bytes(height, width, ndisp, matchers[0].pixel_major(), pairs_in_flight=in_flight)
+        if (height, width, ndisp) != last_shape:
+            print("[{}] workspace {:.2f} GB ({} pair(s) in flight)".format(rank, footprint / 1e9, in_flight))
+            last_shape = (height, width, ndisp)
 
         # decode + standardise (match.py:118-125): population std, no /255
         views = []

@@ -815,6 +815,50 @@ DEFAULT_HP = dict(cbca_intensity=0.02, cbca_distance=14, cbca_num_iterations1=2,
                   blur_threshold=2)  # match.py:32-43
 
 
+SGM_MAX_D = 1024               # mccnn_sgm_pass: four 256-disparity groups per lane
+COST_VOLUME_HWD_MAX_D = 1024   # mccnn_cost_volume_hwd (larger D: the plane-major volume + a layout change)
+
+
+def check_envelope(H, W, D):
+    """Raises ValueError for a pair shape the kernels do not serve: 2 <= D <= SGM_MAX_D and D <= W - 2 (the reference's
+    border rule).  Volumes of any size within device memory are served (SGM rebases past 4 GiB)."""
+    H, W, D = int(H), int(W), int(D)
+    if H < 1 or W < 1:
+        raise ValueError("%dx%d: empty image" % (W, H))
+    if D < 2 or D > SGM_MAX_D:
+        raise ValueError("ndisp=%d outside [2, %d]: SGM is built for at most %d disparities" % (D, SGM_MAX_D, SGM_MAX_D))
+    if D > W - 2:
+        raise ValueError("ndisp=%d needs an image at least ndisp + 2 = %d pixels wide, got W=%d" % (D, D + 2, W))
+
+
+def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flight=1):
+    """Device bytes StereoMatcher.workspace(H, W, D) allocates, times `pairs_in_flight` (match.py --pairs_in_flight:
+    one matcher per pair in flight): four volumes of H*W*Dp*4 bytes (Dp = hwd_pitch(D)), the SGM scratch and the flag
+    planes of the four directions, both support planes, the status and map planes, and - on pixel-major volumes with
+    cbca_kernel != "hwd" - the two aggregation program buffers where their programs encode the shape.  Not included:
+    the feature maps (2 x H*W*64*4 bytes while the cost volume is built) and the conv activations."""
+    check_envelope(H, W, D)
+    lib = hip.load()
+    H, W, D = int(H), int(W), int(D)
+    dp = (D + 3) & ~3
+    n = 4 * H * W * dp * 4
+    n += 5 * int(lib.mccnn_sgm_scratch_bytes(H, W, D))
+    n += 2 * int(lib.mccnn_support_bytes(H, W))
+    n += H * W * 4 + 6 * H * W * 4
+    if pixel_major and cbca_kernel != "hwd":
+        n += 2 * int(lib.mccnn_cbca_prog_bytes(D, H, W))
+    return n * max(1, int(pairs_in_flight))
+
+
+def _require_device_memory(nbytes, what):
+    """Raises RuntimeError (before anything is allocated) when `nbytes` exceed the device memory that is free or held
+    idle by the caching allocator."""
+    free, _total = torch.cuda.mem_get_info()
+    avail = free + torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
+    if nbytes > avail:
+        raise RuntimeError("%s needs %.2f GB of device memory, %.2f GB are available" % (what, nbytes / 1e9, avail / 1e9))
+
+
 class StereoMatcher(object):
     """The timed region of match.py:129-179 for one stereo pair, resident on one GPU.
 
@@ -921,6 +965,9 @@ class StereoMatcher(object):
         key = (H, W, D)
         ws = self._ws.get(key)
         if ws is None:
+            need = workspace_bytes(H, W, D, self.pixel_major(), self.cbca_kernel)
+            self._ws, self._graphs = {}, {}          # one shape resident at a time: the previous one goes first
+            _require_device_memory(need, "StereoMatcher: the workspace of a %dx%d pair with ndisp=%d" % (W, H, D))
             dp = hwd_pitch(D)
             n = H * W * dp                        # >= D*H*W: every volume buffer can hold either layout
             dev = self.device
@@ -1043,7 +1090,7 @@ class StereoMatcher(object):
             side_work(0)
 
         # the bit-exact variant writes its cost volume pixel-major right away (nothing converts layouts after that)
-        direct = self.pixel_major() and D <= 512
+        direct = self.pixel_major() and D <= COST_VOLUME_HWD_MAX_D
         timer.start("cost_volume")
         if direct:
             lh, rh = cost_volume_hwd(fl, fr, D, out=(as_hwd(b2), as_hwd(b3)), mode=self.cv_mode)
