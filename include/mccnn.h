@@ -343,9 +343,11 @@ int mccnn_l2norm_chw_to_hwc(const float *chw, const float *bias, float *hwc, int
  * The 64 -> 64 map layers as an implicit GEMM on v_mfma_f32_32x32x16_f16 with every float32 operand carried as two
  * f16 numbers (x * s = hi + lo, 22 significand bits; products hi*hi and hi*lo + lo*hi accumulated in float32 in two
  * accumulator sets that meet once per output): as close to a float64 evaluation as the float32 library convolutions
- * (2.5e-7 .. 3e-7 on the unit feature vectors for both), not bit-identical to them.
+ * (2.5e-7 .. 3.9e-7 on the unit feature vectors, the library 2.7e-7 .. 3.4e-7, up to 1500 x 1000), not bit-identical
+ * to them.
  * saturation_flag (device int, may be NULL): set to 1 when a stored activation exceeds the f16 range of the records
- * (|x| * act_scale > 65504; the value is clamped, the features are then NOT float32-accurate).  The caller zeroes
+ * (|x| * act_scale > 65504; the value is clamped, the features are then NOT float32-accurate).  Only stored pixels
+ * count: what a ragged tile computes beyond the last column or row of the output never sets it.  The caller zeroes
  * it, reads it back after the pair and recomputes with the float32 library path if it is set (match.py does).
  * "Split records": 256 bytes per pixel, [channel group q of 16][hi: 16 x f16 | lo: 16 x f16], pixel-major
  * [N][H][W][256 B]; act_scale (a power of two, e.g. 256) is the factor the stored activations carry (they saturate

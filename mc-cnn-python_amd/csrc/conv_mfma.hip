@@ -389,7 +389,14 @@ __global__ __launch_bounds__(256) void conv3x3_split_kernel(const char *__restri
             // the row passes through the wave's scratch EPX pixels at a time (all 32, or two halves of 16 where two
             // workgroups share a CU's LDS): the lanes owning those pixels write, the wave reads whole records back
             const int row = ty0 + wave * NBW + nb;
-            const int so = ((n * Ho + row) * Wo + tx0) * REC;            // wave-uniform
+            // wave-uniform.  The rows >= Ho of a ragged last tile store nothing (their voffset is out of range), but
+            // their offset is still formed: taken from the last real row it stays below N Ho Wo REC, where
+            // (n Ho + row) Wo REC may pass 2^31 for sizes the launcher accepts (its guard bounds the INPUT records)
+            const int so = ((n * Ho + min(row, Ho - 1)) * Wo + tx0) * REC;
+            // only a pixel that is stored may raise the saturation flag: the lanes of columns >= Wo and rows >= Ho
+            // convolve records that wrapped in from the next row or the next view
+            const bool stored = row < Ho && tx0 + px < Wo;
+            bool over = false;
 #pragma unroll
             for (int hf = 0; hf < 32 / EPX; ++hf) {
                 __builtin_amdgcn_wave_barrier();
@@ -410,7 +417,7 @@ __global__ __launch_bounds__(256) void conv3x3_split_kernel(const char *__restri
                                                          bias[ch + q] * act_scale);
                                     // above the records' range, or a NaN of either sign (a negative value is not: the
                                     // ReLU makes it 0) - the same test as conv1_split's
-                                    sat |= !(t <= 65504.f);
+                                    over |= !(t <= 65504.f);
                                     y4[q] = __builtin_amdgcn_fmed3f(t, 0.f, 65504.f);
                                 }
                                 split4_scaled(y4, hi, lo);
@@ -440,6 +447,7 @@ __global__ __launch_bounds__(256) void conv3x3_split_kernel(const char *__restri
                 }
             }
             __builtin_amdgcn_wave_barrier();
+            sat |= over && stored;
         }
         // a stored activation left the f16 range of the records (|x| * act_scale > 65504): the clamp keeps the data
         // finite, the flag tells the host that this pair's features are not float32-accurate (mccnn.h)
@@ -492,6 +500,9 @@ extern "C" int mccnn_conv3x3_split(const void *in, const void *packed_weights, c
     MCCNN_REQUIRE(in && packed_weights && bias && out, MCCNN_E_INVALID, "mccnn_conv3x3_split: null pointer");
     MCCNN_REQUIRE(N > 0 && Hi > 2 && Wi > 2, MCCNN_E_INVALID, "mccnn_conv3x3_split: input %dx%d too small", Wi, Hi);
     MCCNN_REQUIRE(weight_scale > 0.f && act_scale > 0.f, MCCNN_E_INVALID, "mccnn_conv3x3_split: scales must be positive");
+    // every byte offset of the kernel is a 32-bit int: the loads stay below the input's N Hi Wi REC, and the stores'
+    // wave-uniform offset below N Ho Wo REC < N Hi Wi REC for every row of every tile, the masked rows of a ragged
+    // last tile included (it is formed from min(row, Ho - 1))
     MCCNN_REQUIRE((size_t)N * Hi * Wi * REC <= 0x7ffffff0u, MCCNN_E_UNSUPPORTED,
                   "mccnn_conv3x3_split: %d x %dx%d records exceed 32-bit buffer offsets", N, Wi, Hi);
     const int Ho = Hi - 2, Wo = Wi - 2;

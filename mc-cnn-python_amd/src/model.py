@@ -28,6 +28,20 @@ import torch.nn.functional as F
 import tf_checkpoint
 
 
+# the split-operand kernels address their records with 32-bit byte offsets: 256 B per pixel of the padded first layer
+SPLIT_RECORD_LIMIT = 0x7ffffff0 // 256
+
+
+def split_feature_route(H, W, pad):
+    """How NET.features_pair_hwc_split evaluates an H x W pair: ("pair", None) - both views as one batch of two;
+    ("views", None) - too many records for one batch, view by view; ("library", rows) - one view alone exceeds the
+    offsets: the float32 library convolutions in bands of `rows` output rows."""
+    padded = (H + 2 * pad - 2) * (W + 2 * pad - 2)
+    if padded > SPLIT_RECORD_LIMIT:
+        return "library", max(64, (SPLIT_RECORD_LIMIT // (W + 2 * pad)) // 2)
+    return ("pair" if 2 * padded <= SPLIT_RECORD_LIMIT else "views"), None
+
+
 class NET(object):
 
     def __init__(self, x=None, weights_path='DEFAULT',
@@ -214,15 +228,12 @@ class NET(object):
         packed = self._split_weights()
         flag = self._split_flag()
         H, W = left_hw.shape
-        # the kernels address their records with 32-bit byte offsets: 256 B per padded pixel, both views in one batch
-        limit = 0x7ffffff0 // 256
-        padded = (H + 2 * pad - 2) * (W + 2 * pad - 2)
-        if padded > limit:
-            rows = max(64, (limit // (W + 2 * pad)) // 2)
+        route, rows = split_feature_route(H, W, pad)
+        if route == "library":
             warnings.warn("split-operand features: a %dx%d view exceeds the kernels' 32-bit record offsets; using the "
                           "float32 library convolutions in bands of %d rows instead" % (W, H, rows))
             return self.features_pair_hwc(left_hw, right_hw, tile_rows=rows)
-        batches = [torch.stack((left_hw, right_hw)).contiguous()] if 2 * padded <= limit else \
+        batches = [torch.stack((left_hw, right_hw)).contiguous()] if route == "pair" else \
             [left_hw[None].contiguous(), right_hw[None].contiguous()]          # too big as a pair: view by view
         outs = []
         nl = self.num_conv_layers

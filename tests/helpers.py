@@ -141,3 +141,66 @@ def stagewise(keep, L, R, D, o, hp=None, features=None):
 def first_differing_stage(d):
     """The first stage of a stagewise() record whose output differs from the CPU checker's, or None."""
     return next((k for k, v in d.items() if v != 0 and not k.endswith("_spacings_of_max_input")), None)
+
+
+def features_float64(net, img, window=None):
+    """[H,W] float32 image -> [H,W,64] float64 unit features by torch on the CPU: conv2d VALID on the once-padded image,
+    ReLU, tf.nn.l2_normalize (model.py:51-64 of the reference as model.NET restates it).  window=(y0, y1, x0, x1):
+    only the output pixels [y0:y1, x0:x1] - the padded image is cropped to the window's receptive field, so every
+    pixel sees what it sees in the whole evaluation (it differs from it by at most 1.1e-16)."""
+    import torch
+    import torch.nn.functional as F
+    pad = (net.input_patch_size - 1) // 2
+    x = F.pad(img.double().cpu()[None, None], (pad, pad, pad, pad))
+    if window is not None:
+        y0, y1, x0, x1 = window
+        x = x[:, :, y0:y1 + 2 * pad, x0:x1 + 2 * pad]
+    nl = net.num_conv_layers
+    for k in range(nl):
+        x = F.conv2d(x, net.weights[k].detach().double().cpu(), net.biases[k].detach().double().cpu())
+        if k < nl - 1:
+            x = F.relu(x)
+    x = x[0].permute(1, 2, 0)
+    return x / torch.sqrt(torch.clamp((x * x).sum(-1, keepdim=True), min=1e-12))
+
+
+def smooth_pair(H, W, seed):
+    """Two standardised float32 [H,W] views: low-pass noise and its shifted, noisier copy."""
+    import torch
+    import torch.nn.functional as F
+    g = torch.Generator().manual_seed(seed)
+    a = F.avg_pool2d(torch.randn((1, 1, H + 8, W + 8), generator=g), 5, 1, 2)[0, 0, 4:-4, 4:-4]
+    b = torch.roll(a, 3, 1) + 0.05 * torch.randn((H, W), generator=g)
+    out = []
+    for t in (a, b):
+        out.append(((t - t.mean()) / t.std()).float().contiguous())
+    return out
+
+
+def split_f16(v):
+    """Already scaled float32 values inside the f16 range -> (hi, lo) float16 with hi = f16(v), lo = f16(v - hi)."""
+    v = np.asarray(v, np.float32)
+    hi = v.astype(np.float16)
+    return hi, (v - hi.astype(np.float32)).astype(np.float16)
+
+
+def records_encode(x, act_scale):
+    """float32 [..., 64] -> the 256-byte split records of include/mccnn.h, uint8 [..., 256]:
+    [q = channel / 16][hi 16 x f16 | lo 16 x f16] of x * act_scale."""
+    x = np.asarray(x, np.float32)
+    assert x.shape[-1] == 64
+    hi, lo = split_f16(x * np.float32(act_scale))
+    rec = np.empty(x.shape[:-1] + (4, 2, 16), np.float16)
+    rec[..., 0, :] = hi.reshape(x.shape[:-1] + (4, 16))
+    rec[..., 1, :] = lo.reshape(x.shape[:-1] + (4, 16))
+    return rec.reshape(x.shape[:-1] + (128,)).view(np.uint8)
+
+
+def records_decode(rec, act_scale):
+    """Split records uint8 [..., 256] -> float32 [..., 64]: (hi + lo) / act_scale.  The sum is exact in float32 for
+    records made from float32 values, and act_scale is a power of two."""
+    rec = np.ascontiguousarray(rec)
+    assert rec.dtype == np.uint8 and rec.shape[-1] == 256
+    h = rec.view(np.float16).reshape(rec.shape[:-1] + (4, 2, 16))
+    v = h[..., 0, :].astype(np.float32) + h[..., 1, :].astype(np.float32)
+    return (v / np.float32(act_scale)).reshape(rec.shape[:-1] + (64,))

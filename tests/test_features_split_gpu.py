@@ -13,7 +13,7 @@ import pytest
 import torch
 
 import tolerances as tol
-import torch.nn.functional as F
+from helpers import features_float64, smooth_pair
 
 pytestmark = pytest.mark.gpu
 
@@ -22,29 +22,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def features_float64(net, img):
-    """[H,W] float32 image -> [H,W,64] float64 unit features on the CPU."""
-    pad = (net.input_patch_size - 1) // 2
-    x = F.pad(img.double().cpu()[None, None], (pad, pad, pad, pad))
-    nl = net.num_conv_layers
-    for k in range(nl):
-        x = F.conv2d(x, net.weights[k].detach().double().cpu(), net.biases[k].detach().double().cpu())
-        if k < nl - 1:
-            x = F.relu(x)
-    x = x[0].permute(1, 2, 0)
-    return x / torch.sqrt(torch.clamp((x * x).sum(-1, keepdim=True), min=1e-12))
-
-
-def smooth_pair(H, W, seed):
-    g = torch.Generator().manual_seed(seed)
-    a = F.avg_pool2d(torch.randn((1, 1, H + 8, W + 8), generator=g), 5, 1, 2)[0, 0, 4:-4, 4:-4]
-    b = torch.roll(a, 3, 1) + 0.05 * torch.randn((H, W), generator=g)
-    out = []
-    for t in (a, b):
-        out.append(((t - t.mean()) / t.std()).float().contiguous())
-    return out
 
 
 @pytest.fixture(scope="module")
@@ -87,6 +64,11 @@ def test_split_features_as_close_to_float64_as_the_library_path(nets, H, W):
         assert e_spl <= tol.FEATURES_F32_CLASS_ABS, "%s: split path %g from float64" % (name, e_spl)
         assert e_lib <= tol.FEATURES_F32_CLASS_ABS, "%s: library path %g from float64" % (name, e_lib)
         assert e_spl <= 1.5 * e_lib + 5e-8, "%s: split %g vs library %g" % (name, e_spl, e_lib)
+    record_measured(record)
+
+
+def record_measured(record):
+    """Merges {key: figures} into the feature tests' file of measured numbers (test_features_shapes_gpu.py too)."""
     out = os.path.join(ROOT, "gpurun_out")
     os.makedirs(out, exist_ok=True)
     path = os.path.join(out, "parity_features_split.json")

@@ -337,3 +337,46 @@ def test_oracle_match_defaults_are_the_matchers():
     assert o.MATCH_DEFAULTS == sd.DEFAULT_HP
     with pytest.raises(ValueError):
         o.match_from_features(None, None, None, None, 4, args=dict(cbca_iterations=3))
+
+
+def test_split_feature_route_boundaries():
+    """NET.features_pair_hwc_split's choice between one batch of two, view by view and the banded library convolutions,
+    at the record counts where it changes: (H + 8)(W + 8) = limit // 2, limit // 2 + 1, limit, limit + 1."""
+    from model import SPLIT_RECORD_LIMIT, split_feature_route
+    limit = 0x7ffffff0 // 256
+    assert SPLIT_RECORD_LIMIT == limit == 2 ** 23 - 1
+    for (h8, w8), want in (((2047, 2049), ("pair", None)),            # 2^22 - 1 = limit // 2
+                           ((2048, 2048), ("views", None)),           # limit // 2 + 1
+                           ((47, 178481), ("views", None)),           # 2^23 - 1 = limit
+                           ((2048, 4096), ("library", max(64, (limit // 4098) // 2)))):   # limit + 1
+        assert split_feature_route(h8 - 8, w8 - 8, 5) == want, (h8, w8)
+    assert 2047 * 2049 == limit // 2 and 47 * 178481 == limit and 2048 * 4096 == limit + 1
+    assert split_feature_route(2040, 4088, 5)[1] == 1023
+    assert split_feature_route(500, 750, 5) == ("pair", None)
+    assert split_feature_route(8, 10 ** 6, 5) == ("library", 64)      # never fewer than 64 rows per band
+
+
+def test_split_record_codec_round_trip():
+    """helpers.records_encode / records_decode (the 256-byte split records of include/mccnn.h): layout, 22 significand
+    bits for values whose parts are normal f16 numbers, and hi + lo exactly representable in float32."""
+    import helpers
+    rng = np.random.default_rng(0)
+    x = (rng.uniform(1, 2, (3, 5, 7, 64)) * 2.0 ** rng.integers(-11, 7, (3, 5, 7, 64))
+         * rng.choice([-1.0, 1.0], (3, 5, 7, 64))).astype(np.float32)
+    x[0, 0, 0, :4] = (0.0, 255.0, -255.0, 2.0 ** -11)
+    rec = helpers.records_encode(x, 256.0)
+    assert rec.shape == (3, 5, 7, 256) and rec.dtype == np.uint8
+    back = helpers.records_decode(rec, 256.0)
+    assert back.shape == x.shape and back.dtype == np.float32
+    assert (np.abs(back.astype(np.float64) - x) <= 2.0 ** -22 * np.abs(x)).all()
+    h = rec.view(np.float16).reshape(3, 5, 7, 4, 2, 16)
+    hi, lo = h[..., 0, :], h[..., 1, :]
+    assert np.array_equal(hi.reshape(x.shape), (x * np.float32(256)).astype(np.float16))      # channel c at [c / 16][c % 16]
+    assert (lo != 0).mean() > 0.9
+    tiny = (rng.uniform(0, 1, (2, 3, 4, 64)) * 2.0 ** rng.integers(-30, -8, (2, 3, 4, 64))).astype(np.float32)
+    for r in (rec, helpers.records_encode(tiny, 256.0)):                # subnormal and zero parts included
+        h = r.view(np.float16).reshape(r.shape[:-1] + (4, 2, 16))
+        s64 = h[..., 0, :].astype(np.float64) + h[..., 1, :].astype(np.float64)
+        s32 = h[..., 0, :].astype(np.float32) + h[..., 1, :].astype(np.float32)
+        assert np.array_equal(s32.astype(np.float64), s64)
+    assert np.array_equal(helpers.records_decode(helpers.records_encode(back, 256.0), 256.0), back)   # a fixed point
