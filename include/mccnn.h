@@ -45,7 +45,7 @@ extern "C" {
 
 typedef void *mccnn_stream_t; /* hipStream_t */
 
-#define MCCNN_ABI_VERSION 7 /* 2: window-mask plane, *_hwd entry points; 3: saturation flags; 4: program-driven CBCA; 5: skip programs; 6: one-volume launches; 7: refresh launches, SGM flag planes as a call of their own */
+#define MCCNN_ABI_VERSION 7 /* 2: window-mask plane, *_hwd entry points; 3: saturation flags; 4: program-driven CBCA; 5: skip programs; 6: one-volume launches; 7: refresh launches, SGM flag planes as a call of their own; still 7 with the mccnn_ingest_* entry points: purely additive, nothing that existed changed */
 
 #define MCCNN_E_INVALID (-1)     /* bad argument (null pointer, non-positive size, unsupported shape) */
 #define MCCNN_E_UNSUPPORTED (-2) /* shape outside what the kernels were built for (e.g. D > 1024 for SGM) */
@@ -324,6 +324,22 @@ int mccnn_median(const float *disp, int H, int W, int fh, int fw, float *out, mc
  * |I(q)-I(p)| < thr.  Sums follow NumPy's pairwise order over the clipped window (pf:463,466): bit-exact. */
 int mccnn_bilateral(const float *image, const float *disp, int H, int W, int fh, int fw, const float *table,
                     float thr, float *out, mccnn_stream_t stream);
+
+/* ---- a0  decode + standardise on the device (match.py:118-125) ---------------------------------------------------
+ * From the decoded bytes of a PNG to the standardised float32 image the conv stack reads, bit-identical to
+ *     g = util.read_gray(p).astype(np.float32);  (g - np.mean(g, axis=(0,1))) / np.std(g, axis=(0,1))
+ * as NumPy 2 evaluates it on the host (reduction buffer of 8192 elements; csrc/ingest.hip states the summation order).
+ * image_u8: [H][W][C] uint8, C = 1 (grey), 3 (RGB) or 4 (RGBA, the alpha byte ignored).  Grey of a colour pixel:
+ * (r*9797 + g*19234 + b*3737) >> 15, libpng's rgb_to_gray as OpenCV sets it up.  out: [H][W] float32.  float32
+ * throughout, un-fused, correctly rounded division and square root; a constant image gives NumPy's 0/0 (NaN).
+ * scratch: mccnn_ingest_scratch_bytes(H, W) bytes (chunk sums of BOTH views of a pair: the same size serves the
+ * one-image call), 4-byte aligned, private to one call in flight.  Three launches per call, no synchronisation.
+ * The _pair form takes both views of a stereo pair (same H, W, C) in the same three launches. */
+size_t mccnn_ingest_scratch_bytes(int H, int W); /* 0 for non-positive sizes */
+int mccnn_ingest_u8(const uint8_t *image_u8, int H, int W, int C, float *out, void *scratch, size_t scratch_bytes,
+                    mccnn_stream_t stream);
+int mccnn_ingest_u8_pair(const uint8_t *left_u8, const uint8_t *right_u8, int H, int W, int C, float *out_left,
+                         float *out_right, void *scratch, size_t scratch_bytes, mccnn_stream_t stream);
 
 /* ---- a1 epilogues of the conv stack (model.py:51-64, 111-125) ------------------------------------------------
  * mccnn_bias_act: x[n][c][i] = act(x[n][c][i] + bias[c]) in place on an NCHW tensor (plane = H*W elements) -

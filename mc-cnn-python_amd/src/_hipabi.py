@@ -83,6 +83,9 @@ SIGNATURES = {
     "mccnn_conv1_split": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
     "mccnn_conv3x3_split": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _vp]),
     "mccnn_l2norm_chw_to_hwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "mccnn_ingest_scratch_bytes": (_sz, [_i, _i]),
+    "mccnn_ingest_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "mccnn_ingest_u8_pair": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,304 @@
+"""match.py --pipeline: a list of pairs streamed through the matcher instead of handled one at a time on one thread.
+
+    readers (N threads)         main thread, per slot              writer (1 thread)
+    calib.txt, envelope check,  H2D of the bytes (non-blocking),   waits for the pair's event,
+    PNG -> raw uint8 in pinned  ingest + match: eager, or one      PFM / PGM / time files
+    host memory, list order     hipGraph replay; map -> pinned
+                                host buffer + event
+
+ListPipeline is the decode / submit / collect core: ordering, back-pressure, the capture policy and error handling.  It
+knows nothing of the GPU - it is handed `read` (entry -> job, run on the reader threads), a match `backend` and `write`
+(run on the writer thread), so all of that is tested on the CPU with a fake backend.  MatcherBackend is the real one.
+
+Capture policy.  A graph costs two warm-up pairs plus a capture, and a matcher keeps one shape resident, so a slot
+captures a (H, W, ndisp, C) only when it sees it for the second time in a row; first sight and alternating shapes run
+eagerly (match_u8).  Once captured, a key is replayed for as long as the slot's shape (H, W, ndisp) stays.
+
+The backend's interface:
+    thread_init()                     called once on every reader / writer thread
+    submit(slot, job, mode) -> ticket mode in ("eager", "capture", "replay"); enqueues, never blocks on the GPU
+    wait(ticket) -> result            blocks until the pair's map is on the host (writer thread, and main on slot reuse)
+    retire(slot, job, ticket)         the slot is about to be reused; returns None, or the ticket of a repeated pair
+                                      (the saturation redo of match.py) whose result replaces the first one's files
+"""
+import os
+import queue
+import threading
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+import util
+
+DEFAULT_READERS = 4          # the GPU hosts allow a process 16 CPUs; never sized by os.cpu_count()
+
+
+class Job(object):
+    """One decoded pair: what a reader hands to the main thread."""
+
+    def __init__(self, index, name, key, **fields):
+        self.index = index           # position in the list file
+        self.name = name             # for the log
+        self.key = key               # (H, W, ndisp, C): what a captured graph is good for
+        self.__dict__.update(fields)
+
+
+class ListPipeline(object):
+    def __init__(self, read, backend, write, slots=1, readers=DEFAULT_READERS, depth=None, writer_depth=8):
+        self.read, self.backend, self.write = read, backend, write
+        self.slots = max(1, int(slots))
+        self.readers = max(1, int(readers))
+        # jobs handed to the readers and not yet taken by the main thread (being decoded or waiting, decoded): the bound
+        # of the reader queue - pinned host memory in use is at most this many pairs + the pairs in flight
+        self.depth = max(1, int(depth if depth is not None else 2 * self.readers))
+        self.writer_depth = max(1, int(writer_depth))
+        self.counters = dict(pairs=0, captures=0, replays=0, eager=0, redone=0)
+        # where the wall time went: the main thread waiting for a decoded pair / for a slot's previous pair / enqueuing,
+        # and the writer thread waiting for maps / writing files (which stage bounds the run: tools/bench_list.py)
+        self.seconds = dict(main_wait_readers=0.0, main_wait_slot=0.0, main_submit=0.0, writer_wait_gpu=0.0,
+                            writer_files=0.0)
+        self.submitted_at = []       # host clock at every submit: the steady rate behind the first pairs' capture
+        self.max_read_ahead = 0      # the largest number of outstanding reader jobs seen (tests: <= depth)
+        self._last_key = [None] * self.slots
+        self._captured = [set() for _ in range(self.slots)]
+
+    # ---- capture policy -------------------------------------------------------------------------------------------
+    def mode_for(self, slot, key):
+        """'replay' for a key this slot has captured, 'capture' when the slot sees the key for the second time in a row,
+        'eager' otherwise.  A change of shape (everything but the channel count) drops the slot's captured keys: the
+        matcher keeps one shape resident."""
+        last = self._last_key[slot]
+        if last is not None and tuple(last[:3]) != tuple(key[:3]):
+            self._captured[slot].clear()
+        self._last_key[slot] = key
+        if key in self._captured[slot]:
+            return "replay"
+        if key == last:
+            self._captured[slot].add(key)
+            return "capture"
+        return "eager"
+
+    # ---- writer thread --------------------------------------------------------------------------------------------
+    def _writer_loop(self):
+        failed = False
+        try:
+            self.backend.thread_init()
+        except BaseException as e:       # noqa: B902 - handed to the main thread
+            self._writer_error, failed = e, True
+        while True:
+            item = self._writer_q.get()
+            if item is None:
+                return
+            if failed:
+                continue                 # keep draining: the main thread must never block on a full queue
+            job, ticket, t0 = item
+            try:
+                t1 = time.time()
+                result = self.backend.wait(ticket)
+                t2 = time.time()
+                self.write(job, result, t2 - t0)
+                self.seconds["writer_wait_gpu"] += t2 - t1
+                self.seconds["writer_files"] += time.time() - t2
+            except BaseException as e:   # noqa: B902
+                self._writer_error, failed = e, True
+
+    def _check_writer(self):
+        if self._writer_error is not None:
+            raise self._writer_error
+
+    # ---- main thread ----------------------------------------------------------------------------------------------
+    def _retire(self, slot, inflight):
+        if inflight[slot] is None:
+            return
+        job, ticket, t0 = inflight[slot]
+        inflight[slot] = None
+        again = self.backend.retire(slot, job, ticket)
+        if again is not None:            # repeated pair: written after (and over) the first result, same writer
+            self.counters["redone"] += 1
+            self._writer_q.put((job, again, t0))
+
+    def run(self, entries):
+        """Matches `entries` in order; returns the counters.  An exception of a reader, of the backend or of the writer
+        ends the run: the pairs already submitted are still written (unless the writer is what failed), every thread
+        is joined, and the exception is raised."""
+        entries = list(entries)
+        self._writer_error = None
+        self._writer_q = queue.Queue(maxsize=self.writer_depth)
+        writer = threading.Thread(target=self._writer_loop, name="list-writer", daemon=True)
+        pool = ThreadPoolExecutor(max_workers=self.readers, thread_name_prefix="list-reader",
+                                  initializer=self.backend.thread_init)
+        inflight = [None] * self.slots
+        futures = []
+        fed = 0
+        writer.start()
+        try:
+            for n in range(len(entries)):
+                while fed < len(entries) and fed - n < self.depth:
+                    futures.append(pool.submit(self.read, entries[fed]))
+                    fed += 1
+                self.max_read_ahead = max(self.max_read_ahead, fed - n)
+                ta = time.time()
+                job = futures[n].result()            # list order; a reader's exception surfaces here
+                futures[n] = None
+                self._check_writer()
+                slot = n % self.slots
+                tb = time.time()
+                self._retire(slot, inflight)         # the oldest pair is the one that used this slot
+                mode = self.mode_for(slot, job.key)
+                t0 = time.time()
+                self.submitted_at.append(t0)
+                ticket = self.backend.submit(slot, job, mode)
+                self.seconds["main_wait_readers"] += tb - ta
+                self.seconds["main_wait_slot"] += t0 - tb
+                self.seconds["main_submit"] += time.time() - t0
+                self.counters["pairs"] += 1
+                self.counters[{"eager": "eager", "capture": "captures", "replay": "replays"}[mode]] += 1
+                inflight[slot] = (job, ticket, t0)
+                self._writer_q.put((job, ticket, t0))
+            for k in range(self.slots):              # oldest first
+                self._retire((len(entries) + k) % self.slots, inflight)
+        finally:
+            for f in futures:
+                if f is not None:
+                    f.cancel()
+            pool.shutdown(wait=True)
+            self._writer_q.put(None)
+            writer.join()
+        self._check_writer()
+        return dict(self.counters)
+
+    def summary(self):
+        c = self.counters
+        return "pipeline: pairs=%d captures=%d replays=%d eager=%d" % (c["pairs"], c["captures"], c["replays"], c["eager"])
+
+
+# ---- the readers' side of match.py ------------------------------------------------------------------------------------
+def decode_u8(path):
+    """A PNG as raw bytes: uint8 [H,W] ('L'), [H,W,3] ('RGB') or [H,W,4] ('RGBA') as stored - no grey conversion, no
+    float.  Any other PIL mode goes through the same convert() calls as util.read_gray up to its uint8 array."""
+    from PIL import Image
+    im = Image.open(path)
+    if im.mode in ("L", "P", "1", "I;16", "I"):
+        if im.mode != "L":
+            im = im.convert("L")
+    elif im.mode not in ("RGB", "RGBA"):
+        im = im.convert("RGB")
+    return np.asarray(im, dtype=np.uint8)
+
+
+def _three_channels(a):
+    """[H,W] or [H,W,4] -> [H,W,3] with the same grey value: (v, v, v) maps to v, alpha is ignored anyway."""
+    return np.repeat(a[:, :, None], 3, axis=2) if a.ndim == 2 else a[:, :, :3]
+
+
+def pinned_u8(a):
+    import torch
+    t = torch.empty(a.shape, dtype=torch.uint8, pin_memory=True)
+    np.copyto(t.numpy(), a)
+    return t
+
+
+def make_reader(paths, check_shape, to_host_buffer=pinned_u8):
+    """read(index) for ListPipeline on top of match.py's file layout.  `paths(index)` -> dict(left, right, calib, out,
+    out_time, out_img, res_dir, img_dir); `check_shape(H, W, ndisp)` raises for a pair outside the envelope - before
+    anything of that pair is decoded, let alone reaches the GPU."""
+    def read(index):
+        p = paths(index)
+        height, width, ndisp = util.parseCalib(p["calib"])
+        check_shape(height, width, ndisp)
+        util.recurMk(os.path.abspath(p["res_dir"]))
+        util.recurMk(os.path.abspath(p["img_dir"]))
+        left, right = decode_u8(p["left"]), decode_u8(p["right"])
+        if left.shape[2:] != right.shape[2:]:
+            left, right = _three_channels(left), _three_channels(right)
+        for a, which in ((left, p["left"]), (right, p["right"])):
+            if a.shape[:2] != (height, width):
+                raise ValueError("%s is %dx%d, its calib.txt says %dx%d" % (which, a.shape[1], a.shape[0], width, height))
+        channels = 1 if left.ndim == 2 else left.shape[2]
+        return Job(index, p["left"], (height, width, ndisp, channels), height=height, width=width, ndisp=ndisp,
+                   left=to_host_buffer(left), right=to_host_buffer(right), paths=p)
+    return read
+
+
+def make_writer(rank=0, log=print):
+    """write(job, map, seconds) for ListPipeline: the three files of match.py, with the existing util functions."""
+    from datetime import datetime
+
+    def write(job, disparity, seconds):
+        p = job.paths
+        util.saveDisparity(disparity, p["out_img"])
+        util.writePfm(disparity, p["out"])
+        util.saveTimeFile(seconds, p["out_time"])
+        log("[{}] {}: {:.3f} s -> {}".format(rank, datetime.now(), seconds, p["out"]))
+    return write
+
+
+class Ticket(object):
+    def __init__(self, host, done):
+        self.host, self.done = host, done
+
+
+class MatcherBackend(object):
+    """ListPipeline's backend on StereoMatchers: one matcher and one stream per slot, as match.py --pairs_in_flight."""
+
+    def __init__(self, matchers, streams, make_library_matcher, rank=0, log=print):
+        import torch
+        self.torch = torch
+        self.matchers, self.streams = matchers, streams
+        self.make_library_matcher = make_library_matcher
+        self.device = torch.cuda.current_device()
+        self.rank, self.log = rank, log
+        self._redo_left = 0
+        self._redo_matcher = None
+
+    def thread_init(self):
+        self.torch.cuda.set_device(self.device)      # the current device is a per-thread setting
+
+    def _stream(self, slot):
+        import contextlib
+        s = self.streams[slot]
+        return self.torch.cuda.stream(s) if s is not None else contextlib.nullcontext()
+
+    def _to_host(self, disparity):
+        torch = self.torch
+        host = torch.empty(tuple(disparity.shape), dtype=torch.float32, pin_memory=True)
+        host.copy_(disparity, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        return Ticket(host, done)
+
+    def submit(self, slot, job, mode):
+        self.log("[{}] pair {}: {}  ({}x{}, ndisp {}, {} byte(s) per pixel, {})".format(
+            self.rank, job.index, job.name, job.width, job.height, job.ndisp, job.key[3], mode))
+        m = self.matchers[slot]
+        with self._stream(slot):
+            if mode == "eager":
+                disparity = m.match_u8(job.left, job.right, job.ndisp)
+            else:
+                disparity = m.match_graph_u8(job.left, job.right, job.ndisp)
+            return self._to_host(disparity)
+
+    def wait(self, ticket):
+        ticket.done.synchronize()
+        return ticket.host.numpy()
+
+    def retire(self, slot, job, ticket):
+        ticket.done.synchronize()
+        # match.py's saturation redo: the hand-written feature kernels report an activation beyond the range of their
+        # records; that pair - and, with several in flight, the ones that shared the flag with it - is matched again
+        # with the float32 library convolutions before its slot is reused
+        m0 = self.matchers[0]
+        if m0.features == "split_f16" and m0.features_saturated():
+            self._redo_left = len(self.matchers)
+        if self._redo_left <= 0:
+            return None
+        self._redo_left -= 1
+        if self._redo_matcher is None:
+            self._redo_matcher = self.make_library_matcher()
+        self.log("[{}] activations left the matrix-core feature kernels' range: {} repeated with the float32 library "
+                 "convolutions".format(self.rank, job.paths["out"]))
+        disparity = self._redo_matcher.match_u8(job.left, job.right, job.ndisp)
+        again = self._to_host(disparity)
+        self.torch.cuda.synchronize()
+        return again

@@ -13,6 +13,8 @@ Addition: --fast computes the cost volume on the matrix cores instead of in NumP
 near-ties in the WTA can then resolve differently) and leaves every other stage as it is - a few per cent faster;
 --fast --separable_cbca adds the aggregation through float64 prefix sums on plane-major volumes (<= 1e-6 per
 iteration), the fast variant of rounds 2-3, which the bit-exact aggregation has overtaken since.
+--pipeline streams the list (list_matcher.py): decoder threads, grey conversion + standardisation on the device, one
+hipGraph replay per pair where a shape repeats, a writer thread - the same files, byte for byte.
 Multi-GPU: launch one process per GPU with different -g / -s / -e, as the reference intends (match.py:17, 26-28),
 or use `torchrun --nproc-per-node N match.py ...`: rank r then takes the pairs i = r (mod N) of the window.
 """
@@ -81,6 +83,15 @@ parser.add_argument("--pairs_in_flight", type=int, default=1,
                          "pair reaches a third of the throughput of a 750x500x256 one); 2 overlaps the launch ramps of "
                          "one pair with the other.  Results are identical; timeMCCNN.txt then holds each pair's own "
                          "wall time, overlap included")
+parser.add_argument("--pipeline", action="store_true",
+                    help="stream the list (src/list_matcher.py): reader threads decode the PNGs to raw bytes in pinned "
+                         "host memory ahead of the GPU, grey conversion and standardisation run on the device "
+                         "(bit-identical to the host's), a shape that repeats is replayed as one hipGraph per pair, and a "
+                         "writer thread writes the files.  Same files as without the flag, byte for byte; every other "
+                         "flag keeps its meaning.  timeMCCNN.txt then holds, as with --pairs_in_flight, the pair's own "
+                         "wall time from the enqueue of its host-to-device copy to its map being on the host, overlap "
+                         "with other pairs (and a graph capture, where the pair paid one) included")
+parser.add_argument("--readers", type=int, default=4, help="with --pipeline: decoder threads")
 # opt-in departures from the reference's results: what the MC-CNN paper does and the reference names but leaves out
 parser.add_argument("--paper_support_regions", action="store_true",
                     help="CBCA support regions intersected with the other view's at every disparity (paper sec. 4.1; "
@@ -159,6 +170,31 @@ def main(argv=None):
 
     matchers = [make_matcher("miopen" if args.features == "library" else "auto") for _ in range(in_flight)]
     streams = [torch.cuda.Stream() for _ in range(in_flight)] if in_flight > 1 else [None]
+    if args.pipeline:
+        import list_matcher as lm
+
+        def paths(index):
+            left_path = left_paths[index]
+            pair_dir = os.path.dirname(left_path)
+            res_dir = pair_dir.replace(args.data_dir, result_root)
+            img_dir = pair_dir.replace(args.data_dir, image_root)
+            return dict(left=left_path, right=left_path.replace(left_image_suffix, right_image_suffix),
+                        calib=left_path.replace(left_image_suffix, calib_suffix), res_dir=res_dir, img_dir=img_dir,
+                        out=os.path.join(res_dir, out_file), out_time=os.path.join(res_dir, out_time_file),
+                        out_img=os.path.join(img_dir, out_img_file))
+
+        def check_shape(height, width, ndisp):      # the flagless loop's refusal, with its message
+            sd.workspace_bytes(height, width, ndisp, matchers[0].pixel_major(), pairs_in_flight=in_flight)
+
+        backend = lm.MatcherBackend(matchers, streams, lambda: make_matcher("miopen"), rank=rank)
+        pipeline = lm.ListPipeline(lm.make_reader(paths, check_shape), backend, lm.make_writer(rank), slots=in_flight,
+                                   readers=args.readers)
+        try:
+            pipeline.run(shard_indices(args.start, args.end, len(left_paths), rank, world))
+        finally:
+            print("[{}] {}".format(rank, pipeline.summary()))
+        return pipeline
+
     pending = []          # pairs launched and not yet written: (device map, done event, start time, output paths)
     launched = 0
     last_shape = None

@@ -181,6 +181,45 @@ def cost_volume_hwd(fl, fr, ndisp, out=None, mode=hip.MCCNN_CV_EXACT):
     return lcv, rcv
 
 
+# ---- a0 ----------------------------------------------------------------------------------------------------------
+def ingest_scratch(H, W, device):
+    """Scratch of one ingest call in flight (the chunk sums of both views): mccnn_ingest_scratch_bytes(H, W) bytes."""
+    nbytes = int(hip.load().mccnn_ingest_scratch_bytes(H, W))
+    return torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=device)
+
+
+def _u8_image(image_u8):
+    if image_u8.dtype != torch.uint8 or image_u8.dim() not in (2, 3):
+        raise ValueError("ingest: expected a uint8 image [H,W] or [H,W,C], got %s %s" % (image_u8.dtype, tuple(image_u8.shape)))
+    return image_u8.shape[0], image_u8.shape[1], (image_u8.shape[2] if image_u8.dim() == 3 else 1)
+
+
+def ingest_u8(image_u8, out=None, scratch=None):
+    """uint8 device image [H,W] (grey) or [H,W,C], C = 1, 3 (RGB) or 4 (RGBA, alpha ignored) -> the standardised float32
+    image [H,W] match() reads: bit for bit what match.py computes on the host, util.read_gray's grey conversion and
+    NumPy's (g - mean) / std in NumPy's summation order (csrc/ingest.hip).  `scratch`: an ingest_scratch()."""
+    H, W, C = _u8_image(image_u8)
+    out = out if out is not None else torch.empty((H, W), dtype=torch.float32, device=image_u8.device)
+    scratch = scratch if scratch is not None else ingest_scratch(H, W, image_u8.device)
+    hip.check(hip.load().mccnn_ingest_u8(hip.ptr(image_u8), H, W, C, hip.ptr(out), hip.ptr(scratch),
+                                         scratch.numel() * 4, hip.stream()), "mccnn_ingest_u8")
+    return out
+
+
+def ingest_u8_pair(left_u8, right_u8, out_l=None, out_r=None, scratch=None):
+    """ingest_u8() on both views of a pair (same shape and channel count) in one call; returns (left, right)."""
+    H, W, C = _u8_image(left_u8)
+    if _u8_image(right_u8) != (H, W, C):
+        raise ValueError("ingest_u8_pair: the two images must have the same shape")
+    out_l = out_l if out_l is not None else torch.empty((H, W), dtype=torch.float32, device=left_u8.device)
+    out_r = out_r if out_r is not None else torch.empty((H, W), dtype=torch.float32, device=left_u8.device)
+    scratch = scratch if scratch is not None else ingest_scratch(H, W, left_u8.device)
+    hip.check(hip.load().mccnn_ingest_u8_pair(hip.ptr(left_u8), hip.ptr(right_u8), H, W, C, hip.ptr(out_l), hip.ptr(out_r),
+                                              hip.ptr(scratch), scratch.numel() * 4, hip.stream()),
+              "mccnn_ingest_u8_pair")
+    return out_l, out_r
+
+
 # ---- a3 ----------------------------------------------------------------------------------------------------------
 def support_buffer(H, W, device):
     """An empty support plane (see cross_arms): the [H,W] view of a mccnn_support_bytes(H, W) allocation."""
@@ -948,6 +987,7 @@ class StereoMatcher(object):
         self._graphs = {}
         self._side = None
         self._right = None
+        self._ingest = None
 
     def _right_stream(self):
         """The stream of the right volume's chain of aggregation launches: this matcher's own (like its side stream), so
@@ -1273,6 +1313,71 @@ class StereoMatcher(object):
         # the workspace map is overwritten by the next pair: hand out a copy unless the caller passed its own tensor
         # or (match_graph) wants the static buffer
         return db if (_static_out or out is not None) else db.clone()
+
+    def _ingest_buffers(self, H, W):
+        """Static float32 inputs + ingest scratch of the eager byte path: kept per shape, so that a pair allocates
+        nothing (the workspace is reused by the next pair in the same way)."""
+        b = self._ingest
+        if b is None or b[0] != (H, W):
+            dev = self.device
+            b = ((H, W), torch.empty((H, W), dtype=torch.float32, device=dev),
+                 torch.empty((H, W), dtype=torch.float32, device=dev), ingest_scratch(H, W, dev))
+            self._ingest = b
+        return b[1:]
+
+    def match_u8(self, left_u8, right_u8, ndisp, out=None):
+        """match() straight from the decoded bytes of the two PNGs: uint8 device tensors [H,W] or [H,W,C] (C = 1, 3, 4;
+        see ingest_u8), or pinned host tensors, which are copied in stream order without blocking.  The standardisation runs on the device, bit-identical to match.py's on the host, so the map is
+        what match() returns on the host-standardised images."""
+        H, W, _ = _u8_image(left_u8)
+        sl, sr, scratch = self._ingest_buffers(H, W)
+        left_u8 = left_u8.to(self.device, non_blocking=True).contiguous()
+        right_u8 = right_u8.to(self.device, non_blocking=True).contiguous()
+        ingest_u8_pair(left_u8, right_u8, sl, sr, scratch)
+        return self.match(sl, sr, ndisp, out=out)
+
+    def match_graph_u8(self, left_u8, right_u8, ndisp):
+        """match_graph() from bytes: static uint8 inputs, and the ingest launches INSIDE the captured graph, writing the
+        static float32 images the rest of the graph reads - per pair two byte copies (from the device or from pinned host
+        memory, in stream order, non-blocking) and one replay.  One graph per
+        (H, W, ndisp, C); the rules of match_graph's capture hold (fresh side / right-chain streams per capture, every
+        stream idle before it, two eager warm-up pairs).  Returns the static output map (overwritten by the next call)."""
+        H, W, C = _u8_image(left_u8)
+        if _u8_image(right_u8) != (H, W, C):
+            raise ValueError("match_graph_u8: the two images must have the same shape")
+        key = (H, W, int(ndisp), "u8", C)
+        g = self._graphs.get(key)
+        if g is None:
+            self.workspace(H, W, int(ndisp))     # may reset self._graphs: one shape resident at a time
+            self._side = None
+            self._right = None
+            bl = torch.empty(tuple(left_u8.shape), dtype=torch.uint8, device=self.device)
+            br = torch.empty_like(bl)
+            sl = torch.empty((H, W), dtype=torch.float32, device=self.device)
+            sr = torch.empty((H, W), dtype=torch.float32, device=self.device)
+            scratch = ingest_scratch(H, W, self.device)
+            bl.copy_(left_u8)
+            br.copy_(right_u8)
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(2):
+                    ingest_u8_pair(bl, br, sl, sr, scratch)
+                    self._match(sl, sr, ndisp)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()             # every stream idle before the capture begins (see match_graph)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                ingest_u8_pair(bl, br, sl, sr, scratch)
+                out = self._match(sl, sr, ndisp, _static_out=True)
+            g = (graph, bl, br, sl, sr, out)
+            self._graphs[key] = g
+        graph, bl, br, sl, sr, out = g
+        bl.copy_(left_u8, non_blocking=True)
+        br.copy_(right_u8, non_blocking=True)
+        graph.replay()
+        self._saturated_pair(sl, sr, ndisp, out)      # on_saturation (one host synchronisation unless "ignore")
+        return out
 
     def match_graph(self, left_image, right_image, ndisp):
         """match() replayed as ONE hipGraph launch: the ~75 kernel launches of a pair are captured once per image
