@@ -166,6 +166,20 @@ int mccnn_cbca_iter_hwd_pair_wta(const float *in_left, float *out_left, const mc
                                  int H, int W, int L, float *disparity_left, float *disparity_right, int store_right,
                                  mccnn_stream_t stream);
 
+/* ---- a4 on the pixel-major layout for every distance the support word holds: 1 <= L <= 32 (arms up to 31) ----------
+ * Same contract and same bits as mccnn_cbca_iter_hwd / mccnn_cbca_iter_hwd_pair (whole support buffer written by
+ * mccnn_cross_arms, in != out, no allocation, no synchronisation, D up to 1024), with a register window of 2 pixels x
+ * 63 columns and 128-disparity chunks instead of 5 x 27 and 256: for L <= 14 the result equals mccnn_cbca_iter_hwd's
+ * bit for bit, for 15 <= L <= 32 it equals mccnn_cbca_iter(..., MCCNN_CBCA_REFERENCE_ORDER) on the plane-major volume.
+ * Only plane 0 of the support buffer is read (the window masks are derived from its arm fields).  L > 32:
+ * MCCNN_E_UNSUPPORTED.  The input is addressed row by row, so the shape limit is one image row below 2 GiB.  There is
+ * no fused-WTA form: run mccnn_wta_hwd on the result of the last iteration. */
+int mccnn_cbca_iter_hwd_long(const float *in_hwd, float *out_hwd, const mccnn_support_t *support, int D, int H, int W,
+                             int L, mccnn_stream_t stream);
+int mccnn_cbca_iter_hwd_long_pair(const float *in_left, float *out_left, const mccnn_support_t *support_left,
+                                  const float *in_right, float *out_right, const mccnn_support_t *support_right, int D,
+                                  int H, int W, int L, mccnn_stream_t stream);
+
 /* ---- a4 on the pixel-major layout, program-driven (pf:149-163; round 4) ---------------------------------------------
  * Bit-identical to mccnn_cbca_iter_hwd_pair and faster (0.45 vs 0.55 ms per two-volume iteration at 750x500x256): the
  * per-image control of that kernel - region rows, pixel windows and arm runs of every 4 x 5 patch of anchors - is

@@ -44,6 +44,8 @@ SIGNATURES = {
     "mccnn_cbca_iter_hwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mccnn_cbca_iter_hwd_pair": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mccnn_cbca_iter_hwd_pair_wta": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "mccnn_cbca_iter_hwd_long": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mccnn_cbca_iter_hwd_long_pair": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mccnn_cbca_prog_bytes": (_sz, [_i, _i, _i]),
     "mccnn_cbca_prog_build_pair": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mccnn_cbca_iter_prog_pair": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -184,7 +184,8 @@ def main(argv=None):
                         out_img=os.path.join(img_dir, out_img_file))
 
         def check_shape(height, width, ndisp):      # the flagless loop's refusal, with its message
-            sd.workspace_bytes(height, width, ndisp, matchers[0].pixel_major(), pairs_in_flight=in_flight)
+            sd.workspace_bytes(height, width, ndisp, matchers[0].pixel_major(),
+                               matchers[0].workspace_cbca_kernel(height, width, ndisp), pairs_in_flight=in_flight)
 
         backend = lm.MatcherBackend(matchers, streams, lambda: make_matcher("miopen"), rank=rank)
         pipeline = lm.ListPipeline(lm.make_reader(paths, check_shape), backend, lm.make_writer(rank), slots=in_flight,
@@ -242,7 +243,9 @@ def main(argv=None):
         print("[{}] pair {}: {} | {}  ({}x{}, ndisp {})".format(rank, index, left_path, right_path, width, height, ndisp))
         # refuses a shape outside what the kernels serve (ValueError naming the limit); each matcher checks its own
         # workspace against the free device memory before it allocates it
-        footprint = sd.workspace_bytes(height, width, ndisp, matchers[0].pixel_major(), pairs_in_flight=in_flight)
+        footprint = sd.workspace_bytes(height, width, ndisp, matchers[0].pixel_major(),
+                                       matchers[0].workspace_cbca_kernel(height, width, ndisp),
+                                       pairs_in_flight=in_flight)
         if (height, width, ndisp) != last_shape:
             print("[{}] workspace {:.2f} GB ({} pair(s) in flight)".format(rank, footprint / 1e9, in_flight))
             last_shape = (height, width, ndisp)

@@ -12,9 +12,10 @@ There is no CPU fallback: without a HIP device or without the built library ever
 Options the reference does not have (module attributes; the DEFAULTS are the bit-exact variants, so that a drop-in
 user gets the reference's numbers - the fast ones are opt-in and only tolerance-bounded):
     COST_VOLUME_MODE  "exact" (NumPy summation order, bit-exact, default) | "mfma" (matrix cores, <= 2e-6 abs)
-    CBCA_ORDER        "reference" (flat list order, bit-exact, default: the pixel-major kernel, mccnn_cbca_iter_hwd)
-                      | "reference_plane_major" (the same sums by the plane-major kernel of mccnn_cbca_iter - slower;
-                        also what distances > 14 fall back to) | "separable" (fast, <= 1e-6 abs per iteration)
+    CBCA_ORDER        "reference" (flat list order, bit-exact, default: the pixel-major kernels - mccnn_cbca_iter_hwd
+                        and the aggregation programs up to distance 14, mccnn_cbca_iter_hwd_long for 15 to 32)
+                      | "reference_plane_major" (the same sums by the plane-major kernel of mccnn_cbca_iter - slower)
+                      | "separable" (fast, <= 1e-6 abs per iteration)
 Opt-in departures from the reference's results (defaults reproduce it):
     CBCA_BOTH_VIEWS          False | True  - the paper's support regions intersected with the other view's (pf:122-144
                                              names it and skips it as impractical; pf:661-729 is its dead attempt)
@@ -123,7 +124,9 @@ def cost_volume_aggregation(left_image, right_image, left_cost_volume, right_cos
     was_np = False
     images = [_img(left_image)[0], _img(right_image)[0]]
     supports = [sd.cross_arms(img, intensity_threshold, int(distance_threshold)) for img in images]
-    if not CBCA_BOTH_VIEWS and CBCA_ORDER == "reference" and int(distance_threshold) <= 14:
+    pixel_major = not CBCA_BOTH_VIEWS and CBCA_ORDER == "reference" and sd.aggregation_route(
+        distance_threshold, images[0].shape[1], 1, _CBCA_ORDERS[CBCA_ORDER]) != "plane_major"
+    if pixel_major and int(distance_threshold) <= sd.CBCA_HWD_MAX_DISTANCE:
         # What match.py's default runs: the reference's summation order on pixel-major copies, both views per launch,
         # through the program-driven assembly kernel (its programs are built once here and serve every iteration; from
         # the second iteration on the pixels whose support region is the pixel itself are left alone - same bits).
@@ -146,9 +149,9 @@ def cost_volume_aggregation(left_image, right_image, left_cost_volume, right_cos
         if CBCA_BOTH_VIEWS:
             res, _spare = sd.cbca_both_views(v, torch.empty_like(v), supports[k], supports[1 - k], int(max_average_time),
                                              int(distance_threshold), hip.MCCNN_SIDE_LEFT if k == 0 else hip.MCCNN_SIDE_RIGHT)
-        elif CBCA_ORDER == "reference" and int(distance_threshold) <= 14:
-            # the reference's summation order on a pixel-major copy (disparities on lanes): bit-identical to the
-            # plane-major reference-order kernel, several times faster
+        elif pixel_major:
+            # the reference's summation order on a pixel-major copy (disparities on lanes; sd.cbca_hwd picks the kernel
+            # by distance): bit-identical to the plane-major reference-order kernel, several times faster
             D = v.shape[0]
             hv = sd.dhw_to_hwd(v)
             hres, _spare = sd.cbca_hwd(hv, torch.empty_like(hv), supports[k], D, int(max_average_time),

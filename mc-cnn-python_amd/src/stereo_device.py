@@ -325,19 +325,54 @@ def _check_support(support, H, W, who):
         raise ValueError("%s: `support` must be the tensor cross_arms() returned (a copy drops its derived planes)" % who)
 
 
+CBCA_HWD_MAX_DISTANCE = 14     # mccnn_cbca_iter_hwd* and the aggregation programs: arms up to 13
+CBCA_MAX_DISTANCE = 32         # the support word's 5-bit arms (mccnn_cross_arms, mccnn_cbca_iter_hwd_long*)
+
+
+def aggregation_route(distance, W, D, order=hip.MCCNN_CBCA_REFERENCE_ORDER, extras=None, layout="auto",
+                      cbca_kernel="auto", H=1):
+    """Which aggregation kernel a pair takes - the one decision StereoMatcher, workspace_bytes' callers and
+    process_functional share.  Needs no device (only the library's host-side shape rule).  Returns
+        "plane_major"  layout="plane_major", the separable order or two-view regions: every stage on [D,H,W]
+        "prog"         pixel-major, distance <= 14, and the aggregation programs encode the shape (and cbca_kernel
+                       is not "hwd")
+        "hwd"          pixel-major, distance <= 14 otherwise (mccnn_cbca_iter_hwd_pair)
+        "hwd_long"     pixel-major, 15 <= distance <= 32 (mccnn_cbca_iter_hwd_long_pair; no program buffers)
+    and raises ValueError for a distance outside [1, CBCA_MAX_DISTANCE]."""
+    distance = int(distance)
+    if distance < 1 or distance > CBCA_MAX_DISTANCE:
+        raise ValueError("cbca_distance=%d outside [1, %d]: the support word holds 5-bit arms" % (distance, CBCA_MAX_DISTANCE))
+    if layout not in ("auto", "plane_major"):
+        raise ValueError("layout must be 'auto' or 'plane_major'")
+    if layout != "auto" or order != hip.MCCNN_CBCA_REFERENCE_ORDER or (extras or {}).get("both_view_support"):
+        return "plane_major"
+    if distance > CBCA_HWD_MAX_DISTANCE:
+        return "hwd_long"
+    if cbca_kernel != "hwd" and int(hip.load().mccnn_cbca_prog_bytes(int(D), int(H), int(W))) != 0:
+        return "prog"
+    return "hwd"
+
+
+def route_cbca_kernel(route, cbca_kernel="auto"):
+    """The `cbca_kernel` to hand workspace_bytes for a route: "hwd" where no program buffers are allocated."""
+    return "hwd" if route in ("hwd", "hwd_long") else cbca_kernel
+
+
 def cbca_hwd(vol, tmp, support, D, iterations, distance_threshold, timer=None):
     """`iterations` rounds of cross-based averaging in the reference's summation order (bit-exact) on a pixel-major
-    volume [H,W,Dp] (mccnn_cbca_iter_hwd).  Same ping-pong contract as cbca(): returns (result, spare)."""
+    volume [H,W,Dp]: mccnn_cbca_iter_hwd for distances up to CBCA_HWD_MAX_DISTANCE, mccnn_cbca_iter_hwd_long for 15 to
+    CBCA_MAX_DISTANCE.  Same ping-pong contract as cbca(): returns (result, spare)."""
     H, W, Dp = vol.shape
     assert Dp == hwd_pitch(D) and tuple(tmp.shape) == (H, W, Dp)
     _check_support(support, H, W, "cbca_hwd")
     lib = hip.load()
     src, dst = vol, tmp
     timer = timer or _NO_TIMER
+    name = "mccnn_cbca_iter_hwd" if int(distance_threshold) <= CBCA_HWD_MAX_DISTANCE else "mccnn_cbca_iter_hwd_long"
     for _ in range(int(iterations)):
         timer.start("cbca_iter_hwd")
-        hip.check(lib.mccnn_cbca_iter_hwd(hip.ptr(src), hip.ptr(dst), hip.ptr(support), int(D), H, W,
-                                          int(distance_threshold), hip.stream()), "mccnn_cbca_iter_hwd")
+        hip.check(getattr(lib, name)(hip.ptr(src), hip.ptr(dst), hip.ptr(support), int(D), H, W,
+                                     int(distance_threshold), hip.stream()), name)
         timer.stop()
         src, dst = dst, src
     return src, dst
@@ -350,7 +385,8 @@ def cbca_hwd_wta_max_d():
 
 def cbca_hwd_pair(vol_l, tmp_l, support_l, vol_r, tmp_r, support_r, D, iterations, distance_threshold, timer=None,
                   wta_out=None, store_right=True):
-    """cbca_hwd() on the left and the right volume, one launch per iteration (mccnn_cbca_iter_hwd_pair).
+    """cbca_hwd() on the left and the right volume, one launch per iteration (mccnn_cbca_iter_hwd_pair, or
+    mccnn_cbca_iter_hwd_long_pair for distances above CBCA_HWD_MAX_DISTANCE - which has no fused-WTA form).
     Returns ((result_l, spare_l), (result_r, spare_r)).  wta_out = (disp_l, disp_r) [H,W] float32: the last iteration
     also writes the WTA disparities of both results (mccnn_cbca_iter_hwd_pair_wta; D <= cbca_hwd_wta_max_d());
     store_right=False then leaves the right result volume unwritten (its returned tensor holds stale data)."""
@@ -365,8 +401,11 @@ def cbca_hwd_pair(vol_l, tmp_l, support_l, vol_r, tmp_r, support_r, D, iteration
     (sl, dl), (sr, dr) = (vol_l, tmp_l), (vol_r, tmp_r)
     timer = timer or _NO_TIMER
     n = int(iterations)
-    if wta_out is not None and (n < 1 or D > cbca_hwd_wta_max_d()):
-        raise ValueError("cbca_hwd_pair: the fused WTA needs at least one iteration and D <= %d" % cbca_hwd_wta_max_d())
+    long_arms = int(distance_threshold) > CBCA_HWD_MAX_DISTANCE
+    if wta_out is not None and (n < 1 or D > cbca_hwd_wta_max_d() or long_arms):
+        raise ValueError("cbca_hwd_pair: the fused WTA needs at least one iteration, D <= %d and a distance <= %d"
+                         % (cbca_hwd_wta_max_d(), CBCA_HWD_MAX_DISTANCE))
+    pair_name = "mccnn_cbca_iter_hwd_long_pair" if long_arms else "mccnn_cbca_iter_hwd_pair"
     for it in range(n):
         timer.start("cbca_iter_hwd_pair")
         if wta_out is not None and it == n - 1:
@@ -379,9 +418,9 @@ def cbca_hwd_pair(vol_l, tmp_l, support_l, vol_r, tmp_r, support_r, D, iteration
                                                        1 if store_right else 0, hip.stream()),
                       "mccnn_cbca_iter_hwd_pair_wta")
         else:
-            hip.check(lib.mccnn_cbca_iter_hwd_pair(hip.ptr(sl), hip.ptr(dl), hip.ptr(support_l), hip.ptr(sr), hip.ptr(dr),
-                                                   hip.ptr(support_r), int(D), H, W, int(distance_threshold),
-                                                   hip.stream()), "mccnn_cbca_iter_hwd_pair")
+            hip.check(getattr(lib, pair_name)(hip.ptr(sl), hip.ptr(dl), hip.ptr(support_l), hip.ptr(sr), hip.ptr(dr),
+                                              hip.ptr(support_r), int(D), H, W, int(distance_threshold),
+                                              hip.stream()), pair_name)
         timer.stop()
         sl, dl, sr, dr = dl, sl, dr, sr
     return (sl, dl), (sr, dr)
@@ -1005,7 +1044,7 @@ class StereoMatcher(object):
         key = (H, W, D)
         ws = self._ws.get(key)
         if ws is None:
-            need = workspace_bytes(H, W, D, self.pixel_major(), self.cbca_kernel)
+            need = workspace_bytes(H, W, D, self.pixel_major(), self.workspace_cbca_kernel(H, W, D))
             self._ws, self._graphs = {}, {}          # one shape resident at a time: the previous one goes first
             _require_device_memory(need, "StereoMatcher: the workspace of a %dx%d pair with ndisp=%d" % (W, H, D))
             dp = hwd_pitch(D)
@@ -1020,22 +1059,33 @@ class StereoMatcher(object):
                 maps=torch.empty((6, H, W), dtype=torch.float32, device=dev),   # dl, dr, interp, subpixel, median, out
             )
             ws["progs"] = None
-            if self.pixel_major() and self.cbca_kernel != "hwd":
+            # (distances above CBCA_HWD_MAX_DISTANCE: the aggregation programs do not encode such arms - the joined
+            # two-volume path of mccnn_cbca_iter_hwd_long_pair runs, as for shapes the programs do not encode)
+            if self.route(H, W, D) == "prog":
                 ws["progs"] = cbca_prog_buffers(D, H, W, dev)
-                if ws["progs"] is None and self.cbca_kernel == "prog":
-                    raise ValueError("cbca_kernel='prog': %dx%dx%d is outside what the aggregation programs encode" % (W, H, D))
+            elif self.pixel_major() and self.cbca_kernel == "prog":
+                raise ValueError("cbca_kernel='prog': %dx%dx%d (cbca_distance %d) is outside what the aggregation "
+                                 "programs encode" % (W, H, D, int(self.hp["cbca_distance"])))
             bilateral_table_device(5, 5, 0, self.hp["blur_sigma"], dev)
             self._ws = {key: ws}  # one shape resident at a time
             self._graphs = {}
         return ws
 
+    def route(self, H, W, D):
+        """aggregation_route() of this matcher for a pair shape."""
+        return aggregation_route(self.hp["cbca_distance"], W, D, self.cbca_order, self.extras, self.layout,
+                                 self.cbca_kernel, H)
+
+    def workspace_cbca_kernel(self, H, W, D):
+        """The `cbca_kernel` argument under which workspace_bytes states what workspace() allocates."""
+        return route_cbca_kernel(self.route(H, W, D), self.cbca_kernel)
+
     def pixel_major(self):
         """True when the pair runs on pixel-major volumes from the first aggregation on: the bit-exact variant
-        (reference-order CBCA, arms <= 13, no two-view regions).  CBCA, SGM, WTA and sub-pixel then all work on
-        [H,W,Dp] and no layout change surrounds the SGM stage."""
-        return (self.layout == "auto" and self.cbca_order == hip.MCCNN_CBCA_REFERENCE_ORDER
-                and not self.extras["both_view_support"]
-                and int(self.hp["cbca_distance"]) <= 14)
+        (reference-order CBCA, any distance the support word holds, no two-view regions).  CBCA, SGM, WTA and
+        sub-pixel then all work on [H,W,Dp] and no layout change surrounds the SGM stage."""
+        return aggregation_route(self.hp["cbca_distance"], 1, 1, self.cbca_order, self.extras, self.layout,
+                                 "hwd") != "plane_major"
 
     def _saturated_pair(self, left_image, right_image, ndisp, out):
         """on_saturation for the pair that has just been launched: None when its features were fine (or nobody is to
@@ -1165,7 +1215,8 @@ class StereoMatcher(object):
             progs = ws["progs"]
 
             def aggregate_hwd(lh, lt, rh, rt, n, **kw):
-                # the program-driven assembly kernel where its programs exist, cbca_hwd_kernel otherwise (same bits)
+                # the program-driven assembly kernel where its programs exist, cbca_hwd_kernel or - distances above
+                # CBCA_HWD_MAX_DISTANCE - cbca_hwd_long_kernel otherwise (same bits)
                 if progs is None:
                     return cbca_hwd_pair(lh, lt, sup_l, rh, rt, sup_r, D, int(n), hp["cbca_distance"], timer, **kw)
                 return cbca_prog_pair(lh, lt, sup_l, rh, rt, sup_r, progs, D, int(n), hp["cbca_distance"], timer,
@@ -1237,7 +1288,8 @@ class StereoMatcher(object):
                 keep["sgm"] = (hwd_to_dhw(lh, D), hwd_to_dhw(rh, D))
             # the last iteration carries the WTA of both results (and leaves the right volume, which nothing else
             # reads, unwritten) when a wave holds all disparities of a pixel
-            fuse = int(hp["cbca_num_iterations2"]) >= 1 and D <= cbca_hwd_wta_max_d()
+            fuse = (int(hp["cbca_num_iterations2"]) >= 1 and D <= cbca_hwd_wta_max_d()
+                    and int(hp["cbca_distance"]) <= CBCA_HWD_MAX_DISTANCE)
             if not free:
                 timer.span_start("aggregation_2")
                 (lh, lt), (rh, rt) = aggregate_hwd(lh, lt, rh, rt, hp["cbca_num_iterations2"],
