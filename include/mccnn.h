@@ -105,6 +105,9 @@ int mccnn_cross_arms(const float *image, int H, int W, float tau, int L, mccnn_s
  * same results as two mccnn_cross_arms calls, half the launches. */
 int mccnn_cross_arms_pair(const float *image_left, const float *image_right, int H, int W, float tau, int L,
                           mccnn_support_t *support_left, mccnn_support_t *support_right, mccnn_stream_t stream);
+/* region: [H][W][(2L)^2][2] int32.  L must not be smaller than the distance the plane was built with (a pixel's list
+ * would overrun its (2L)^2 slots): like the aggregation entry points, a plane this library built with longer arms or
+ * for another image size is refused (MCCNN_E_INVALID); addresses it has never seen pass. */
 int mccnn_cross_region_list(const mccnn_support_t *support, int H, int W, int L, int32_t *region,
                             mccnn_stream_t stream);
 
@@ -299,15 +302,21 @@ int mccnn_sgm_first_pass(const float *image_left, const float *image_right, cons
 
 /* ---- a7  disparity_prediction, one volume (pf:239-272): first strict minimum over d, as float32 --------------
  * A pixel whose D costs are all NaN / +inf gets -1 (the reference asserts there, pf:253); mccnn_lr_status treats a
- * negative or NaN disparity as an occlusion. */
+ * disparity <= -1 or NaN as an occlusion. */
 int mccnn_wta(const float *vol_dhw, int D, int H, int W, float *disparity, mccnn_stream_t stream);
 
 /* The same on a pixel-major volume [H][W][Dp] (one 1 KiB run per pixel at D = 256): same index, same -1 rule. */
 int mccnn_wta_hwd(const float *vol_hwd, int D, int H, int W, float *disparity, mccnn_stream_t stream);
 
 /* ---- a8  interpolation (pf:279-378) -------------------------------------------------------------------------
- * mccnn_lr_status: 0 match, 1 mismatch, 2 occlusion (pf:285-307).  mccnn_interpolate: status 1 -> median of the
- * nearest status-0 pixel right/left/below/above, status 2 -> nearest status-0 pixel to the right, else raw. */
+ * mccnn_lr_status: 0 match, 1 mismatch, 2 occlusion (pf:285-307).  A left disparity is truncated toward zero (pf:287:
+ * values in (-1, 0) count as 0); one that is <= -1 or NaN, which the reference cannot index, is an occlusion.  Right
+ * disparities may hold anything (NaN, +-inf, negative, >= D match nothing).  Rows wider than 16384 pixels put the image
+ * rows on grid.y: H <= 65535 there (MCCNN_E_UNSUPPORTED beyond).
+ * mccnn_interpolate: status 1 -> median (np.median: a median of -0.0 is +0.0) of the nearest status-0 pixel
+ * right/left/below/above, status 2 -> nearest status-0 pixel to the right, else raw.  `out` must alias neither
+ * disp_left nor status (MCCNN_E_INVALID: other threads still read both); H <= 65535 (MCCNN_E_UNSUPPORTED beyond), also
+ * for mccnn_interpolate_ex. */
 int mccnn_lr_status(const float *disp_left, const float *disp_right, int H, int W, int D, int32_t *status,
                     mccnn_stream_t stream);
 int mccnn_interpolate(const float *disp_left, const int32_t *status, int H, int W, float *out,
@@ -330,12 +339,15 @@ int mccnn_subpixel_ex(const float *disp, const float *vol_dhw, int D, int H, int
 int mccnn_subpixel_hwd(const float *disp, const float *vol_hwd, int D, int H, int W, int numpy1_promotion, float *out,
                        mccnn_stream_t stream);
 
-/* ---- a10 median_filter (pf:403-421): clipped fh x fw window (odd sizes, fh*fw <= 49), np.median ------------- */
+/* ---- a10 median_filter (pf:403-421): clipped fh x fw window (odd sizes, fh*fw <= 49), np.median -------------
+ * np.median to the bit: NaN in the window gives NaN, and a median of -0.0 is +0.0 (np.mean's sum starts from +0).
+ * Other window sizes and H > 65535 (rows go on grid.y): MCCNN_E_UNSUPPORTED. */
 int mccnn_median(const float *disp, int H, int W, int fh, int fw, float *out, mccnn_stream_t stream);
 
 /* ---- a11 bilateral_filter (pf:424-470) ----------------------------------------------------------------------
  * table: device [fh][fw] float32 spatial kernel (util.normal evaluated on the host, pf:428-436); thr gates
- * |I(q)-I(p)| < thr.  Sums follow NumPy's pairwise order over the clipped window (pf:463,466): bit-exact. */
+ * |I(q)-I(p)| < thr.  Sums follow NumPy's pairwise order over the clipped window (pf:463,466): bit-exact, a gated-out
+ * tap included (0 * NaN = NaN, as NumPy computes it).  Window sizes and the row limit as for mccnn_median. */
 int mccnn_bilateral(const float *image, const float *disp, int H, int W, int fh, int fw, const float *table,
                     float thr, float *out, mccnn_stream_t stream);
 
@@ -358,9 +370,11 @@ int mccnn_ingest_u8_pair(const uint8_t *left_u8, const uint8_t *right_u8, int H,
 /* ---- a1 epilogues of the conv stack (model.py:51-64, 111-125) ------------------------------------------------
  * mccnn_bias_act: x[n][c][i] = act(x[n][c][i] + bias[c]) in place on an NCHW tensor (plane = H*W elements) -
  *   tf.nn.bias_add + tf.nn.relu of model.py:118-123 in ONE pass over the activations (relu != 0), or the bias
- *   alone (relu == 0).  The convolution itself runs in PyTorch-ROCm/MIOpen without bias.
+ *   alone (relu == 0).  The convolution itself runs in PyTorch-ROCm/MIOpen without bias.  The ReLU here and in
+ *   mccnn_conv1_pad_bias_relu keeps a NaN (as NumPy's, torch's and TensorFlow's do) and gives +0.0 for -0.0; N*C <= 65535.
  * mccnn_l2norm_chw_to_hwc: tf.nn.l2_normalize over channels (model.py:64), x * rsqrt(max(sum x^2, 1e-12)), fused
- *   with the last layer's bias (bias may be NULL) and the layout change NCHW [C][H][W] -> NHWC [H][W][C]. */
+ *   with the last layer's bias (bias may be NULL) and the layout change NCHW [C][H][W] -> NHWC [H][W][C]; a NaN
+ *   channel makes its whole pixel NaN (tf.maximum keeps a NaN sum).  C = 64 only (MCCNN_E_UNSUPPORTED otherwise). */
 int mccnn_bias_act(float *x, const float *bias, int N, int C, long plane, int relu, mccnn_stream_t stream);
 /* First layer fused with the input padding (pf:20-25, model.py:51-53): images [N][H][W] -> out [N][C][H+2pad-2]
  * [W+2pad-2] = relu(conv3x3_valid(zero_pad(image, pad), weights [C][1][3][3]) + bias [C]). */

@@ -1002,6 +1002,8 @@ extern "C" int mccnn_cross_region_list(const mccnn_support_t *support, int H, in
     using namespace mccnn;
     MCCNN_REQUIRE(support && region, MCCNN_E_INVALID, "mccnn_cross_region_list: null pointer");
     MCCNN_REQUIRE(H > 0 && W > 0 && L >= 1, MCCNN_E_INVALID, "mccnn_cross_region_list: bad size");
+    // a pixel has (2L)^2 slots: a plane built with longer arms than L would overrun them (unknown pointers pass)
+    if (const int rc = check_support_record(support, H, W, L, "mccnn_cross_region_list")) return rc;
     const dim3 grid(cdiv(W, 256), H), block(256);
     hipLaunchKernelGGL(cross_region_list_kernel, grid, block, 0, (hipStream_t)stream, support, H, W, (2 * L) * (2 * L),
                        region);

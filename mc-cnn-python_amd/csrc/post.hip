@@ -36,6 +36,7 @@ __global__ __launch_bounds__(256) void wta_kernel(const float *__restrict__ vol,
 // pixel x with value r can satisfy that only for d within a few integers of r, i.e. for w = x + d in a handful of
 // places; every thread evaluates the reference's own float32 expression for those candidates of its x and sets the
 // bits of the w it hits in a row mask in LDS.  Same predicate, same arithmetic, O(1) per pixel.
+constexpr int MAX_GRID_Y = 65535;   // kernels that put image rows on blockIdx.y refuse taller images
 constexpr int LR_MAX_WORDS = 512;   // rows up to 16384 pixels; wider rows take lr_status_walk_kernel
 
 __global__ __launch_bounds__(256) void lr_status_kernel(const float *__restrict__ dl, const float *__restrict__ dr,
@@ -62,10 +63,11 @@ __global__ __launch_bounds__(256) void lr_status_kernel(const float *__restrict_
         const float lf = dl[(size_t)h * W + w];
         const int ld = (int)lf;  // pf:287 int() truncation
         int st;
-        if (!(lf >= 0.f) || w < ld) {
-            // pf:289-291.  A negative or NaN disparity cannot come out of the reference (its WTA asserts a finite
+        if (!(lf > -1.f) || w < ld) {
+            // pf:289-291.  A disparity <= -1 or NaN cannot come out of the reference (its WTA asserts a finite
             // minimum, pf:253); mccnn_wta writes -1 for a pixel whose costs are all NaN/+inf, and such a pixel is treated
-            // as occluded here instead of indexing the right map out of bounds.
+            // as occluded here instead of indexing the right map out of bounds.  Values in (-1, 0) truncate to 0
+            // (pf:287) like everywhere else.
             st = 2;
         } else if (fabsf((float)ld - drow[w - ld]) <= 1.f) {
             st = 0;  // pf:294
@@ -86,7 +88,7 @@ __global__ __launch_bounds__(256) void lr_status_walk_kernel(const float *__rest
     const float lf = dl[(size_t)h * W + w];
     const int ld = (int)lf;
     int st;
-    if (!(lf >= 0.f) || w < ld) {
+    if (!(lf > -1.f) || w < ld) {
         st = 2;
     } else if (fabsf((float)ld - drow[w - ld]) <= 1.f) {
         st = 0;
@@ -102,15 +104,16 @@ __global__ __launch_bounds__(256) void lr_status_walk_kernel(const float *__rest
 __device__ __forceinline__ float median_upto4(float *v, int n)
 {
     // np.median of 1..n float32 values (n <= 4 in the reference's rule, <= 16 in the paper's): sort, middle element or
-    // mean of the two middle ones
+    // mean of the two middle ones.  np.median ends in np.mean, whose float32 sum starts from +0: a median of -0.0 comes
+    // out as +0.0 (0.f + x; every other value, NaN and inf included, is unchanged by it)
     for (int i = 1; i < n; ++i) {
         const float x = v[i];
         int j = i - 1;
         while (j >= 0 && v[j] > x) { v[j + 1] = v[j]; --j; }
         v[j + 1] = x;
     }
-    if (n & 1) return v[n >> 1];
-    return (v[(n >> 1) - 1] + v[n >> 1]) / 2.f;
+    if (n & 1) return 0.f + v[n >> 1];
+    return (0.f + (v[(n >> 1) - 1] + v[n >> 1])) / 2.f;
 }
 
 // The two rules the reference names but leaves out (pf:318 "in origin paper, they use 16 directions", pf:361 "they use
@@ -332,8 +335,8 @@ __global__ __launch_bounds__(256) void median_kernel(const float *__restrict__ d
         }
     float res;
     if (has_nan) res = __builtin_nanf("");  // np.median propagates NaN
-    else if (n & 1) res = v[n >> 1];
-    else res = (v[(n >> 1) - 1] + v[n >> 1]) / 2.f;  // np.mean of the two middle float32 values
+    else if (n & 1) res = 0.f + v[n >> 1];           // np.mean of one value: the sum starts from +0 (-0.0 -> +0.0)
+    else res = (0.f + (v[(n >> 1) - 1] + v[n >> 1])) / 2.f;  // np.mean of the two middle float32 values
     out[(size_t)h * W + w] = res;
 }
 
@@ -373,10 +376,12 @@ __global__ __launch_bounds__(256) void median5x5_kernel(const float *__restrict_
         case 25: res = v[12]; break;
         case 15: res = v[7]; break;
         case 9: res = v[4]; break;
-        case 20: res = (v[9] + v[10]) / 2.f; break;    // np.mean of the two middle float32 values
-        case 16: res = (v[7] + v[8]) / 2.f; break;
-        default: res = (v[5] + v[6]) / 2.f; break;     // 12
+        case 20: res = v[9] + v[10]; break;            // np.mean of the two middle float32 values
+        case 16: res = v[7] + v[8]; break;
+        default: res = v[5] + v[6]; break;             // 12
     }
+    res = 0.f + res;                                   // np.mean's sum starts from +0: a median of -0.0 is +0.0
+    if (!(n & 1)) res = res / 2.f;
     if (has_nan) res = __builtin_nanf("");  // np.median propagates NaN
     out[(size_t)h * W + w] = res;
 }
@@ -494,6 +499,10 @@ __global__ __launch_bounds__(256) void bilateral5x5_kernel(const float *__restri
 }
 
 // ---- a1 epilogues -------------------------------------------------------------------------------------------------
+// ReLU as NumPy's, torch's and TensorFlow's compute it: a NaN stays a NaN (fmaxf(NaN, 0) is 0 and would hand back finite
+// features for a NaN image).  ReLU(-0.0) = +0.0, as fmaxf gave on this hardware: every non-NaN input keeps its bits.
+__device__ __forceinline__ float relu_nan(float t) { return t <= 0.f ? 0.f : t; }
+
 // bias (+ ReLU) in place over an NCHW tensor: blockIdx.y = n*C + c, 4 consecutive elements per thread (planes start at
 // arbitrary 4-byte offsets, so the 16-byte accesses are declared 4-byte aligned)
 __global__ __launch_bounds__(256) void bias_act_kernel(float *__restrict__ x, const float *__restrict__ bias, int C,
@@ -508,13 +517,13 @@ __global__ __launch_bounds__(256) void bias_act_kernel(float *__restrict__ x, co
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float t = v[j] + b;
-            v[j] = relu ? fmaxf(t, 0.f) : t;
+            v[j] = relu ? relu_nan(t) : t;
         }
         *reinterpret_cast<f4u *>(p + i) = v;
     } else {
         for (long j = i; j < plane; ++j) {
             const float t = p[j] + b;
-            p[j] = relu ? fmaxf(t, 0.f) : t;
+            p[j] = relu ? relu_nan(t) : t;
         }
     }
 }
@@ -546,7 +555,7 @@ __global__ __launch_bounds__(256) void conv1_pad_bias_relu_kernel(const float *_
 #pragma unroll
         for (int k = 0; k < 9; ++k) acc += w[c * 9 + k] * v[k];
         acc += bias[c];
-        o[(size_t)c * Ho * Wo] = fmaxf(acc, 0.f);
+        o[(size_t)c * Ho * Wo] = relu_nan(acc);
     }
 }
 
@@ -568,7 +577,7 @@ __global__ __launch_bounds__(256) void l2norm_chw_to_hwc_kernel(const float *__r
     if (ty == 0) {
         float s = 0.f;
         for (int c = 0; c < C; ++c) s = fmaf(tile[c][tx], tile[c][tx], s);
-        s = fmaxf(s, 1e-12f);
+        s = s < 1e-12f ? 1e-12f : s;   // np.maximum / tf.maximum: a NaN sum stays NaN (fmaxf would drop it)
         scale[tx] = 1.f / sqrtf(s);
     }
     __syncthreads();
@@ -596,6 +605,8 @@ extern "C" int mccnn_lr_status(const float *disp_left, const float *disp_right, 
     using namespace mccnn;
     MCCNN_REQUIRE(disp_left && disp_right && status, MCCNN_E_INVALID, "mccnn_lr_status: null pointer");
     MCCNN_REQUIRE(D > 0 && H > 0 && W > 0, MCCNN_E_INVALID, "mccnn_lr_status: non-positive size");
+    MCCNN_REQUIRE(W <= 32 * LR_MAX_WORDS || H <= MAX_GRID_Y, MCCNN_E_UNSUPPORTED,
+                  "mccnn_lr_status: H=%d exceeds grid.y for rows wider than %d", H, 32 * LR_MAX_WORDS);
     if (W <= 32 * LR_MAX_WORDS)
         hipLaunchKernelGGL(lr_status_kernel, dim3(H), dim3(256), 0, (hipStream_t)stream, disp_left, disp_right, H, W, D,
                            status);
@@ -612,7 +623,10 @@ extern "C" int mccnn_interpolate(const float *disp_left, const int32_t *status, 
     MCCNN_REQUIRE(disp_left && status && out, MCCNN_E_INVALID, "mccnn_interpolate: null pointer");
     MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "mccnn_interpolate: non-positive size");
     MCCNN_REQUIRE(disp_left != out, MCCNN_E_INVALID, "mccnn_interpolate: out must not alias the input map");
-    if (H < 65535 && W <= 64 * INTERP_MAX_WORDS && (const void *)status != (const void *)out) {
+    MCCNN_REQUIRE((const void *)status != (const void *)out, MCCNN_E_INVALID,
+                  "mccnn_interpolate: out must not alias the status map");
+    MCCNN_REQUIRE(H <= MAX_GRID_Y, MCCNN_E_UNSUPPORTED, "mccnn_interpolate: H=%d exceeds grid.y", H);
+    if (H < 65535 && W <= 64 * INTERP_MAX_WORDS) {
         hipLaunchKernelGGL(interpolate_vertical_kernel, dim3(cdiv(W, 64), 2), dim3(64), 0, (hipStream_t)stream, status, H,
                            W, reinterpret_cast<uint16_t *>(out));
         int rc = check_launch("mccnn_interpolate(vertical)");
@@ -633,6 +647,9 @@ extern "C" int mccnn_interpolate_ex(const float *disp_left, const int32_t *statu
     MCCNN_REQUIRE(disp_left && status && out, MCCNN_E_INVALID, "mccnn_interpolate_ex: null pointer");
     MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "mccnn_interpolate_ex: non-positive size");
     MCCNN_REQUIRE(disp_left != out, MCCNN_E_INVALID, "mccnn_interpolate_ex: out must not alias the input map");
+    MCCNN_REQUIRE((const void *)status != (const void *)out, MCCNN_E_INVALID,
+                  "mccnn_interpolate_ex: out must not alias the status map");
+    MCCNN_REQUIRE(H <= MAX_GRID_Y, MCCNN_E_UNSUPPORTED, "mccnn_interpolate_ex: H=%d exceeds grid.y", H);
     MCCNN_REQUIRE(directions == 4 || directions == 16, MCCNN_E_INVALID, "mccnn_interpolate_ex: directions=%d (4 or 16)",
                   directions);
     const dim3 grid(cdiv(W, 256), H), block(256);
@@ -684,6 +701,7 @@ extern "C" int mccnn_median(const float *disp, int H, int W, int fh, int fw, flo
     MCCNN_REQUIRE(disp != out, MCCNN_E_INVALID, "mccnn_median: out must not alias the input map");
     MCCNN_REQUIRE(fh >= 1 && fw >= 1 && (fh & 1) && (fw & 1) && fh * fw <= MAXWIN, MCCNN_E_UNSUPPORTED,
                   "mccnn_median: window %dx%d must be odd x odd with at most %d taps", fh, fw, MAXWIN);
+    MCCNN_REQUIRE(H <= MAX_GRID_Y, MCCNN_E_UNSUPPORTED, "mccnn_median: H=%d exceeds grid.y", H);
     if (fh == 5 && fw == 5 && H >= 5 && W >= 5)
         hipLaunchKernelGGL(median5x5_kernel, dim3(cdiv(W, 256), H), dim3(256), 0, (hipStream_t)stream, disp, H, W, out);
     else
@@ -701,6 +719,7 @@ extern "C" int mccnn_bilateral(const float *image, const float *disp, int H, int
     MCCNN_REQUIRE(disp != out, MCCNN_E_INVALID, "mccnn_bilateral: out must not alias the input map");
     MCCNN_REQUIRE(fh >= 1 && fw >= 1 && (fh & 1) && (fw & 1) && fh * fw <= MAXWIN, MCCNN_E_UNSUPPORTED,
                   "mccnn_bilateral: window %dx%d must be odd x odd with at most %d taps", fh, fw, MAXWIN);
+    MCCNN_REQUIRE(H <= MAX_GRID_Y, MCCNN_E_UNSUPPORTED, "mccnn_bilateral: H=%d exceeds grid.y", H);
     if (fh == 5 && fw == 5)
         hipLaunchKernelGGL(bilateral5x5_kernel, dim3(cdiv(W, 256), H), dim3(256), 0, (hipStream_t)stream, image, disp, H,
                            W, table, thr, out);

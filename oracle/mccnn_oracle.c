@@ -355,7 +355,11 @@ void orc_lr_status(const float *dl, const float *dr, int H, int W, int D, int32_
 {
     for (int h = 0; h < H; h++)
         for (int w = 0; w < W; w++) {
-            int ld = (int)dl[(size_t)h * W + w]; /* pf:287 */
+            float lf = dl[(size_t)h * W + w];
+            /* a disparity <= -1 (mccnn_wta's -1) or NaN indexes the right map out of bounds in the reference:
+             * include/mccnn.h makes it an occlusion; (-1, 0) truncates to 0 (pf:287) */
+            if (!(lf > -1.f)) { status[(size_t)h * W + w] = 2; continue; }
+            int ld = (int)lf; /* pf:287 */
             int32_t st = 0;
             if (w < ld) { status[(size_t)h * W + w] = 2; continue; } /* pf:289-291 */
             float rd = dr[(size_t)h * W + (w - ld)];
@@ -376,8 +380,9 @@ static float median_small(float *v, int n)
         while (j >= 0 && v[j] > x) { v[j + 1] = v[j]; j--; }
         v[j + 1] = x;
     }
-    if (n & 1) return v[n / 2];
-    return (v[n / 2 - 1] + v[n / 2]) / 2.f; /* np.median -> np.mean of the two middle values, float32 */
+    /* np.median -> np.mean of the middle value(s), float32; the mean's sum starts from +0, so -0.0 becomes +0.0 */
+    if (n & 1) return 0.f + v[n / 2];
+    return (0.f + (v[n / 2 - 1] + v[n / 2])) / 2.f;
 }
 
 void orc_interpolation(const float *dl, const float *dr, int H, int W, int D, float *out)
@@ -453,7 +458,8 @@ void orc_median(const float *dl, int H, int W, int fh, int fw, float *out)
                 }
             if (has_nan) { out[(size_t)h * W + w] = NAN; continue; } /* np.median propagates NaN */
             qsort(buf, n, sizeof(float), cmp_float);
-            out[(size_t)h * W + w] = (n & 1) ? buf[n / 2] : (buf[n / 2 - 1] + buf[n / 2]) / 2.f;
+            /* np.mean of the middle value(s): the float32 sum starts from +0 (a median of -0.0 is +0.0) */
+            out[(size_t)h * W + w] = (n & 1) ? 0.f + buf[n / 2] : (0.f + (buf[n / 2 - 1] + buf[n / 2])) / 2.f;
         }
     free(buf);
 }
