@@ -24,6 +24,7 @@ class StageTimer(object):
     def __init__(self, enabled=False):
         self.enabled = enabled
         self.records = []  # (name, start_event, end_event)
+        self.spans = []    # [name, start_event, end_event or None while open]
         self._open = None
 
     def start(self, name):
@@ -47,20 +48,20 @@ class StageTimer(object):
         if self.enabled:
             ev = torch.cuda.Event(enable_timing=True)
             ev.record()
-            self.__dict__.setdefault("spans", []).append([name, ev, None])
+            self.spans.append([name, ev, None])
 
     def span_stop(self, name):
         if self.enabled:
             ev = torch.cuda.Event(enable_timing=True)
             ev.record()
-            for s in reversed(self.__dict__.get("spans", [])):
+            for s in reversed(self.spans):
                 if s[0] == name and s[2] is None:
                     s[2] = ev
                     break
 
     def spans_ms(self):
         out = {}
-        for name, a, b in self.__dict__.get("spans", []):
+        for name, a, b in self.spans:
             if b is not None:
                 out.setdefault(name, []).append(a.elapsed_time(b))
         return out
@@ -274,15 +275,19 @@ def cross_region_list(support, distance_threshold):
 
 
 # ---- a4 ----------------------------------------------------------------------------------------------------------
+def _check_support(support, H, W, who):
+    have = support.untyped_storage().nbytes() - support.storage_offset() * support.element_size()
+    if tuple(support.shape) != (H, W) or not support.is_contiguous() or have < hip.load().mccnn_support_bytes(H, W):
+        raise ValueError("%s: `support` must be the tensor cross_arms() returned (a copy drops its derived planes)" % who)
+
+
 def cbca(vol, tmp, support, iterations, distance_threshold, order=hip.MCCNN_CBCA_SEPARABLE, timer=None):
     """`iterations` rounds of cross-based averaging.  Ping-pongs between `vol` and `tmp` (same shape);
     returns (result, spare) - the input buffer is clobbered when iterations >= 2, the reference's is not, so
     callers that need the input keep their own copy."""
     D, H, W = vol.shape
     lib = hip.load()
-    have = support.untyped_storage().nbytes() - support.storage_offset() * support.element_size()
-    if tuple(support.shape) != (H, W) or not support.is_contiguous() or have < lib.mccnn_support_bytes(H, W):
-        raise ValueError("cbca: `support` must be the tensor cross_arms() returned (a copy drops its derived planes)")
+    _check_support(support, H, W, "cbca")
     src, dst = vol, tmp
     timer = timer or _NO_TIMER
     for _ in range(int(iterations)):
@@ -303,10 +308,8 @@ def cbca_pair(vol_l, tmp_l, support_l, vol_r, tmp_r, support_r, iterations, dist
     if tuple(vol_r.shape) != (D, H, W):
         raise ValueError("cbca_pair: the two volumes must have the same shape")
     lib = hip.load()
-    for sup in (support_l, support_r):
-        have = sup.untyped_storage().nbytes() - sup.storage_offset() * sup.element_size()
-        if tuple(sup.shape) != (H, W) or not sup.is_contiguous() or have < lib.mccnn_support_bytes(H, W):
-            raise ValueError("cbca_pair: `support` must be the tensor cross_arms() returned")
+    _check_support(support_l, H, W, "cbca_pair")
+    _check_support(support_r, H, W, "cbca_pair")
     (sl, dl), (sr, dr) = (vol_l, tmp_l), (vol_r, tmp_r)
     timer = timer or _NO_TIMER
     for _ in range(int(iterations)):
@@ -317,12 +320,6 @@ def cbca_pair(vol_l, tmp_l, support_l, vol_r, tmp_r, support_r, iterations, dist
         timer.stop()
         sl, dl, sr, dr = dl, sl, dr, sr
     return (sl, dl), (sr, dr)
-
-
-def _check_support(support, H, W, who):
-    have = support.untyped_storage().nbytes() - support.storage_offset() * support.element_size()
-    if tuple(support.shape) != (H, W) or not support.is_contiguous() or have < hip.load().mccnn_support_bytes(H, W):
-        raise ValueError("%s: `support` must be the tensor cross_arms() returned (a copy drops its derived planes)" % who)
 
 
 CBCA_HWD_MAX_DISTANCE = 14     # mccnn_cbca_iter_hwd* and the aggregation programs: arms up to 13
@@ -378,6 +375,12 @@ def cbca_hwd(vol, tmp, support, D, iterations, distance_threshold, timer=None):
     return src, dst
 
 
+def _check_wta_out(wta_out, H, W, who):
+    for t in wta_out:
+        if tuple(t.shape) != (H, W) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("%s: wta_out must be two contiguous float32 [H,W] tensors" % who)
+
+
 def cbca_hwd_wta_max_d():
     """Largest D whose last aggregation iteration can carry the WTA (one chunk of disparities per wave)."""
     return 256
@@ -402,16 +405,15 @@ def cbca_hwd_pair(vol_l, tmp_l, support_l, vol_r, tmp_r, support_r, D, iteration
     timer = timer or _NO_TIMER
     n = int(iterations)
     long_arms = int(distance_threshold) > CBCA_HWD_MAX_DISTANCE
-    if wta_out is not None and (n < 1 or D > cbca_hwd_wta_max_d() or long_arms):
-        raise ValueError("cbca_hwd_pair: the fused WTA needs at least one iteration, D <= %d and a distance <= %d"
-                         % (cbca_hwd_wta_max_d(), CBCA_HWD_MAX_DISTANCE))
+    if wta_out is not None:
+        if n < 1 or D > cbca_hwd_wta_max_d() or long_arms:
+            raise ValueError("cbca_hwd_pair: the fused WTA needs at least one iteration, D <= %d and a distance <= %d"
+                             % (cbca_hwd_wta_max_d(), CBCA_HWD_MAX_DISTANCE))
+        _check_wta_out(wta_out, H, W, "cbca_hwd_pair")
     pair_name = "mccnn_cbca_iter_hwd_long_pair" if long_arms else "mccnn_cbca_iter_hwd_pair"
     for it in range(n):
         timer.start("cbca_iter_hwd_pair")
         if wta_out is not None and it == n - 1:
-            for t in wta_out:
-                if tuple(t.shape) != (H, W) or t.dtype != torch.float32 or not t.is_contiguous():
-                    raise ValueError("cbca_hwd_pair: wta_out must be two contiguous float32 [H,W] tensors")
             hip.check(lib.mccnn_cbca_iter_hwd_pair_wta(hip.ptr(sl), hip.ptr(dl), hip.ptr(support_l), hip.ptr(sr),
                                                        hip.ptr(dr), hip.ptr(support_r), int(D), H, W,
                                                        int(distance_threshold), hip.ptr(wta_out[0]), hip.ptr(wta_out[1]),
@@ -489,10 +491,44 @@ def right_stream(device):
     return _RIGHT_STREAMS[key]
 
 
+# (skip_schedule kind, volumes per launch) -> (entry point, StageTimer name): every launch of the program-driven
+# aggregation kernel goes through this table (_prog_launch).  bench.py reads the timer names.
+_PROG_LAUNCH = {
+    ("full", 1): ("mccnn_cbca_iter_prog", "cbca_iter_prog"),
+    ("refresh", 1): ("mccnn_cbca_iter_prog_refresh", "cbca_iter_prog"),
+    ("skip", 1): ("mccnn_cbca_iter_prog_skip", "cbca_iter_prog_skip"),
+    ("full", 2): ("mccnn_cbca_iter_prog_pair", "cbca_iter_prog_pair"),
+    ("refresh", 2): ("mccnn_cbca_iter_prog_pair_refresh", "cbca_iter_prog_pair"),
+    ("skip", 2): ("mccnn_cbca_iter_prog_pair_skip", "cbca_iter_prog_pair_skip"),
+    ("wta", 2): ("mccnn_cbca_iter_prog_pair_wta", "cbca_iter_prog_pair"),
+}
+
+
+def _prog_launch(kind, volumes, D, distance_threshold, timer, tail=()):
+    """One launch from _PROG_LAUNCH on the current stream.  volumes: one (src, dst, support, prog) per volume of the
+    launch - one, or the left and the right; tail: the arguments an entry point takes behind the distance."""
+    name, timed_as = _PROG_LAUNCH[kind, len(volumes)]
+    H, W, _ = volumes[0][0].shape
+    timer.start(timed_as)
+    hip.check(getattr(hip.load(), name)(*[hip.ptr(t) for volume in volumes for t in volume], int(D), H, W,
+                                        int(distance_threshold), *tail, hip.stream()), name)
+    timer.stop()
+
+
+def _prog_launch_wta(left, right, D, distance_threshold, wta_out, store_right, timer):
+    """The two-volume launch that carries the WTA: an aggregation's last iteration on the full programs, which also
+    writes the disparities of both results to wta_out and, with store_right false, leaves the right result volume
+    unwritten.  left / right: (src, dst, support, prog)."""
+    H, W, _ = left[0].shape
+    _check_wta_out(wta_out, H, W, "cbca_prog_pair")
+    _prog_launch("wta", (left, right), D, distance_threshold, timer,
+                 (hip.ptr(wta_out[0]), hip.ptr(wta_out[1]), 1 if store_right else 0))
+
+
 def skip_schedule(n, fused_last, skip_unit_regions=True, refresh_first=True):
     """Which kernel every iteration of an n-iteration aggregation runs: a list of "full", "refresh" (the full kernel that
-    also writes unit-region pixels back into its input, mccnn_cbca_iter_prog_refresh), "skip" and "wta" (the full kernel
-    fused with a7; fused_last).  cbca_prog_pair's docstring has the argument."""
+    also writes unit-region pixels back into its input), "skip" and "wta" (the full kernel fused with a7; fused_last) -
+    the kinds of _PROG_LAUNCH.  cbca_prog_pair's docstring has the argument."""
     n = int(n)
     kinds = []
     for it in range(n):
@@ -513,36 +549,33 @@ def skip_schedule(n, fused_last, skip_unit_regions=True, refresh_first=True):
 
 
 def cbca_prog_pair(vol_l, tmp_l, support_l, vol_r, tmp_r, support_r, progs, D, iterations, distance_threshold, timer=None,
-                   wta_out=None, store_right=True, skip_unit_regions=True, skip_ready=None, right_stream=None,
-                   refresh_first=True):
-    """cbca_hwd_pair's result (bit for bit) through the program-driven assembly kernel (mccnn_cbca_iter_prog_pair);
-    `progs` from cbca_prog_build_pair on the same support buffers and D.  Same ping-pong contract; wta_out /
-    store_right as in cbca_hwd_pair (mccnn_cbca_iter_prog_pair_wta for the last iteration).
+                   wta_out=None, store_right=True, skip_unit_regions=True, right_stream=None, refresh_first=True):
+    """cbca_hwd_pair's result (bit for bit) through the program-driven assembly kernel (_PROG_LAUNCH); `progs` from
+    cbca_prog_build_pair on the same support buffers and D.  Same ping-pong contract; wta_out / store_right as in
+    cbca_hwd_pair (_prog_launch_wta for the last iteration).
 
-    skip_unit_regions: from the SECOND iteration on, pixels whose support region is the pixel itself are left alone
-    (mccnn_cbca_iter_prog_pair_skip).  Such a pixel gets v1 = (0 + v0) / 1 in the first iteration (pf:156-161 with
-    aver_num = 1), which is v0 except that -0.0 becomes +0.0 and a signalling NaN is quieted, and (0 + v1) / 1 = v1 bit
-    for bit ever after.  The first iteration (full programs) puts v1 into the partner buffer; with refresh_first
-    (default, round 6) and an even number of iterations that would otherwise have to end with a full launch, it is a
-    mccnn_cbca_iter_prog_refresh launch, which also writes v1 back into the input buffer, so that BOTH buffers
-    hold the final value of these pixels and every later iteration may skip them, whichever buffer it writes: as a
-    NEIGHBOUR in somebody else's region v0 and v1 give the same sum bit for bit (a running sum that started as 0 + x is
-    never -0.0, so adding -0.0 or +0.0 cannot differ; a NaN operand gives the same quiet NaN either way), and nothing
-    else reads them - except the caller, from the final buffer.  refresh_first=False is round 5's rule: the input buffer
-    keeps v0, so with an even number of iterations - the result lands in the input buffer - the last iteration runs the
-    full programs and rewrites every pixel.  The iteration that carries the WTA runs the full programs either way.  Same
-    bits everywhere, fewer bytes moved.  NOTE: a refresh launch modifies the INPUT volume (v0 -> v1 at unit-region
-    pixels); skip_schedule issues one only for an even number of iterations without a fused WTA - where the input buffer
-    is also the result buffer, which holds v1 there in the end either way.
-    skip_ready: an event after which the second program set is complete when it was built on another stream (the
-    current stream waits for it in front of the first iteration that needs it).
+    skip_unit_regions: from the SECOND iteration on, pixels whose support region is the pixel itself are left alone (the
+    "skip" launches).  Such a pixel gets v1 = (0 + v0) / 1 in the first iteration (pf:156-161 with aver_num = 1), which
+    is v0 except that -0.0 becomes +0.0 and a signalling NaN is quieted, and (0 + v1) / 1 = v1 bit for bit ever after.
+    The first iteration (full programs) puts v1 into the partner buffer; with refresh_first (default, round 6) and an
+    even number of iterations that would otherwise have to end with a full launch, it is a "refresh" launch, which also
+    writes v1 back into the input buffer, so that BOTH buffers hold the final value of these pixels and every later
+    iteration may skip them, whichever buffer it writes: as a NEIGHBOUR in somebody else's region v0 and v1 give the
+    same sum bit for bit (a running sum that started as 0 + x is never -0.0, so adding -0.0 or +0.0 cannot differ; a
+    NaN operand gives the same quiet NaN either way), and nothing else reads them - except the caller, from the final
+    buffer.  refresh_first=False is round 5's rule: the input buffer keeps v0, so with an even number of iterations -
+    the result lands in the input buffer - the last iteration runs the full programs and rewrites every pixel.  The
+    iteration that carries the WTA runs the full programs either way.  Same bits everywhere, fewer bytes moved.  NOTE:
+    a refresh launch modifies the INPUT volume (v0 -> v1 at unit-region pixels); skip_schedule issues one only for an
+    even number of iterations without a fused WTA - where the input buffer is also the result buffer, which holds v1
+    there in the end either way.
 
-    right_stream: when given, the two volumes run as two independent chains of ONE-volume launches
-    (mccnn_cbca_iter_prog / _skip) - the left chain on the current stream, the right chain on `right_stream`, forked
-    from the current stream here and joined to it before returning (or before the WTA-carrying last launch, which stays
-    one two-volume launch).  The volumes never meet, so nothing orders the chains against each other, and one chain's
-    launch fills the compute units the other's leaves idle while its heaviest patches finish: the same bits, 8.7 % less
-    time for 16 iterations at 750x500x256 (profiles/r05_cbca_two_streams.txt)."""
+    right_stream: when given, the two volumes run as two independent chains of ONE-volume launches (cbca_prog_chain) -
+    the left chain on the current stream, the right chain on `right_stream`, forked from the current stream here and
+    joined to it before returning (or before the WTA-carrying last launch, which stays one two-volume launch).  The
+    volumes never meet, so nothing orders the chains against each other, and one chain's launch fills the compute
+    units the other's leaves idle while its heaviest patches finish: the same bits, 8.7 % less time for 16 iterations
+    at 750x500x256 (profiles/r05_cbca_two_streams.txt)."""
     H, W, Dp = vol_l.shape
     assert Dp == hwd_pitch(D)
     for t in (tmp_l, vol_r, tmp_r):
@@ -550,96 +583,51 @@ def cbca_prog_pair(vol_l, tmp_l, support_l, vol_r, tmp_r, support_r, progs, D, i
             raise ValueError("cbca_prog_pair: the volumes must have the same shape")
     _check_support(support_l, H, W, "cbca_prog_pair")
     _check_support(support_r, H, W, "cbca_prog_pair")
-    lib = hip.load()
-    (sl, dl), (sr, dr) = (vol_l, tmp_l), (vol_r, tmp_r)
     timer = timer or _NO_TIMER
     n = int(iterations)
-    if wta_out is not None and (n < 1 or D > cbca_hwd_wta_max_d()):
+    fused = wta_out is not None
+    if fused and (n < 1 or D > cbca_hwd_wta_max_d()):
         raise ValueError("cbca_prog_pair: the fused WTA needs at least one iteration and D <= %d" % cbca_hwd_wta_max_d())
-    kinds = skip_schedule(n, wta_out is not None, skip_unit_regions and _skip_set_built(progs), refresh_first)
-
-    def skips(it):
-        return kinds[it] == "skip"
-
-    n_chain = 0
+    skipping = skip_unit_regions and _skip_set_built(progs)
+    (sl, dl), (sr, dr) = (vol_l, tmp_l), (vol_r, tmp_r)
+    first = 0
     if right_stream is not None:
         # ---- two chains of one-volume launches (every iteration but a WTA-carrying last one) ----
-        n_chain = n - 1 if wta_out is not None else n
+        first = n - 1 if fused else n
         main = torch.cuda.current_stream()
         right_stream.wait_stream(main)
-        chains = ((main, vol_l, tmp_l, support_l, progs[0]), (right_stream, vol_r, tmp_r, support_r, progs[1]))
         ends = []
-        for st, src, dst, sup, prog in chains:
+        for st, vol, tmp, sup, prog in ((main, vol_l, tmp_l, support_l, progs[0]),
+                                        (right_stream, vol_r, tmp_r, support_r, progs[1])):
             with torch.cuda.stream(st):
-                waited_ = False
-                for it in range(n_chain):
-                    skip = skips(it)
-                    if skip and skip_ready is not None and not waited_:
-                        st.wait_event(skip_ready)
-                        waited_ = True
-                    fn, who = ((lib.mccnn_cbca_iter_prog_skip, "mccnn_cbca_iter_prog_skip") if skip
-                               else (lib.mccnn_cbca_iter_prog_refresh, "mccnn_cbca_iter_prog_refresh") if kinds[it] == "refresh"
-                               else (lib.mccnn_cbca_iter_prog, "mccnn_cbca_iter_prog"))
-                    timer.start("cbca_iter_prog_skip" if skip else "cbca_iter_prog")
-                    hip.check(fn(hip.ptr(src), hip.ptr(dst), hip.ptr(sup), hip.ptr(prog), int(D), H, W,
-                                 int(distance_threshold), hip.stream()), who)
-                    timer.stop()
-                    src, dst = dst, src
-                ends.append((src, dst))
+                ends.append(cbca_prog_chain(vol, tmp, sup, prog, D, first, distance_threshold, total=n, fused_last=fused,
+                                            skip_unit_regions=skipping, timer=timer, refresh_first=refresh_first))
         main.wait_stream(right_stream)
         (sl, dl), (sr, dr) = ends
-    waited = n_chain > 0 and any(skips(it) for it in range(n_chain))
-    for it in range(n_chain, n):
-        fused = wta_out is not None and it == n - 1
-        skip = skips(it)
-        timer.start("cbca_iter_prog_pair_skip" if skip else "cbca_iter_prog_pair")
-        if fused:
-            for t in wta_out:
-                if tuple(t.shape) != (H, W) or t.dtype != torch.float32 or not t.is_contiguous():
-                    raise ValueError("cbca_prog_pair: wta_out must be two contiguous float32 [H,W] tensors")
-            hip.check(lib.mccnn_cbca_iter_prog_pair_wta(hip.ptr(sl), hip.ptr(dl), hip.ptr(support_l), hip.ptr(progs[0]),
-                                                        hip.ptr(sr), hip.ptr(dr), hip.ptr(support_r), hip.ptr(progs[1]),
-                                                        int(D), H, W, int(distance_threshold), hip.ptr(wta_out[0]),
-                                                        hip.ptr(wta_out[1]), 1 if store_right else 0, hip.stream()),
-                      "mccnn_cbca_iter_prog_pair_wta")
+    kinds = skip_schedule(n, fused, skipping, refresh_first)
+    for it in range(first, n):
+        left, right = (sl, dl, support_l, progs[0]), (sr, dr, support_r, progs[1])
+        if kinds[it] == "wta":
+            _prog_launch_wta(left, right, D, distance_threshold, wta_out, store_right, timer)
         else:
-            fn, who = ((lib.mccnn_cbca_iter_prog_pair_skip, "mccnn_cbca_iter_prog_pair_skip") if skip
-                       else (lib.mccnn_cbca_iter_prog_pair_refresh, "mccnn_cbca_iter_prog_pair_refresh")
-                       if kinds[it] == "refresh" else (lib.mccnn_cbca_iter_prog_pair, "mccnn_cbca_iter_prog_pair"))
-            if skip_ready is not None and skip and not waited:
-                torch.cuda.current_stream().wait_event(skip_ready)
-                waited = True
-            hip.check(fn(hip.ptr(sl), hip.ptr(dl), hip.ptr(support_l), hip.ptr(progs[0]), hip.ptr(sr), hip.ptr(dr),
-                         hip.ptr(support_r), hip.ptr(progs[1]), int(D), H, W, int(distance_threshold), hip.stream()), who)
-        timer.stop()
+            _prog_launch(kinds[it], (left, right), D, distance_threshold, timer)
         sl, dl, sr, dr = dl, sl, dr, sr
     return (sl, dl), (sr, dr)
 
 
 def cbca_prog_chain(vol, tmp, support, prog, D, iterations, distance_threshold, first=0, total=None, fused_last=False,
-                    skip_unit_regions=True, skip_ready=None, timer=None, refresh_first=True):
-    """Iterations first .. iterations-1 of ONE volume's aggregation on the current stream (mccnn_cbca_iter_prog /
-    _skip; cbca_prog_pair's rule for which iterations leave the unit-region pixels alone, with `total` = the length of
-    the whole aggregation and fused_last = its last iteration carries the WTA and is not part of the chain)."""
-    H, W, Dp = vol.shape
-    lib = hip.load()
+                    skip_unit_regions=True, timer=None, refresh_first=True):
+    """Iterations first .. iterations-1 of ONE volume's aggregation on the current stream (the one-volume entries of
+    _PROG_LAUNCH; cbca_prog_pair's rule for which iterations leave the unit-region pixels alone, with `total` = the
+    length of the whole aggregation and fused_last = its last iteration carries the WTA and is not part of the chain).
+    The only loop over one-volume launches."""
     n = int(total if total is not None else iterations)
     kinds = skip_schedule(n, fused_last, skip_unit_regions and _skip_set_built((prog,)), refresh_first)
     src, dst = vol, tmp
-    waited = False
     timer = timer or _NO_TIMER
     for it in range(int(first), int(iterations)):
-        skip = kinds[it] == "skip"
-        if skip and skip_ready is not None and not waited:
-            torch.cuda.current_stream().wait_event(skip_ready)
-            waited = True
-        fn, who = ((lib.mccnn_cbca_iter_prog_skip, "mccnn_cbca_iter_prog_skip") if skip
-                   else (lib.mccnn_cbca_iter_prog_refresh, "mccnn_cbca_iter_prog_refresh") if kinds[it] == "refresh"
-                   else (lib.mccnn_cbca_iter_prog, "mccnn_cbca_iter_prog"))
-        timer.start("cbca_iter_prog_skip" if skip else "cbca_iter_prog")
-        hip.check(fn(hip.ptr(src), hip.ptr(dst), hip.ptr(support), hip.ptr(prog), int(D), H, W, int(distance_threshold),
-                     hip.stream()), who)
-        timer.stop()
+        # (a chain asked to run the WTA iteration all the same runs it as what it is without the WTA: a full launch)
+        _prog_launch("full" if kinds[it] == "wta" else kinds[it], ((src, dst, support, prog),), D, distance_threshold, timer)
         src, dst = dst, src
     return src, dst
 
@@ -687,12 +675,24 @@ def sgm_scratch(H, W, D, device):
     return torch.empty((n,), dtype=torch.uint8, device=device)
 
 
+def _sgm_arrays(sides, *volume_lists):
+    """What the SGM entry points take for their 1 or 2 volumes: (n, the c_int[2] of sides, one c_void_p[2] per volume
+    list), the unused second slots zero."""
+    n = len(volume_lists[0])
+    return (n, (ctypes.c_int * 2)(*(list(sides) + [0] * (2 - n)))) + tuple(
+        (ctypes.c_void_p * 2)(*([v.data_ptr() for v in vols] + [None] * (2 - n))) for vols in volume_lists)
+
+
+def _sgm_penalties(sgm_P1, sgm_P2, sgm_Q1, sgm_Q2, sgm_D, sgm_V):
+    """The float32 scalars of the SGM passes: (P1 along a row, P1 along a column = P1 / V in Python double division
+    rounded once (pf:204), P2, Q1, Q2, the intensity threshold D)."""
+    return _f32(sgm_P1), _f32(sgm_P1 / sgm_V), _f32(sgm_P2), _f32(sgm_Q1), _f32(sgm_Q2), _f32(sgm_D)
+
+
 def sgm_pass_hwd(image_left, image_right, vols_hwd, sides, D, r, p1, p2, q1, q2, thr, scratch):
     """One direction, in place on 1 or 2 HWD volumes.  p1..thr are already float32-rounded Python floats."""
     H, W = image_left.shape
-    n = len(vols_hwd)
-    vol_arr = (ctypes.c_void_p * 2)(*([v.data_ptr() for v in vols_hwd] + [None] * (2 - n)))
-    side_arr = (ctypes.c_int * 2)(*(list(sides) + [0] * (2 - n)))
+    n, side_arr, vol_arr = _sgm_arrays(sides, vols_hwd)
     hip.check(hip.load().mccnn_sgm_pass(hip.ptr(image_left), hip.ptr(image_right), vol_arr, side_arr, n, int(D), H, W,
                                         int(r[0]), int(r[1]), p1, p2, q1, q2, thr, hip.ptr(scratch),
                                         scratch.numel(), hip.stream()), "mccnn_sgm_pass")
@@ -717,9 +717,7 @@ def sgm_flag_planes(image_left, image_right, D, sgm_D, out=None):
 def sgm_pass_flagged_hwd(vols_hwd, sides, D, r, p1, p2, q1, q2, flags):
     """One direction, in place on 1 or 2 HWD volumes, with the direction's flag planes already built (sgm_flag_planes)."""
     H, W, _ = vols_hwd[0].shape
-    n = len(vols_hwd)
-    vol_arr = (ctypes.c_void_p * 2)(*([v.data_ptr() for v in vols_hwd] + [None] * (2 - n)))
-    side_arr = (ctypes.c_int * 2)(*(list(sides) + [0] * (2 - n)))
+    n, side_arr, vol_arr = _sgm_arrays(sides, vols_hwd)
     hip.check(hip.load().mccnn_sgm_pass_flagged(vol_arr, side_arr, n, int(D), H, W, int(r[0]), int(r[1]), p1, p2, q1, q2,
                                                 hip.ptr(flags), flags.numel(), hip.stream()), "mccnn_sgm_pass_flagged")
 
@@ -731,9 +729,7 @@ def sgm_average_hwd(image_left, image_right, vols_hwd, sides, D, sgm_P1, sgm_P2,
     (the CPU checker used by the tests evaluates it literally; the parity tests pin the equality).
     flags: sgm_flag_planes() of the same images, D and sgm_D - the passes then launch no flag kernels of their own
     (`scratch` is not used)."""
-    p1h = _f32(sgm_P1)
-    p1v = _f32(sgm_P1 / sgm_V)  # Python double division, rounded once (pf:204)
-    p2, q1, q2, thr = _f32(sgm_P2), _f32(sgm_Q1), _f32(sgm_Q2), _f32(sgm_D)
+    p1h, p1v, p2, q1, q2, thr = _sgm_penalties(sgm_P1, sgm_P2, sgm_Q1, sgm_Q2, sgm_D, sgm_V)
     for i, r in enumerate(SGM_DIRECTIONS):
         # (a launch that advances ONE volume - the free-running chains of StereoMatcher - is priced apart from the
         # two-volume launch: half the bytes, and it runs beside whatever the other volume's chain is doing)
@@ -755,15 +751,10 @@ def sgm_average_from_dhw(image_left, image_right, vols_dhw, vols_hwd, sides, D, 
     pixel-major `vols_hwd` (mccnn_sgm_first_pass: layout change fused into the pass), the other three run in place on
     `vols_hwd`.  For D > 256 the layout change is a separate launch."""
     H, W = image_left.shape
-    p1h = _f32(sgm_P1)
-    p1v = _f32(sgm_P1 / sgm_V)
-    p2, q1, q2, thr = _f32(sgm_P2), _f32(sgm_Q1), _f32(sgm_Q2), _f32(sgm_D)
-    n = len(vols_dhw)
+    p1h, p1v, p2, q1, q2, thr = _sgm_penalties(sgm_P1, sgm_P2, sgm_Q1, sgm_Q2, sgm_D, sgm_V)
     rest = SGM_DIRECTIONS
     if D <= SGM_FIRST_PASS_MAX_D:
-        src = (ctypes.c_void_p * 2)(*([v.data_ptr() for v in vols_dhw] + [None] * (2 - n)))
-        dst = (ctypes.c_void_p * 2)(*([v.data_ptr() for v in vols_hwd] + [None] * (2 - n)))
-        side_arr = (ctypes.c_int * 2)(*(list(sides) + [0] * (2 - n)))
+        n, side_arr, src, dst = _sgm_arrays(sides, vols_dhw, vols_hwd)
         timer.start("sgm_first_pass")
         hip.check(hip.load().mccnn_sgm_first_pass(hip.ptr(image_left), hip.ptr(image_right), src, dst, side_arr, n,
                                                   int(D), H, W, p1h, p2, q1, q2, thr, hip.ptr(scratch),
@@ -955,8 +946,8 @@ class StereoMatcher(object):
 
     def __init__(self, net, hp=None, cv_mode=hip.MCCNN_CV_EXACT, cbca_order=hip.MCCNN_CBCA_REFERENCE_ORDER,
                  feature_tile_rows=None, extras=None, features="auto", layout="auto", cbca_kernel="auto",
-                 on_saturation="fallback", skip_unit_regions=True, two_chains=True, one_launch_builder=True,
-                 side_early=False, free_chains=True, refresh_first=True, sgm_flags_once=True):
+                 on_saturation="fallback", skip_unit_regions=True, two_chains=True, free_chains=True, refresh_first=True,
+                 sgm_flags_once=True):
         self.device = hip.require_device()
         self.net = net
         self.hp = dict(DEFAULT_HP)
@@ -982,7 +973,7 @@ class StereoMatcher(object):
             raise ValueError("layout must be 'auto' or 'plane_major'")
         self.layout = layout
         # reference-order aggregation on pixel-major volumes: "prog" = the program-driven assembly kernel
-        # (mccnn_cbca_iter_prog_pair), "hwd" = cbca_hwd_kernel; "auto": the first wherever its programs encode the shape
+        # (cbca_prog_pair), "hwd" = cbca_hwd_kernel; "auto": the first wherever its programs encode the shape
         if cbca_kernel not in ("auto", "prog", "hwd"):
             raise ValueError("cbca_kernel must be 'auto', 'prog' or 'hwd'")
         self.cbca_kernel = cbca_kernel
@@ -996,15 +987,10 @@ class StereoMatcher(object):
         # the program-driven aggregation as two chains of one-volume launches on two streams (cbca_prog_pair,
         # right_stream): same bits; False = one two-volume launch per iteration
         self.two_chains = bool(two_chains)
-        # both program sets from one launch beside the cost volume (mccnn_cbca_prog_build_both_pair); False = round 4's
-        # two launches, the skip programs beside the first aggregation (A/B measurements)
-        self.one_launch_builder = bool(one_launch_builder)
-        # options measured with tools/dev_ab_matchers.py (profiles/r05_ab_matcher_options.txt): side_early - the side
-        # stream's work beside the conv stack instead of beside the cost volume (+0.04 ms: worse); free_chains (default
-        # since round 6) - each volume's aggregation -> SGM -> aggregation as ONE free-running chain of one-volume
-        # launches on its own stream, no join between the stages (-0.10 .. -0.16 ms per cfg2 pair, same bits); False =
-        # round 5's schedule: the chains join after every stage and the SGM passes are two-volume launches
-        self.side_early = bool(side_early)
+        # free_chains (default since round 6; measured with tools/dev_ab_matchers.py, profiles/r05_ab_matcher_options.txt):
+        # each volume's aggregation -> SGM -> aggregation as ONE free-running chain of one-volume launches on its own
+        # stream, no join between the stages (-0.10 .. -0.16 ms per cfg2 pair, same bits); False = round 5's schedule: the
+        # chains join after every stage and the SGM passes are two-volume launches
         self.free_chains = bool(free_chains)
         # skip_schedule's rule (round 6): an aggregation with an even number of iterations whose last launch carries no WTA
         # (match.py's first: 2 iterations) starts with a refresh launch and then skips to the end; False = round 5's rule
@@ -1113,250 +1099,194 @@ class StereoMatcher(object):
                 return redo
         return res
 
-    def _match(self, left_image, right_image, ndisp, timer=_NO_TIMER, keep=None, _static_out=False, out=None):
-        """left/right: standardised float32 device tensors [H,W] (or [H,W,1]).  Returns the final left disparity
-        map [H,W] on the device.  The matcher's workspace is reused by the next call, so the map is handed out as a
-        copy - one [H,W] allocation + one copy per pair; pass `out` (a contiguous float32 [H,W] device tensor) and the
-        last kernel writes there instead: nothing is allocated but the conv activations.  `keep`, if a dict, receives
-        intermediate device tensors in the reference's [D,H,W] layout (tests)."""
+    # ---- one pair, stage by stage (_match below is the schedule; INTEGRATION.md has the map) ----
+    def _side_work(self, ws, L, R, D, want_flags):
+        """What depends on the images only, on the matcher's side stream (forked from the current one): the support arms,
+        the aggregation programs where the workspace has buffers for them - both sets from one pass over the support
+        words - and, when wanted, the SGM flag planes.  Returns (sup_l, sup_r, flag_planes or None, the event after which
+        all of it is complete)."""
         hp = self.hp
-        L = left_image.reshape(left_image.shape[0], left_image.shape[1]).contiguous()
-        R = right_image.reshape(right_image.shape[0], right_image.shape[1]).contiguous()
-        H, W = L.shape
-        D = int(ndisp)
-        ws = self.workspace(H, W, D)
-        dhw = (D, H, W)
-        hwd = (H, W, hwd_pitch(D))
-        nd, nh = D * H * W, H * W * hwd[2]
-        as_dhw = lambda buf: buf[:nd].view(dhw)       # noqa: E731
-        as_hwd = lambda buf: buf[:nh].view(hwd)       # noqa: E731
-        b0, b1, b2, b3 = ws["vol"]
-        sides = [hip.MCCNN_SIDE_LEFT, hip.MCCNN_SIDE_RIGHT]
+        if self._side is None:
+            self._side = torch.cuda.Stream()
+        self._side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self._side):
+            sup_l, sup_r = cross_arms_pair(L, R, hp["cbca_intensity"], hp["cbca_distance"], ws["sup_l"], ws["sup_r"])
+            if ws["progs"] is not None:
+                cbca_prog_build_pair(sup_l, sup_r, D, hp["cbca_distance"], ws["progs"],
+                                     "both" if self.skip_unit_regions else "full")
+            flag_planes = sgm_flag_planes(L, R, D, hp["sgm_D"], out=ws["sgm_flags"]) if want_flags else None
+            ready = torch.cuda.Event()
+            ready.record(self._side)
+        return sup_l, sup_r, flag_planes, ready
 
-        # The support arms and the aggregation programs depend on the images only: without per-stage timing they run
-        # on a side stream beside the cost volume - the arms and, since round 5, both program sets in one launch (round
-        # 4 built the skip programs in a launch of their own beside the first aggregation and SGM).  Round-4
-        # measurements at cfg2 (one box, 100 pairs each, twice): everything on the main stream 9.22 / 9.22 ms,
-        # everything beside the conv stack 9.19 / 9.12 (the builder's waves slow the matrix-core kernels down by what
-        # they save), beside the cost volume 9.14 / 9.06.
-        overlap = timer is _NO_TIMER
-        skip_ready = full_ready = sup_l = sup_r = flag_planes = None
-        want_flags = (self.sgm_flags_once and self.free_chains and keep is None and ws["progs"] is not None
-                      and self.two_chains and self.pixel_major())
-
-        def side_work(stage):
-            """stage 0: support arms + both program sets (or, one_launch_builder=False, the full programs; stage 1: the
-            skip programs)."""
-            nonlocal skip_ready, full_ready, sup_l, sup_r, flag_planes
-            if self._side is None:
-                self._side = torch.cuda.Stream()
-            self._side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self._side):
-                if stage == 0:
-                    sup_l, sup_r = cross_arms_pair(L, R, hp["cbca_intensity"], hp["cbca_distance"], ws["sup_l"], ws["sup_r"])
-                    if ws["progs"] is not None:
-                        # both program sets from one pass over the support words (round 5: one launch of about the
-                        # time either of the two earlier launches took)
-                        cbca_prog_build_pair(sup_l, sup_r, D, hp["cbca_distance"], ws["progs"],
-                                             "both" if (self.skip_unit_regions and self.one_launch_builder) else "full")
-                    if want_flags:
-                        flag_planes = sgm_flag_planes(L, R, D, hp["sgm_D"], out=ws["sgm_flags"])
-                    full_ready = torch.cuda.Event()
-                    full_ready.record(self._side)
-                elif ws["progs"] is not None and self.skip_unit_regions and not self.one_launch_builder:
-                    cbca_prog_build_pair(sup_l, sup_r, D, hp["cbca_distance"], ws["progs"], "skip")
-                    skip_ready = torch.cuda.Event()
-                    skip_ready.record(self._side)
-
-        if overlap and self.side_early:
-            side_work(0)
-        timer.start("features")
-        if self.features == "split_f16":
-            fl, fr = self.net.features_pair_hwc_split(L, R)
-        else:
-            fl, fr = self.net.features_pair_hwc(L, R, tile_rows=self.feature_tile_rows)
+    def _side_work_timed(self, ws, L, R, D, timer):
+        """The arms and the programs of _side_work on the current stream, each under its own timer entry (per-stage
+        timing: nothing runs beside anything).  Returns (sup_l, sup_r)."""
+        hp = self.hp
+        timer.start("cross_arms")
+        sup_l, sup_r = cross_arms_pair(L, R, hp["cbca_intensity"], hp["cbca_distance"], ws["sup_l"], ws["sup_r"])
         timer.stop()
-        if overlap and not self.side_early:
-            side_work(0)
+        if ws["progs"] is not None:
+            timer.start("cbca_prog_build")
+            cbca_prog_build_pair(sup_l, sup_r, D, hp["cbca_distance"], ws["progs"])
+            timer.stop()
+        return sup_l, sup_r
 
-        # the bit-exact variant writes its cost volume pixel-major right away (nothing converts layouts after that)
+    def _cost_volumes(self, fl, fr, D, dhw, hwd, timer):
+        """Returns (left, right, pixel_major): the bit-exact variant writes its cost volume pixel-major right away
+        (nothing converts layouts after that) where the kernel serves D; everything else starts plane-major."""
         direct = self.pixel_major() and D <= COST_VOLUME_HWD_MAX_D
         timer.start("cost_volume")
         if direct:
-            lh, rh = cost_volume_hwd(fl, fr, D, out=(as_hwd(b2), as_hwd(b3)), mode=self.cv_mode)
+            left, right = cost_volume_hwd(fl, fr, D, out=(hwd[2], hwd[3]), mode=self.cv_mode)
         else:
-            lcv, rcv = cost_volume(fl, fr, D, self.cv_mode, out=(as_dhw(b0), as_dhw(b1)))
+            left, right = cost_volume(fl, fr, D, self.cv_mode, out=(dhw[0], dhw[1]))
         timer.stop()
-        del fl, fr
-        if keep is not None:
-            keep["cv"] = (hwd_to_dhw(lh, D), hwd_to_dhw(rh, D)) if direct else (lcv.clone(), rcv.clone())
+        return left, right, direct
 
-        if overlap:
-            torch.cuda.current_stream().wait_event(full_ready)
-            if ws["progs"] is not None and not self.one_launch_builder:
-                side_work(1)
-        else:
-            timer.start("cross_arms")
-            sup_l, sup_r = cross_arms_pair(L, R, hp["cbca_intensity"], hp["cbca_distance"], ws["sup_l"], ws["sup_r"])
+    def _sgm_hp(self):
+        return [self.hp[k] for k in ("sgm_P1", "sgm_P2", "sgm_Q1", "sgm_Q2", "sgm_D", "sgm_V")]
+
+    def _wta_hwd(self, lh, rh, D, m, timer):
+        timer.start("wta")
+        dl, dr = wta_hwd(lh, D, out=m[0]), wta_hwd(rh, D, out=m[1])
+        timer.stop()
+        return dl, dr
+
+    def _pixel_major_free(self, ws, L, R, D, left, right, sups, flag_planes, fuse, m, timer):
+        """Pixel-major volumes, free-running chains (default): each volume's aggregation -> SGM -> aggregation is ONE
+        chain of one-volume launches on its own stream - the left on the current stream, the right on the matcher's right
+        stream; the two chains meet again only in front of the WTA-carrying last launch.  left / right: (volume, spare
+        buffer); returns (dl, dr, left_volume)."""
+        hp, progs, dist = self.hp, ws["progs"], self.hp["cbca_distance"]
+        n1, n2 = int(hp["cbca_num_iterations1"]), int(hp["cbca_num_iterations2"])
+        if flag_planes is None and self.sgm_flags_once:      # (per-stage timing: nothing ran beside the cost volume)
+            timer.start("sgm_flags")
+            flag_planes = sgm_flag_planes(L, R, D, hp["sgm_D"], out=ws["sgm_flags"])
             timer.stop()
-            if ws["progs"] is not None:
-                timer.start("cbca_prog_build")
-                cbca_prog_build_pair(sup_l, sup_r, D, hp["cbca_distance"], ws["progs"])
-                timer.stop()
-
-        ex = self.extras
-        m = ws["maps"] if keep is None else torch.empty_like(ws["maps"])
-        if self.pixel_major():
-            # ---- bit-exact variant: pixel-major from here on ----
-            if not direct:
-                timer.start("cv_to_pixel_major")
-                lh, rh = dhw_to_hwd(lcv, as_hwd(b2)), dhw_to_hwd(rcv, as_hwd(b3))
-                timer.stop()
-            progs = ws["progs"]
-
-            def aggregate_hwd(lh, lt, rh, rt, n, **kw):
-                # the program-driven assembly kernel where its programs exist, cbca_hwd_kernel or - distances above
-                # CBCA_HWD_MAX_DISTANCE - cbca_hwd_long_kernel otherwise (same bits)
-                if progs is None:
-                    return cbca_hwd_pair(lh, lt, sup_l, rh, rt, sup_r, D, int(n), hp["cbca_distance"], timer, **kw)
-                return cbca_prog_pair(lh, lt, sup_l, rh, rt, sup_r, progs, D, int(n), hp["cbca_distance"], timer,
-                                      skip_ready=skip_ready if overlap else None,
-                                      skip_unit_regions=self.skip_unit_regions, refresh_first=self.refresh_first,
-                                      right_stream=self._right_stream() if self.two_chains else None, **kw)
-
-            # free-running chains (default): each volume's aggregation -> SGM -> aggregation is ONE chain of one-volume
-            # launches on its own stream; the two chains meet again only in front of the WTA-carrying last launch.  (With
-            # `keep` the stages are joined, so that both volumes of a stage can be handed out.)
-            free = (self.free_chains and keep is None and progs is not None and self.two_chains)
-            if free:
-                n1, n2 = int(hp["cbca_num_iterations1"]), int(hp["cbca_num_iterations2"])
-                fuse = n2 >= 1 and D <= cbca_hwd_wta_max_d()
-                if flag_planes is None and self.sgm_flags_once:      # (per-stage timing: nothing ran beside the cost volume)
-                    timer.start("sgm_flags")
-                    flag_planes = sgm_flag_planes(L, R, D, hp["sgm_D"], out=ws["sgm_flags"])
-                    timer.stop()
-                if flag_planes is None and "scratch2" not in ws:
-                    ws["scratch2"] = sgm_scratch(H, W, D, self.device)
-                main_s, right_s = torch.cuda.current_stream(), self._right_stream()
-                right_s.wait_stream(main_s)
-                ends = []
-                for st, v, t, sup, prog, side, scr in ((main_s, lh, as_hwd(b0), sup_l, progs[0], sides[0], ws["scratch"]),
-                                                       (right_s, rh, as_hwd(b1), sup_r, progs[1], sides[1], ws.get("scratch2"))):
-                    with torch.cuda.stream(st):
-                        # (the brackets are recorded on the chain's own stream: a stage's span beside the other chain)
-                        timer.span_start("aggregation_1")
-                        v, t = cbca_prog_chain(v, t, sup, prog, D, n1, hp["cbca_distance"],
-                                               skip_unit_regions=self.skip_unit_regions, refresh_first=self.refresh_first,
-                                               skip_ready=skip_ready if overlap else None, timer=timer)
-                        timer.span_stop("aggregation_1")
-                        timer.span_start("sgm")
-                        # (the flag planes of the four directions were built once, on the side stream beside the cost
-                        # volume: both chains read them and launch no flag kernels of their own - 8 launches of 11 us
-                        # off the two critical chains)
-                        sgm_average_hwd(L, R, [v], [side], D, hp["sgm_P1"], hp["sgm_P2"], hp["sgm_Q1"], hp["sgm_Q2"],
-                                        hp["sgm_D"], hp["sgm_V"], scr, timer, flags=flag_planes)
-                        timer.span_stop("sgm")
-                        timer.span_start("aggregation_2")
-                        v, t = cbca_prog_chain(v, t, sup, prog, D, n2 - 1 if fuse else n2, hp["cbca_distance"], total=n2,
-                                               fused_last=fuse, skip_unit_regions=self.skip_unit_regions,
-                                               refresh_first=self.refresh_first,
-                                               skip_ready=skip_ready if overlap else None, timer=timer)
-                        timer.span_stop("aggregation_2")
-                        ends.append((v, t))
-                main_s.wait_stream(right_s)
-                (lh, lt), (rh, rt) = ends
-                if fuse:
-                    timer.start("cbca_iter_prog_pair")
-                    hip.check(hip.load().mccnn_cbca_iter_prog_pair_wta(
-                        hip.ptr(lh), hip.ptr(lt), hip.ptr(sup_l), hip.ptr(progs[0]), hip.ptr(rh), hip.ptr(rt), hip.ptr(sup_r),
-                        hip.ptr(progs[1]), int(D), H, W, int(hp["cbca_distance"]), hip.ptr(m[0]), hip.ptr(m[1]), 0,
-                        hip.stream()), "mccnn_cbca_iter_prog_pair_wta")
-                    timer.stop()
-                    lh, lt, rh, rt = lt, lh, rt, rh
-            if not free:
+        if flag_planes is None and "scratch2" not in ws:
+            ws["scratch2"] = sgm_scratch(L.shape[0], L.shape[1], D, self.device)
+        chain = dict(skip_unit_regions=self.skip_unit_regions, refresh_first=self.refresh_first, timer=timer)
+        main_s, right_s = torch.cuda.current_stream(), self._right_stream()
+        right_s.wait_stream(main_s)
+        ends = []
+        for st, (v, t), sup, prog, side, scr in ((main_s, left, sups[0], progs[0], hip.MCCNN_SIDE_LEFT, ws["scratch"]),
+                                                 (right_s, right, sups[1], progs[1], hip.MCCNN_SIDE_RIGHT, ws.get("scratch2"))):
+            with torch.cuda.stream(st):
+                # (the brackets are recorded on the chain's own stream: a stage's span beside the other chain)
                 timer.span_start("aggregation_1")
-                (lh, lt), (rh, rt) = aggregate_hwd(lh, as_hwd(b0), rh, as_hwd(b1), hp["cbca_num_iterations1"])
+                v, t = cbca_prog_chain(v, t, sup, prog, D, n1, dist, **chain)
                 timer.span_stop("aggregation_1")
-            if keep is not None:
-                keep["cbca1"] = (hwd_to_dhw(lh, D), hwd_to_dhw(rh, D))
-            if not free:
                 timer.span_start("sgm")
-                sgm_average_hwd(L, R, [lh, rh], sides, D, hp["sgm_P1"], hp["sgm_P2"], hp["sgm_Q1"], hp["sgm_Q2"],
-                                hp["sgm_D"], hp["sgm_V"], ws["scratch"], timer)
+                # (the flag planes of the four directions were built once, on the side stream beside the cost volume:
+                # both chains read them and launch no flag kernels of their own - 8 launches of 11 us off the two
+                # critical chains)
+                sgm_average_hwd(L, R, [v], [side], D, *self._sgm_hp(), scr, timer, flags=flag_planes)
                 timer.span_stop("sgm")
-            if keep is not None:
-                keep["sgm"] = (hwd_to_dhw(lh, D), hwd_to_dhw(rh, D))
-            # the last iteration carries the WTA of both results (and leaves the right volume, which nothing else
-            # reads, unwritten) when a wave holds all disparities of a pixel
-            fuse = (int(hp["cbca_num_iterations2"]) >= 1 and D <= cbca_hwd_wta_max_d()
-                    and int(hp["cbca_distance"]) <= CBCA_HWD_MAX_DISTANCE)
-            if not free:
                 timer.span_start("aggregation_2")
-                (lh, lt), (rh, rt) = aggregate_hwd(lh, lt, rh, rt, hp["cbca_num_iterations2"],
-                                                   wta_out=(m[0], m[1]) if fuse else None, store_right=keep is not None)
+                v, t = cbca_prog_chain(v, t, sup, prog, D, n2 - 1 if fuse else n2, dist, total=n2, fused_last=fuse, **chain)
                 timer.span_stop("aggregation_2")
-            if overlap and skip_ready is not None:
-                torch.cuda.current_stream().wait_event(skip_ready)      # joins the side stream whatever the iteration count
-            if keep is not None:
-                keep["cbca2"] = (hwd_to_dhw(lh, D), hwd_to_dhw(rh, D))
-            if fuse:
-                dl, dr = m[0], m[1]
-            else:
-                timer.start("wta")
-                dl = wta_hwd(lh, D, out=m[0])
-                dr = wta_hwd(rh, D, out=m[1])
-                timer.stop()
-            sub = lambda di: subpixel_hwd(di, lh, D, out=m[3], numpy1_promotion=ex["numpy1_promotion"])   # noqa: E731
-        else:
-            def aggregate(vol, tmp, own, other, n, side):
-                if ex["both_view_support"]:
-                    return cbca_both_views(vol, tmp, own, other, n, hp["cbca_distance"], side, timer)
-                return cbca(vol, tmp, own, n, hp["cbca_distance"], self.cbca_order, timer)
+                ends.append((v, t))
+        main_s.wait_stream(right_s)
+        (lh, lt), (rh, rt) = ends
+        if not fuse:
+            return self._wta_hwd(lh, rh, D, m, timer) + (lh,)
+        # (the right result volume, which nothing else reads, stays unwritten)
+        _prog_launch_wta((lh, lt, sups[0], progs[0]), (rh, rt, sups[1], progs[1]), D, dist, (m[0], m[1]), False, timer)
+        return m[0], m[1], lt
 
-            def aggregate_both(lcv, t1d, rcv, t2d, n):
-                # the separable kernel takes both views in one launch; the other variants run view by view
-                if not ex["both_view_support"] and self.cbca_order == hip.MCCNN_CBCA_SEPARABLE:
-                    return cbca_pair(lcv, t1d, sup_l, rcv, t2d, sup_r, n, hp["cbca_distance"], self.cbca_order, timer)
-                return (aggregate(lcv, t1d, sup_l, sup_r, n, hip.MCCNN_SIDE_LEFT),
-                        aggregate(rcv, t2d, sup_r, sup_l, n, hip.MCCNN_SIDE_RIGHT))
+    def _aggregate_hwd(self, progs, left, right, sups, D, n, timer, **kw):
+        """One aggregation of both pixel-major volumes, joined to the current stream when it returns: the program-driven
+        assembly kernel where its programs exist, cbca_hwd_kernel or - distances above CBCA_HWD_MAX_DISTANCE -
+        cbca_hwd_long_kernel otherwise (same bits).  kw: wta_out / store_right."""
+        (lh, lt), (rh, rt) = left, right
+        if progs is None:
+            return cbca_hwd_pair(lh, lt, sups[0], rh, rt, sups[1], D, int(n), self.hp["cbca_distance"], timer, **kw)
+        return cbca_prog_pair(lh, lt, sups[0], rh, rt, sups[1], progs, D, int(n), self.hp["cbca_distance"], timer,
+                              skip_unit_regions=self.skip_unit_regions, refresh_first=self.refresh_first,
+                              right_stream=self._right_stream() if self.two_chains else None, **kw)
 
-            (lcv, t1d), (rcv, t2d) = aggregate_both(lcv, as_dhw(b2), rcv, as_dhw(b3), hp["cbca_num_iterations1"])
-            if keep is not None:
-                keep["cbca1"] = (lcv.clone(), rcv.clone())
+    def _pixel_major_joined(self, ws, L, R, D, left, right, sups, fuse, m, timer, keep):
+        """Pixel-major volumes, one stage after the other on the current stream (an aggregation may fork into two chains
+        inside, cbca_prog_pair): free_chains / two_chains off, shapes or distances without aggregation programs, and
+        `keep`, which is handed both volumes of every stage here.  Same arguments and result as _pixel_major_free."""
+        hp, progs = self.hp, ws["progs"]
+        sides = [hip.MCCNN_SIDE_LEFT, hip.MCCNN_SIDE_RIGHT]
+        timer.span_start("aggregation_1")
+        (lh, lt), (rh, rt) = self._aggregate_hwd(progs, left, right, sups, D, hp["cbca_num_iterations1"], timer)
+        timer.span_stop("aggregation_1")
+        if keep is not None:
+            keep["cbca1"] = (hwd_to_dhw(lh, D), hwd_to_dhw(rh, D))
+        timer.span_start("sgm")
+        sgm_average_hwd(L, R, [lh, rh], sides, D, *self._sgm_hp(), ws["scratch"], timer)
+        timer.span_stop("sgm")
+        if keep is not None:
+            keep["sgm"] = (hwd_to_dhw(lh, D), hwd_to_dhw(rh, D))
+        # (with the WTA in the last launch the right result volume, which nothing else reads, stays unwritten)
+        timer.span_start("aggregation_2")
+        (lh, lt), (rh, rt) = self._aggregate_hwd(progs, (lh, lt), (rh, rt), sups, D, hp["cbca_num_iterations2"], timer,
+                                                 wta_out=(m[0], m[1]) if fuse else None, store_right=keep is not None)
+        timer.span_stop("aggregation_2")
+        if keep is not None:
+            keep["cbca2"] = (hwd_to_dhw(lh, D), hwd_to_dhw(rh, D))
+        return ((m[0], m[1]) if fuse else self._wta_hwd(lh, rh, D, m, timer)) + (lh,)
 
-            # SGM on pixel-major copies in the spare ping-pong buffers (every buffer holds either layout)
-            lh, rh = t1d.reshape(-1), t2d.reshape(-1)
-            lh = next(as_hwd(b) for b in ws["vol"] if b.data_ptr() == lh.data_ptr())
-            rh = next(as_hwd(b) for b in ws["vol"] if b.data_ptr() == rh.data_ptr())
-            sgm_average_from_dhw(L, R, [lcv, rcv], [lh, rh], sides, D, hp["sgm_P1"], hp["sgm_P2"], hp["sgm_Q1"],
-                                 hp["sgm_Q2"], hp["sgm_D"], hp["sgm_V"], ws["scratch"], timer)
-            timer.start("hwd_to_dhw")
-            hwd_to_dhw(lh, D, lcv)
-            hwd_to_dhw(rh, D, rcv)
-            timer.stop()
-            if keep is not None:
-                keep["sgm"] = (lcv.clone(), rcv.clone())
+    def _aggregate_dhw(self, left, right, sups, n, timer):
+        """One aggregation of both plane-major volumes: the separable kernel takes both views in one launch; the other
+        variants (reference order, two-view regions) run view by view."""
+        dist, both = self.hp["cbca_distance"], self.extras["both_view_support"]
+        if not both and self.cbca_order == hip.MCCNN_CBCA_SEPARABLE:
+            return cbca_pair(left[0], left[1], sups[0], right[0], right[1], sups[1], n, dist, self.cbca_order, timer)
+        res = []
+        for (vol, tmp), own, other, side in ((left, sups[0], sups[1], hip.MCCNN_SIDE_LEFT),
+                                             (right, sups[1], sups[0], hip.MCCNN_SIDE_RIGHT)):
+            res.append(cbca_both_views(vol, tmp, own, other, n, dist, side, timer) if both
+                       else cbca(vol, tmp, own, n, dist, self.cbca_order, timer))
+        return res
 
-            (lcv, t1d), (rcv, t2d) = aggregate_both(lcv, t1d, rcv, t2d, hp["cbca_num_iterations2"])
-            if keep is not None:
-                keep["cbca2"] = (lcv.clone(), rcv.clone())
-            timer.start("wta")
-            dl = wta(lcv, out=m[0])
-            dr = wta(rcv, out=m[1])
-            timer.stop()
-            sub = lambda di: subpixel(di, lcv, out=m[3], numpy1_promotion=ex["numpy1_promotion"])   # noqa: E731
+    def _plane_major(self, ws, L, R, D, left, right, hwd, sups, m, timer, keep):
+        """Every stage on the reference's [D,H,W] layout but SGM, which runs on pixel-major copies in the spare
+        ping-pong buffers (every buffer holds either layout).  Same arguments and result as _pixel_major_free, plus the
+        pixel-major views of the volume buffers."""
+        hp = self.hp
+        (lcv, t1d), (rcv, t2d) = self._aggregate_dhw(left, right, sups, hp["cbca_num_iterations1"], timer)
+        if keep is not None:
+            keep["cbca1"] = (lcv.clone(), rcv.clone())
+        lh = next(h for b, h in zip(ws["vol"], hwd) if b.data_ptr() == t1d.data_ptr())
+        rh = next(h for b, h in zip(ws["vol"], hwd) if b.data_ptr() == t2d.data_ptr())
+        sgm_average_from_dhw(L, R, [lcv, rcv], [lh, rh], [hip.MCCNN_SIDE_LEFT, hip.MCCNN_SIDE_RIGHT], D, *self._sgm_hp(),
+                             ws["scratch"], timer)
+        timer.start("hwd_to_dhw")
+        hwd_to_dhw(lh, D, lcv)
+        hwd_to_dhw(rh, D, rcv)
+        timer.stop()
+        if keep is not None:
+            keep["sgm"] = (lcv.clone(), rcv.clone())
+        (lcv, t1d), (rcv, t2d) = self._aggregate_dhw((lcv, t1d), (rcv, t2d), sups, hp["cbca_num_iterations2"], timer)
+        if keep is not None:
+            keep["cbca2"] = (lcv.clone(), rcv.clone())
+        timer.start("wta")
+        dl, dr = wta(lcv, out=m[0]), wta(rcv, out=m[1])
+        timer.stop()
+        return dl, dr, lcv
 
-        # per-pair maps live in the workspace unless the caller keeps intermediates (tests): apart from the returned
-        # map (see `out`) a pair then allocates nothing but the conv activations and never blocks the host
+    def _post(self, ws, L, D, dl, dr, left_volume, pixel_major, m, timer, keep, out, static_out):
+        """a8 .. a11 on the WTA maps and the left result volume (in the layout `pixel_major` says).  Per-pair maps live
+        in the workspace unless the caller keeps intermediates (tests): apart from the returned map (see `out`) a pair
+        then allocates nothing but the conv activations and never blocks the host."""
+        hp, ex = self.hp, self.extras
+        if out is not None and (tuple(out.shape) != tuple(L.shape) or out.dtype != torch.float32 or not out.is_contiguous()
+                                or out.device != L.device):
+            raise ValueError("match: `out` must be a contiguous float32 [H,W] tensor on the images' device")
         timer.start("post")
         st = lr_status(dl, dr, D, out=ws["status"] if keep is None else None)
         di = interpolate(dl, st, out=m[2], directions=ex["interpolation_directions"],
                          occlusion_from_left=ex["occlusion_from_left"])
-        ds = sub(di)
+        if pixel_major:
+            ds = subpixel_hwd(di, left_volume, D, out=m[3], numpy1_promotion=ex["numpy1_promotion"])
+        else:
+            ds = subpixel(di, left_volume, out=m[3], numpy1_promotion=ex["numpy1_promotion"])
         dm = median(ds, 5, 5, out=m[4])
-        if out is not None and (tuple(out.shape) != (H, W) or out.dtype != torch.float32 or not out.is_contiguous()
-                                or out.device != L.device):
-            raise ValueError("match: `out` must be a contiguous float32 [H,W] tensor on the images' device")
         db = bilateral(L, dm, 5, 5, 0, hp["blur_sigma"], hp["blur_threshold"], out=out if out is not None else m[5])
         timer.stop()
         if keep is not None:
@@ -1364,7 +1294,67 @@ class StereoMatcher(object):
             return db
         # the workspace map is overwritten by the next pair: hand out a copy unless the caller passed its own tensor
         # or (match_graph) wants the static buffer
-        return db if (_static_out or out is not None) else db.clone()
+        return db if (static_out or out is not None) else db.clone()
+
+    def _match(self, left_image, right_image, ndisp, timer=_NO_TIMER, keep=None, _static_out=False, out=None):
+        """left/right: standardised float32 device tensors [H,W] (or [H,W,1]).  Returns the final left disparity
+        map [H,W] on the device.  The matcher's workspace is reused by the next call, so the map is handed out as a
+        copy - one [H,W] allocation + one copy per pair; pass `out` (a contiguous float32 [H,W] device tensor) and the
+        last kernel writes there instead: nothing is allocated but the conv activations.  `keep`, if a dict, receives
+        intermediate device tensors in the reference's [D,H,W] layout (tests)."""
+        L = left_image.reshape(left_image.shape[0], left_image.shape[1]).contiguous()
+        R = right_image.reshape(right_image.shape[0], right_image.shape[1]).contiguous()
+        H, W = L.shape
+        D = int(ndisp)
+        ws = self.workspace(H, W, D)
+        dp = hwd_pitch(D)
+        dhw = [b[:D * H * W].view(D, H, W) for b in ws["vol"]]      # every volume buffer in either layout
+        hwd = [b[:H * W * dp].view(H, W, dp) for b in ws["vol"]]
+        # Without per-stage timing the side work runs beside the cost volume; with it, on the main stream behind it.
+        overlap = timer is _NO_TIMER
+        # Free-running chains need the one-volume program launches (program buffers exist on the pixel-major "prog"
+        # route only); with `keep` the stages are joined, so that both volumes of a stage can be handed out.
+        free = self.free_chains and self.two_chains and keep is None and ws["progs"] is not None
+        flag_planes = None
+
+        timer.start("features")
+        if self.features == "split_f16":
+            fl, fr = self.net.features_pair_hwc_split(L, R)
+        else:
+            fl, fr = self.net.features_pair_hwc(L, R, tile_rows=self.feature_tile_rows)
+        timer.stop()
+        if overlap:
+            sup_l, sup_r, flag_planes, ready = self._side_work(ws, L, R, D, want_flags=free and self.sgm_flags_once)
+        lv, rv, pixel_major = self._cost_volumes(fl, fr, D, dhw, hwd, timer)
+        del fl, fr
+        if keep is not None:
+            keep["cv"] = (hwd_to_dhw(lv, D), hwd_to_dhw(rv, D)) if pixel_major else (lv.clone(), rv.clone())
+        if overlap:
+            torch.cuda.current_stream().wait_event(ready)
+        else:
+            sup_l, sup_r = self._side_work_timed(ws, L, R, D, timer)
+        sups = (sup_l, sup_r)
+
+        m = ws["maps"] if keep is None else torch.empty_like(ws["maps"])
+        if self.pixel_major():
+            if not pixel_major:
+                timer.start("cv_to_pixel_major")
+                lv, rv = dhw_to_hwd(lv, hwd[2]), dhw_to_hwd(rv, hwd[3])
+                timer.stop()
+            # The second aggregation's last iteration carries the WTA of both results when a wave holds all disparities
+            # of a pixel and the arms are short enough for the kernels that have that form (on the free path the
+            # program buffers imply the distance term).
+            fuse = (int(self.hp["cbca_num_iterations2"]) >= 1 and D <= cbca_hwd_wta_max_d()
+                    and int(self.hp["cbca_distance"]) <= CBCA_HWD_MAX_DISTANCE)
+            if free:
+                dl, dr, left_volume = self._pixel_major_free(ws, L, R, D, (lv, hwd[0]), (rv, hwd[1]), sups, flag_planes,
+                                                             fuse, m, timer)
+            else:
+                dl, dr, left_volume = self._pixel_major_joined(ws, L, R, D, (lv, hwd[0]), (rv, hwd[1]), sups, fuse, m,
+                                                               timer, keep)
+        else:
+            dl, dr, left_volume = self._plane_major(ws, L, R, D, (lv, dhw[2]), (rv, dhw[3]), hwd, sups, m, timer, keep)
+        return self._post(ws, L, D, dl, dr, left_volume, self.pixel_major(), m, timer, keep, out, _static_out)
 
     def _ingest_buffers(self, H, W):
         """Static float32 inputs + ingest scratch of the eager byte path: kept per shape, so that a pair allocates
@@ -1388,82 +1378,84 @@ class StereoMatcher(object):
         ingest_u8_pair(left_u8, right_u8, sl, sr, scratch)
         return self.match(sl, sr, ndisp, out=out)
 
+    def _capture(self, key, shape, make_static, prologue=None):
+        """One pair captured as a graph: self._graphs[key] = (graph, static, out).  make_static() allocates and fills
+        the static inputs - static[0], static[1]: the float32 images the pair reads - once the workspace is resident;
+        prologue(*static), if given, is issued in front of every pair, inside the graph too (the ingest launches).
+        The order is the rule:
+          1. workspace() before anything else - it may reset self._graphs (one shape resident at a time);
+          2. fresh side / right-chain streams for this capture: a stream never takes part in the captures of two graphs
+             (see _right_stream);
+          3. two eager warm-up pairs on a stream of their own, so that MIOpen has chosen its kernels and the allocator
+             its blocks, joined to the current stream;
+          4. every stream the pair touches (the side stream of the builder, the right volume's chain) idle before the
+             capture begins: streams that enter a capture with eager work still queued have crashed the runtime once."""
+        H, W, D = shape
+        self.workspace(H, W, D)
+        self._side = self._right = None
+        static = make_static()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                if prologue is not None:
+                    prologue(*static)
+                self._match(static[0], static[1], D)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            if prologue is not None:
+                prologue(*static)
+            out = self._match(static[0], static[1], D, _static_out=True)
+        self._graphs[key] = (graph, static, out)
+        return self._graphs[key]
+
+    def _static_u8(self, left_u8, right_u8, H, W):
+        """The static buffers of match_graph_u8: (float32 left, right, the byte images, the ingest scratch)."""
+        bl = torch.empty(tuple(left_u8.shape), dtype=torch.uint8, device=self.device)
+        br = torch.empty_like(bl)
+        sl = torch.empty((H, W), dtype=torch.float32, device=self.device)
+        sr = torch.empty((H, W), dtype=torch.float32, device=self.device)
+        scratch = ingest_scratch(H, W, self.device)
+        bl.copy_(left_u8)
+        br.copy_(right_u8)
+        return sl, sr, bl, br, scratch
+
     def match_graph_u8(self, left_u8, right_u8, ndisp):
         """match_graph() from bytes: static uint8 inputs, and the ingest launches INSIDE the captured graph, writing the
         static float32 images the rest of the graph reads - per pair two byte copies (from the device or from pinned host
-        memory, in stream order, non-blocking) and one replay.  One graph per
-        (H, W, ndisp, C); the rules of match_graph's capture hold (fresh side / right-chain streams per capture, every
-        stream idle before it, two eager warm-up pairs).  Returns the static output map (overwritten by the next call)."""
+        memory, in stream order, non-blocking) and one replay.  One graph per (H, W, ndisp, C), captured by the rules of
+        _capture.  Returns the static output map (overwritten by the next call)."""
         H, W, C = _u8_image(left_u8)
         if _u8_image(right_u8) != (H, W, C):
             raise ValueError("match_graph_u8: the two images must have the same shape")
         key = (H, W, int(ndisp), "u8", C)
-        g = self._graphs.get(key)
-        if g is None:
-            self.workspace(H, W, int(ndisp))     # may reset self._graphs: one shape resident at a time
-            self._side = None
-            self._right = None
-            bl = torch.empty(tuple(left_u8.shape), dtype=torch.uint8, device=self.device)
-            br = torch.empty_like(bl)
-            sl = torch.empty((H, W), dtype=torch.float32, device=self.device)
-            sr = torch.empty((H, W), dtype=torch.float32, device=self.device)
-            scratch = ingest_scratch(H, W, self.device)
-            bl.copy_(left_u8)
-            br.copy_(right_u8)
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    ingest_u8_pair(bl, br, sl, sr, scratch)
-                    self._match(sl, sr, ndisp)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()             # every stream idle before the capture begins (see match_graph)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                ingest_u8_pair(bl, br, sl, sr, scratch)
-                out = self._match(sl, sr, ndisp, _static_out=True)
-            g = (graph, bl, br, sl, sr, out)
-            self._graphs[key] = g
-        graph, bl, br, sl, sr, out = g
+        g = self._graphs.get(key) or self._capture(
+            key, key[:3], lambda: self._static_u8(left_u8, right_u8, H, W),
+            lambda sl, sr, bl, br, scratch: ingest_u8_pair(bl, br, sl, sr, scratch))
+        graph, (sl, sr, bl, br, _scratch), out = g
         bl.copy_(left_u8, non_blocking=True)
         br.copy_(right_u8, non_blocking=True)
         graph.replay()
         self._saturated_pair(sl, sr, ndisp, out)      # on_saturation (one host synchronisation unless "ignore")
         return out
 
+    @staticmethod
+    def _static_f32(L, R):
+        sl, sr = torch.empty_like(L, dtype=torch.float32), torch.empty_like(R, dtype=torch.float32)
+        sl.copy_(L)
+        sr.copy_(R)
+        return sl, sr
+
     def match_graph(self, left_image, right_image, ndisp):
         """match() replayed as ONE hipGraph launch: the ~75 kernel launches of a pair are captured once per image
-        shape (after two eager warm-up pairs, so MIOpen has chosen its kernels and the allocator its blocks) and
-        replayed on static input/output buffers.  Returns the static output map [H,W] (overwritten by the next
-        call).  The images are copied into the static inputs in stream order; nothing synchronises."""
+        shape (_capture) and replayed on static input/output buffers.  Returns the static output map [H,W] (overwritten
+        by the next call).  The images are copied into the static inputs in stream order; nothing synchronises."""
         L = left_image.reshape(left_image.shape[0], left_image.shape[1])
         R = right_image.reshape(right_image.shape[0], right_image.shape[1])
         key = (L.shape[0], L.shape[1], int(ndisp))
-        g = self._graphs.get(key)
-        if g is None:
-            self.workspace(*key)                 # may reset self._graphs: one shape resident at a time
-            # fresh side / right-chain streams for this capture: a stream never takes part in the captures of two graphs
-            # (see _right_stream)
-            self._side = None
-            self._right = None
-            sl, sr = torch.empty_like(L, dtype=torch.float32), torch.empty_like(R, dtype=torch.float32)
-            sl.copy_(L)
-            sr.copy_(R)
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    self._match(sl, sr, ndisp)
-            torch.cuda.current_stream().wait_stream(side)
-            # every stream the pair touches (the side stream of the builder, the right volume's chain) is idle before the
-            # capture begins: streams that enter a capture with eager work still queued have crashed the runtime once
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                out = self._match(sl, sr, ndisp, _static_out=True)
-            g = (graph, sl, sr, out)
-            self._graphs[key] = g
-        graph, sl, sr, out = g
+        graph, (sl, sr), out = self._graphs.get(key) or self._capture(key, key, lambda: self._static_f32(L, R))
         sl.copy_(L)
         sr.copy_(R)
         graph.replay()

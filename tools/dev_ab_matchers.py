@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Dev harness (GPU box): same-box A/B of StereoMatcher options on the benchmark pair, graph replays, alternating.
-    python tools/dev_ab_matchers.py one_launch_builder=False two_chains=False ...   (each argument = one variant against the default)"""
+    python tools/dev_ab_matchers.py free_chains=False two_chains=False ...   (each argument = one variant against the default)"""
 import os
 import sys
 import time
