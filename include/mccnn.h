@@ -45,7 +45,7 @@ extern "C" {
 
 typedef void *mccnn_stream_t; /* hipStream_t */
 
-#define MCCNN_ABI_VERSION 7 /* 2: window-mask plane, *_hwd entry points; 3: saturation flags; 4: program-driven CBCA; 5: skip programs; 6: one-volume launches; 7: refresh launches, SGM flag planes as a call of their own; still 7 with the mccnn_ingest_* entry points: purely additive, nothing that existed changed */
+#define MCCNN_ABI_VERSION 7 /* 2: window-mask plane, *_hwd entry points; 3: saturation flags; 4: program-driven CBCA; 5: skip programs; 6: one-volume launches; 7: refresh launches, SGM flag planes as a call of their own; still 7 with the mccnn_ingest_* and the mccnn_decision_* / mccnn_cost_volume_accurate* entry points: purely additive, nothing that existed changed */
 
 #define MCCNN_E_INVALID (-1)     /* bad argument (null pointer, non-positive size, unsupported shape) */
 #define MCCNN_E_UNSUPPORTED (-2) /* shape outside what the kernels were built for (e.g. D > 1024 for SGM) */
@@ -74,6 +74,39 @@ int mccnn_cost_volume(const float *fl, const float *fr, int H, int W, int C, int
  * are not written), for MCCNN_CV_EXACT and (ABI 5) MCCNN_CV_MFMA alike; D <= 1024. */
 int mccnn_cost_volume_hwd(const float *fl, const float *fr, int H, int W, int C, int D, float *lcv_hwd, float *rcv_hwd,
                           int mode, mccnn_stream_t stream);
+
+/* ---- a2 for the "accurate" network (Zbontar & LeCun 2016, sec. 3.2): the decision MLP on the matrix cores -----------
+ * s(h,w,d) = sigmoid(wf . relu(W_n ... relu(W_2 . relu(aL[h,w] + aR[h,w-d]) + b_2) ... + b_n) + bf) for w >= d;
+ * lcv = -s at (h,w,d), rcv = -s at (h,w-d,d); the border columns are filled by the same recurrences, the same kernels,
+ * as mccnn_cost_volume / mccnn_cost_volume_hwd (plane-major [D][H][W] / pixel-major [H][W][Dp]).
+ * aL, aR: [H][W][units] float32, the two halves of the first fully-connected layer evaluated per pixel by the caller
+ *   (aL = W1[:, :C] . fL + b1, aR = W1[:, C:] . fR: the layer is linear in the concatenation).
+ * n_fc: hidden layers of `units` units INCLUDING that first one; the kernel applies layers 2 .. n_fc.
+ * packed: their weights as mccnn_decision_pack laid them out for the same n_fc and mode with weight_scale (a power of
+ *   two that brings max |w| near 1024); weights: [n_fc-1][units out][units in] float32; biases: [n_fc-1][units];
+ *   w_final [units], b_final: the last layer.  mccnn_decision_pack_bytes: size of `packed` (0: outside the envelope).
+ * mode MCCNN_CV_EXACT: every float32 operand as two f16 numbers, three v_mfma_f32_32x32x16_f16 products per multiply,
+ *   float32 accumulation - float32-accurate scores; MCCNN_CV_MFMA: one f16 product per multiply.
+ * saturation_flag (device int, may be NULL): set to 1 when an activation of a stored voxel exceeds the f16 range of
+ *   the operands (|x| * 256 > 65504; clamped) - the contract of mccnn_conv3x3_split.
+ * Envelope (MCCNN_E_UNSUPPORTED outside): C (feature maps behind aL / aR) 64 or 112, units = 384, n_fc 3 or 4,
+ *   2 <= D <= 1024, D <= W - 2, H <= 65535; _hwd: one volume row below 2 GiB. */
+size_t mccnn_decision_pack_bytes(int n_fc, int units, int mode);
+int mccnn_decision_pack(const float *weights, int n_fc, int units, float weight_scale, int mode, void *packed,
+                        mccnn_stream_t stream);
+int mccnn_cost_volume_accurate(const float *aL, const float *aR, int H, int W, int C, int units, int n_fc, int D,
+                               const void *packed, const float *biases, const float *w_final, float b_final,
+                               float weight_scale, float *lcv, float *rcv, int mode, int *saturation_flag,
+                               mccnn_stream_t stream);
+int mccnn_cost_volume_accurate_hwd(const float *aL, const float *aR, int H, int W, int C, int units, int n_fc, int D,
+                                   const void *packed, const float *biases, const float *w_final, float b_final,
+                                   float weight_scale, float *lcv_hwd, float *rcv_hwd, int mode, int *saturation_flag,
+                                   mccnn_stream_t stream);
+
+/* The border recurrences alone (pf:94-95, 105-106) on volumes whose w >= d entries are written: the launch every entry
+ * point above ends with, for callers that produce the scores themselves (the library route of the accurate network).
+ * pixel_major = 0: [D][H][W]; != 0: [H][W][Dp], D <= 1024 and one volume row below 2 GiB. */
+int mccnn_cost_volume_fill(float *lcv, float *rcv, int D, int H, int W, int pixel_major, mccnn_stream_t stream);
 
 /* ---- a3  compute_cross_region (pf:571-657) ----------------------------------------------------------------
  * Per pixel: the four arm lengths (<= L-1 per side, anchor-relative threshold |I(q)-I(p)| < tau) and the region

@@ -45,6 +45,12 @@ __device__ __forceinline__ void buffer_store_b96(V3 v, __amdgpu_buffer_rsrc_t rs
 }
 #endif
 
+// Border recurrences of a cost volume whose w >= d scores are written (cost_volume.hip: plane-major [D][H][W] and
+// pixel-major [H][W][Dp]); `what` names the caller in a launch error.
+int launch_cost_volume_fill(float *lcv, float *rcv, int D, int H, int W, hipStream_t s, const char *what);
+int launch_cost_volume_fill_hwd(float *lcv_hwd, float *rcv_hwd, int D, int Dp, int H, int W, hipStream_t s,
+                                const char *what);
+
 #define MCCNN_REQUIRE(cond, code, ...)        \
     do {                                      \
         if (!(cond)) {                        \

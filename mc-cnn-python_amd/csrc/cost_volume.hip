@@ -715,6 +715,31 @@ __global__ __launch_bounds__(64) void cost_volume_fill_hwd_lanes_kernel(float *_
     for (int t = max(nA, 0); t < nsteps; ++t) step(col(t), false, 0.f);
 }
 
+// The border recurrences as launches of their own: every producer of the w >= d scores (the feature dot products here,
+// the decision network of decision_mfma.hip) ends with them.
+int launch_cost_volume_fill(float *lcv, float *rcv, int D, int H, int W, hipStream_t s, const char *what)
+{
+    if (D > 1)
+        hipLaunchKernelGGL(cost_volume_fill_kernel, dim3(cdiv(H, 64), D - 1, 2), dim3(64), 0, s, lcv, rcv, D, H, W);
+    return check_launch(what);
+}
+
+int launch_cost_volume_fill_hwd(float *lcv_hwd, float *rcv_hwd, int D, int Dp, int H, int W, hipStream_t s, const char *what)
+{
+    if (D > 1) {
+#ifdef CV_FILL_FOUR_PER_LANE     // A/B builds: the four-disparities-per-lane sweep (one wave per row and side)
+        if (Dp <= 256)
+            hipLaunchKernelGGL(cost_volume_fill_hwd_kernel<1>, dim3(H, 2), dim3(64), 0, s, lcv_hwd, rcv_hwd, D, Dp, H, W);
+        else
+            hipLaunchKernelGGL(cost_volume_fill_hwd_kernel<2>, dim3(H, 2), dim3(64), 0, s, lcv_hwd, rcv_hwd, D, Dp, H, W);
+#else
+        hipLaunchKernelGGL(cost_volume_fill_hwd_lanes_kernel, dim3(H, 2, cdiv(D, 64)), dim3(64), 0, s, lcv_hwd, rcv_hwd, D, Dp,
+                           H, W);
+#endif
+    }
+    return check_launch(what);
+}
+
 }  // namespace mccnn
 
 extern "C" int mccnn_cost_volume(const float *fl, const float *fr, int H, int W, int C, int D, float *lcv, float *rcv,
@@ -743,9 +768,7 @@ extern "C" int mccnn_cost_volume(const float *fl, const float *fr, int H, int W,
     }
     int rc = check_launch("mccnn_cost_volume");
     if (rc) return rc;
-    if (D > 1)
-        hipLaunchKernelGGL(cost_volume_fill_kernel, dim3(cdiv(H, 64), D - 1, 2), dim3(64), 0, s, lcv, rcv, D, H, W);
-    return check_launch("mccnn_cost_volume(fill)");
+    return launch_cost_volume_fill(lcv, rcv, D, H, W, s, "mccnn_cost_volume(fill)");
 }
 
 extern "C" int mccnn_cost_volume_hwd(const float *fl, const float *fr, int H, int W, int C, int D, float *lcv_hwd,
@@ -787,16 +810,19 @@ extern "C" int mccnn_cost_volume_hwd(const float *fl, const float *fr, int H, in
     }
     int rc = check_launch("mccnn_cost_volume_hwd");
     if (rc) return rc;
-    if (D > 1) {
-#ifdef CV_FILL_FOUR_PER_LANE     // A/B builds: the four-disparities-per-lane sweep (one wave per row and side)
-        if (Dp <= 256)
-            hipLaunchKernelGGL(cost_volume_fill_hwd_kernel<1>, dim3(H, 2), dim3(64), 0, s, lcv_hwd, rcv_hwd, D, Dp, H, W);
-        else
-            hipLaunchKernelGGL(cost_volume_fill_hwd_kernel<2>, dim3(H, 2), dim3(64), 0, s, lcv_hwd, rcv_hwd, D, Dp, H, W);
-#else
-        hipLaunchKernelGGL(cost_volume_fill_hwd_lanes_kernel, dim3(H, 2, cdiv(D, 64)), dim3(64), 0, s, lcv_hwd, rcv_hwd, D, Dp,
-                           H, W);
-#endif
-    }
-    return check_launch("mccnn_cost_volume_hwd(fill)");
+    return launch_cost_volume_fill_hwd(lcv_hwd, rcv_hwd, D, Dp, H, W, s, "mccnn_cost_volume_hwd(fill)");
+}
+
+extern "C" int mccnn_cost_volume_fill(float *lcv, float *rcv, int D, int H, int W, int pixel_major, mccnn_stream_t stream)
+{
+    using namespace mccnn;
+    MCCNN_REQUIRE(lcv && rcv, MCCNN_E_INVALID, "mccnn_cost_volume_fill: null pointer");
+    MCCNN_REQUIRE(H > 0 && W > 0 && D > 0, MCCNN_E_INVALID, "mccnn_cost_volume_fill: non-positive size");
+    MCCNN_REQUIRE(D <= W - 2, MCCNN_E_UNSUPPORTED, "mccnn_cost_volume_fill: D=%d needs W >= D+2, W=%d", D, W);
+    if (!pixel_major) return launch_cost_volume_fill(lcv, rcv, D, H, W, (hipStream_t)stream, "mccnn_cost_volume_fill");
+    const int Dp = mccnn_hwd_pitch(D);
+    MCCNN_REQUIRE(D <= 1024, MCCNN_E_UNSUPPORTED, "mccnn_cost_volume_fill: D=%d > 1024", D);
+    MCCNN_REQUIRE((size_t)W * Dp * 4 < ((size_t)1 << 31), MCCNN_E_UNSUPPORTED,
+                  "mccnn_cost_volume_fill: a %d x %d row exceeds a buffer descriptor's reach", W, D);
+    return launch_cost_volume_fill_hwd(lcv, rcv, D, Dp, H, W, (hipStream_t)stream, "mccnn_cost_volume_fill");
 }

@@ -289,15 +289,14 @@ class MatcherBackend(object):
         # records; that pair - and, with several in flight, the ones that shared the flag with it - is matched again
         # with the float32 library convolutions before its slot is reused
         m0 = self.matchers[0]
-        if m0.features == "split_f16" and m0.features_saturated():
+        if m0.saturation_checked() and m0.features_saturated():
             self._redo_left = len(self.matchers)
         if self._redo_left <= 0:
             return None
         self._redo_left -= 1
         if self._redo_matcher is None:
             self._redo_matcher = self.make_library_matcher()
-        self.log("[{}] activations left the matrix-core feature kernels' range: {} repeated with the float32 library "
-                 "convolutions".format(self.rank, job.paths["out"]))
+        self.log("[{}] ".format(self.rank) + m0.saturation_notice().format(job.paths["out"]))
         disparity = self._redo_matcher.match_u8(job.left, job.right, job.ndisp)
         again = self._to_host(disparity)
         self.torch.cuda.synchronize()

@@ -92,6 +92,16 @@ parser.add_argument("--pipeline", action="store_true",
                          "wall time from the enqueue of its host-to-device copy to its map being on the host, overlap "
                          "with other pairs (and a graph capture, where the pair paid one) included")
 parser.add_argument("--readers", type=int, default=4, help="with --pipeline: decoder threads")
+parser.add_argument("--arch", choices=("fast", "accurate"), default="fast",
+                    help="network architecture: 'fast' (the reference's: dot product of normalised 64-vectors) or 'accurate' "
+                         "(the paper's other network: 112-map tower + a fully-connected decision network evaluated for "
+                         "every pixel and disparity on the matrix cores; --resume is then an .npz with fc<k>/ variables; "
+                         "--fast selects its plain-f16 precision)")
+parser.add_argument("--num_fc_layers", type=int, default=3,
+                    help="with --arch accurate: hidden fully-connected layers (Middlebury 3, KITTI 4)")
+parser.add_argument("--decision", choices=("auto", "kernel", "library"), default="auto",
+                    help="with --arch accurate: the decision stage by the hand-written kernel, by float32 library "
+                         "matmuls, or whichever serves the pair")
 # opt-in departures from the reference's results: what the MC-CNN paper does and the reference names but leaves out
 parser.add_argument("--paper_support_regions", action="store_true",
                     help="CBCA support regions intersected with the other view's at every disparity (paper sec. 4.1; "
@@ -137,7 +147,7 @@ def main(argv=None):
     import _hipabi as hip
     import stereo_device as sd
     from distributed import shard_indices
-    from model import NET
+    from model import ACCURATE_NET, NET
 
     hip.require_device()
     # one rank per GPU under torchrun; MCCNN_SHARED_GPU=1 (tests) lets several ranks share the visible GPUs
@@ -152,23 +162,30 @@ def main(argv=None):
     with open(args.list_file, "r") as f:
         left_paths = [line.strip() for line in f.readlines()]
 
-    net = NET(None, input_patch_size=args.patch_size, num_conv_layers=(args.patch_size - 1) // 2, batch_size=1,
-              device="cuda")
+    accurate = args.arch == "accurate"
+    if accurate:
+        net = ACCURATE_NET(None, input_patch_size=args.patch_size, num_conv_layers=(args.patch_size - 1) // 2,
+                           batch_size=1, device="cuda", num_fc_layers=args.num_fc_layers)
+    else:
+        net = NET(None, input_patch_size=args.patch_size, num_conv_layers=(args.patch_size - 1) // 2, batch_size=1,
+                  device="cuda")
     net.restore(args.resume)  # loaded once and kept resident (the reference re-restores per pair)
     in_flight = max(1, int(args.pairs_in_flight))
 
-    def make_matcher(features):
+    def make_matcher(features, decision=args.decision):
         return sd.StereoMatcher(
             net, hyper_parameters(args),
             cv_mode=hip.MCCNN_CV_MFMA if args.fast else hip.MCCNN_CV_EXACT,
             cbca_order=hip.MCCNN_CBCA_SEPARABLE if (args.fast and args.separable_cbca) else hip.MCCNN_CBCA_REFERENCE_ORDER,
-            features=features,
+            features=features, decision=decision,
             on_saturation="ignore",      # several pairs may be in flight: finish() polls the flag and repeats them
             extras=dict(both_view_support=args.paper_support_regions,
                         interpolation_directions=16 if args.paper_interpolation else 4,
                         occlusion_from_left=args.paper_interpolation, numpy1_promotion=args.numpy1_promotion))
 
     matchers = [make_matcher("miopen" if args.features == "library" else "auto") for _ in range(in_flight)]
+    footprint_kw = dict(pairs_in_flight=in_flight, arch=args.arch,
+                        fc_units=net.num_fc_units if accurate else sd.DECISION_UNITS)
     streams = [torch.cuda.Stream() for _ in range(in_flight)] if in_flight > 1 else [None]
     if args.pipeline:
         import list_matcher as lm
@@ -185,9 +202,9 @@ def main(argv=None):
 
         def check_shape(height, width, ndisp):      # the flagless loop's refusal, with its message
             sd.workspace_bytes(height, width, ndisp, matchers[0].pixel_major(),
-                               matchers[0].workspace_cbca_kernel(height, width, ndisp), pairs_in_flight=in_flight)
+                               matchers[0].workspace_cbca_kernel(height, width, ndisp), **footprint_kw)
 
-        backend = lm.MatcherBackend(matchers, streams, lambda: make_matcher("miopen"), rank=rank)
+        backend = lm.MatcherBackend(matchers, streams, lambda: make_matcher("miopen", "library"), rank=rank)
         pipeline = lm.ListPipeline(lm.make_reader(paths, check_shape), backend, lm.make_writer(rank), slots=in_flight,
                                    readers=args.readers)
         try:
@@ -208,14 +225,13 @@ def main(argv=None):
         # the hand-written feature kernels report an activation beyond the range of their stored records (never seen
         # on standardised images with the trained weights): that pair - and, with several in flight, the ones that
         # shared the flag with it - is matched again with the float32 library convolutions
-        if matchers[0].features == "split_f16" and matchers[0].features_saturated():
+        if matchers[0].saturation_checked() and matchers[0].features_saturated():
             redo["left"] = in_flight
         if redo["left"] > 0:
             redo["left"] -= 1
             if redo["matcher"] is None:
-                redo["matcher"] = make_matcher("miopen")
-            print("[{}] activations left the matrix-core feature kernels' range: {} repeated with the float32 library "
-                  "convolutions".format(rank, out_path))
+                redo["matcher"] = make_matcher("miopen", "library")
+            print("[{}] ".format(rank) + matchers[0].saturation_notice().format(out_path))
             disparity = redo["matcher"].match(images[0], images[1], images[2])
             torch.cuda.synchronize()
         left_disparity_map = disparity.cpu().numpy()
@@ -244,8 +260,7 @@ def main(argv=None):
         # refuses a shape outside what the kernels serve (ValueError naming the limit); each matcher checks its own
         # workspace against the free device memory before it allocates it
         footprint = sd.workspace_bytes(height, width, ndisp, matchers[0].pixel_major(),
-                                       matchers[0].workspace_cbca_kernel(height, width, ndisp),
-                                       pairs_in_flight=in_flight)
+                                       matchers[0].workspace_cbca_kernel(height, width, ndisp), **footprint_kw)
         if (height, width, ndisp) != last_shape:
             print("[{}] workspace {:.2f} GB ({} pair(s) in flight)".format(rank, footprint / 1e9, in_flight))
             last_shape = (height, width, ndisp)

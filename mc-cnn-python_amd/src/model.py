@@ -1,4 +1,4 @@
-"""Feature head of the "fast" MC-CNN - drop-in for /root/reference/src/model.py (NET, :9-65; conv, :90-125).
+"""Feature head of the "fast" MC-CNN (NET) and the "accurate" network (ACCURATE_NET, at the end of the file) - drop-in for /root/reference/src/model.py (NET, :9-65; conv, :90-125).
 
 Same constructor arguments and attributes (`.X`, `.conv1 ... .convN`, `.features`); the TensorFlow graph is
 replaced by eager PyTorch-ROCm convolutions (MIOpen), which is where north_star keeps the small conv stack.
@@ -278,6 +278,177 @@ class NET(object):
             for v in range(2):   # the band's unit vectors go straight into the [H,W,64] result
                 stereo_device.l2norm_chw_to_hwc(t[v], self.biases[-1], out=feats[v][y0:y1])
         return feats[0], feats[1]
+
+
+class ACCURATE_NET(NET):
+    """The "accurate" architecture of Zbontar & LeCun 2016 (sec. 3.2), which the reference leaves out: the same tower
+    of 3x3 VALID convolutions - ReLU after EVERY layer, NO normalisation, 112 maps by default - and a decision network
+    on the concatenation [fL ; fR]: num_fc_layers fully-connected layers of num_fc_units units with ReLU, then a
+    units -> 1 layer and a sigmoid.  Middlebury: 5 conv layers, patch 11, 3 fc layers; KITTI: 4, 9, 4.
+
+    Variables: conv{k}/weights|biases as NET, fc{k}/weights [in,out], fc{k}/biases, k = 1 .. num_fc_layers + 1 (held
+    in torch layout [out,in] in .fc_weights / .fc_biases).  Checkpoints are .npz files.
+    Patch batches run on torch (CPU or GPU): `net(x)` gives the tower's [B,1,1,C] outputs, `net.scores(l, r)` the
+    similarity in (0,1).  Whole images use NET's float32 library convolutions; the per-voxel decision stage is
+    stereo_device.cost_volume_accurate (csrc/decision_mfma.hip, or torch matmuls)."""
+
+    def __init__(self, x=None, weights_path='DEFAULT',
+                 input_patch_size=11, num_conv_layers=5, num_conv_feature_maps=112,
+                 conv_kernel_size=3, batch_size=128, device=None, seed=0, num_fc_layers=3, num_fc_units=384):
+        self.num_fc_layers = int(num_fc_layers)
+        self.num_fc_units = int(num_fc_units)
+        assert self.num_fc_layers >= 1 and self.num_fc_units >= 1
+        NET.__init__(self, x, weights_path, input_patch_size, num_conv_layers, num_conv_feature_maps, conv_kernel_size,
+                     batch_size, device, seed)
+
+    def _init_variables(self, seed):
+        NET._init_variables(self, seed)
+        g = torch.Generator().manual_seed(seed + 1)
+        self.fc_weights = []  # torch layout [out, in]
+        self.fc_biases = []
+        fan_in = 2 * self.num_conv_feature_maps
+        for k in range(self.num_fc_layers + 1):
+            fan_out = self.num_fc_units if k < self.num_fc_layers else 1
+            limit = math.sqrt(6.0 / (fan_in + fan_out))   # glorot_uniform, like the conv variables
+            w = (torch.rand((fan_out, fan_in), generator=g) * 2 - 1) * limit
+            b = (torch.rand((fan_out,), generator=g) * 2 - 1) * limit
+            self.fc_weights.append(w.to(self.device))
+            self.fc_biases.append(b.to(self.device))
+            fan_in = fan_out
+
+    def set_layers(self, layers, fc_layers=None):
+        """layers as NET.set_layers; fc_layers: list of (weights [in,out], biases [out]), fc1 .. fc<n_fc+1>."""
+        NET.set_layers(self, layers)
+        if fc_layers is not None:
+            assert len(fc_layers) == self.num_fc_layers + 1, "checkpoint has %d fc layers, ACCURATE_NET was built with %d" % (
+                len(fc_layers), self.num_fc_layers + 1)
+            self.fc_weights = [torch.from_numpy(np.ascontiguousarray(np.asarray(w, np.float32).T)).to(self.device)
+                               for w, _ in fc_layers]
+            self.fc_biases = [torch.from_numpy(np.ascontiguousarray(b, dtype=np.float32)).to(self.device)
+                              for _, b in fc_layers]
+            fan_in = 2 * self.num_conv_feature_maps
+            for k, w in enumerate(self.fc_weights):
+                fan_out = self.num_fc_units if k < self.num_fc_layers else 1
+                assert tuple(w.shape) == (fan_out, fan_in), "fc%d/weights is %s, expected [%d,%d]" % (
+                    k + 1, tuple(w.shape)[::-1], fan_in, fan_out)
+                fan_in = fan_out
+        return self
+
+    def get_fc_layers(self):
+        return [(np.ascontiguousarray(w.detach().cpu().numpy().T), b.detach().cpu().numpy())
+                for w, b in zip(self.fc_weights, self.fc_biases)]
+
+    def restore(self, checkpoint):
+        layers, fc = tf_checkpoint.load_accurate_net_weights(checkpoint)
+        return self.set_layers(layers, fc)
+
+    def save(self, path):
+        tf_checkpoint.save_npz(path, self.get_layers(), self.get_fc_layers())
+
+    # -- forward ------------------------------------------------------------------------------------------------------
+    def _convs_nchw(self, x):
+        outs = []
+        for k in range(self.num_conv_layers):
+            x = F.relu(F.conv2d(x, self.weights[k], self.biases[k]))
+            outs.append(x)
+        return outs
+
+    def __call__(self, x):
+        x = torch.as_tensor(x, dtype=torch.float32).to(self.device)
+        assert x.dim() == 4 and x.shape[-1] == 1, "ACCURATE_NET expects NHWC input with one channel"
+        self.X = x
+        outs = self._convs_nchw(x.permute(0, 3, 1, 2).contiguous())
+        for k, o in enumerate(outs, start=1):
+            setattr(self, "conv%d" % k, o.permute(0, 2, 3, 1))
+        self.features = outs[-1].permute(0, 2, 3, 1)
+        return self.features
+
+    def decision_logits(self, fl, fr):
+        """fl, fr: [..., C] tower outputs -> [...] logits of the decision network on [fl ; fr]."""
+        x = torch.cat((fl, fr), dim=-1)
+        for k in range(self.num_fc_layers):
+            x = F.relu(F.linear(x, self.fc_weights[k], self.fc_biases[k]))
+        return F.linear(x, self.fc_weights[-1], self.fc_biases[-1])[..., 0]
+
+    def decision(self, fl, fr):
+        return torch.sigmoid(self.decision_logits(fl, fr))
+
+    def patch_logits(self, left, right):
+        """left, right: NHWC patch batches [B,p,p,1] -> [B] logits (both through the shared tower as one batch)."""
+        left = torch.as_tensor(left, dtype=torch.float32).to(self.device)
+        right = torch.as_tensor(right, dtype=torch.float32).to(self.device)
+        B = left.shape[0]
+        f = self(torch.cat((left, right), dim=0)).reshape(2 * B, -1)
+        return self.decision_logits(f[:B], f[B:])
+
+    def scores(self, left, right):
+        return torch.sigmoid(self.patch_logits(left, right))
+
+    def first_layer_halves(self, fl, fr, out=None):
+        """The first fc layer is linear in the concatenation: aL = W1[:, :C] fl + b1, aR = W1[:, C:] fr, once per pixel
+        (two library matmuls).  fl, fr: [H,W,C] -> ([H,W,units], [H,W,units]); out: the two tensors to write."""
+        H, W, C = fl.shape
+        w1, b1 = self.fc_weights[0].detach(), self.fc_biases[0].detach()
+        u = w1.shape[0]
+        if out is None:
+            out = (torch.empty((H, W, u), dtype=torch.float32, device=fl.device),
+                   torch.empty((H, W, u), dtype=torch.float32, device=fl.device))
+        torch.addmm(b1, fl.reshape(H * W, C), w1[:, :C].t(), out=out[0].view(H * W, u))
+        torch.mm(fr.reshape(H * W, C), w1[:, C:].t(), out=out[1].view(H * W, u))
+        return out
+
+    # -- whole images -------------------------------------------------------------------------------------------------
+    def supports_split_features(self):
+        return False   # the matrix-core feature kernels are built for 64 maps and end in a normalisation
+
+    def _tower_hwc(self, images):
+        """images [B,H,W] -> [B,H,W,C]: the float32 library stack (_convs_device leaves the last layer's bias out),
+        bias + ReLU of the last layer in one in-place HIP pass, NCHW -> NHWC."""
+        import stereo_device
+        pad = (self.input_patch_size - 1) // 2
+        assert pad == self.num_conv_layers * (self.conv_kernel_size - 1) // 2, \
+            "patch size must equal the receptive field so that features keep the image size"
+        x = self._convs_device(images, pad)
+        x = stereo_device.bias_act_(x, self.biases[-1].detach(), True)
+        return x.permute(0, 2, 3, 1).contiguous()
+
+    def features_hwc(self, image_hw):
+        return self._tower_hwc(image_hw[None].contiguous())[0]
+
+    def features_pair_hwc(self, left_hw, right_hw, tile_rows=None):
+        if tile_rows is not None:
+            raise ValueError("row banding is implemented for the fast network only")
+        f = self._tower_hwc(torch.stack((left_hw, right_hw)))
+        return f[0], f[1]
+
+    def features_pair_hwc_split(self, left_hw, right_hw):
+        raise ValueError("the split-operand feature kernels are built for the fast network (64 maps, normalised)")
+
+    # -- decision kernel operands ---------------------------------------------------------------------------------------
+    def decision_operands(self, mode):
+        """What mccnn_cost_volume_accurate* reads besides aL / aR, rebuilt when a weight tensor changes: (packed weights
+        of fc 2 .. n_fc, weight_scale, biases [n_fc-1,units], final weights [units], final bias as a float).  Reads two
+        scalars back to the host: once per weight set, never inside a graph capture."""
+        import stereo_device
+        key = (int(mode),) + tuple((w.data_ptr(), w._version) for w in self.fc_weights + self.fc_biases)
+        cache = getattr(self, "_decision_cache", None)
+        if cache is None or cache[0] != key:
+            mid = torch.stack([w.detach() for w in self.fc_weights[1:-1]]).contiguous()
+            packed, scale = stereo_device.decision_pack(mid, self.num_fc_layers, mode)
+            biases = torch.stack([b.detach() for b in self.fc_biases[1:-1]]).contiguous()
+            cache = (key, (packed, scale, biases, self.fc_weights[-1].detach().reshape(-1).contiguous(),
+                           float(self.fc_biases[-1].detach().reshape(-1)[0])))
+            self._decision_cache = cache
+        return cache[1]
+
+    def _split_flag(self):
+        """Device int the decision kernel sets when an activation of a stored voxel leaves the f16 range of its
+        operands (|x| >= 255.9): the contract of the fast network's feature kernels."""
+        f = getattr(self, "_split_sat", None)
+        if f is None or f.device != self.fc_weights[0].device:
+            f = torch.zeros((1,), dtype=torch.int32, device=self.fc_weights[0].device)
+            self._split_sat = f
+        return f
 
 
 if __name__ == "__main__":

@@ -25,15 +25,18 @@ Opt-in departures from the reference's results (defaults reproduce it):
                                              rounded once): what the reference's own Python 2.7 + NumPy 1.14 computes;
                                              the default is NumPy >= 2's float32 chain, which the golden vectors pin
 """
+import hashlib
+
 import numpy as np
 import torch
 
 import _hipabi as hip
 import stereo_device as sd
-from model import NET
+from model import ACCURATE_NET, NET
 
 FEATURES = "split_f16"       # "split_f16": hand-written matrix-core conv stack (float32-accurate); "library": MIOpen
 COST_VOLUME_MODE = "exact"
+ACCURATE_DECISION = "auto"   # compute_cost_volume_accurate: "auto" | "kernel" (csrc/decision_mfma.hip) | "library" (torch)
 CBCA_ORDER = "reference"
 CBCA_BOTH_VIEWS = False
 INTERPOLATION_DIRECTIONS = 4
@@ -44,7 +47,7 @@ _CV_MODES = {"exact": hip.MCCNN_CV_EXACT, "mfma": hip.MCCNN_CV_MFMA}
 _CBCA_ORDERS = {"separable": hip.MCCNN_CBCA_SEPARABLE, "reference": hip.MCCNN_CBCA_REFERENCE_ORDER,
                 "reference_plane_major": hip.MCCNN_CBCA_REFERENCE_ORDER}
 
-__all__ = ["compute_features", "compute_cost_volume", "cost_volume_aggregation", "SGM_average",
+__all__ = ["compute_features", "compute_cost_volume", "compute_cost_volume_accurate", "cost_volume_aggregation", "SGM_average",
            "disparity_prediction", "interpolation", "subpixel_enhance", "median_filter", "bilateral_filter",
            "semi_global_matching", "compute_cross_region"]
 
@@ -105,6 +108,51 @@ def compute_cost_volume(featuresl, featuresr, ndisp):
     fl, was_np = _dev(featuresl)
     fr, _ = _dev(featuresr)
     lcv, rcv = sd.cost_volume(fl, fr, int(ndisp), _CV_MODES[COST_VOLUME_MODE])
+    return _ret(lcv, was_np), _ret(rcv, was_np)
+
+
+_DECISION_NETS = {}
+
+
+def compute_cost_volume_accurate(featuresl, featuresr, ndisp, fc_layers):
+    """The accurate network's counterpart of compute_cost_volume (no such function in the reference, whose README
+    leaves the architecture out): features [H,W,C] as compute_features returns them for an ACCURATE_NET, fc_layers
+    that network itself or its checkpoint's list of (weights [in,out], biases) pairs fc1 .. fc<n+1>.  Returns
+    (lcv, rcv) [D,H,W] = -sigmoid score, borders as compute_cost_volume.  COST_VOLUME_MODE "exact" selects the
+    float32-accurate split-operand kernel, "mfma" the plain f16 one; ACCURATE_DECISION the route."""
+    import warnings
+    fl, was_np = _dev(featuresl)
+    fr, _ = _dev(featuresr)
+    if isinstance(fc_layers, ACCURATE_NET):
+        net = fc_layers
+    else:
+        # keyed on the CONTENT of the arrays (the network holds copies of them): an array edited in place, or a new one
+        # at a recycled address, gets its own packed weights
+        digest = hashlib.sha1()
+        for w, b in fc_layers:
+            for a in (w, b):
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                digest.update(repr(a.shape).encode())
+                digest.update(a.tobytes())
+        key = (digest.hexdigest(), int(fl.shape[-1]), str(fl.device))
+        net = _DECISION_NETS.get(key)
+        if net is None:
+            net = ACCURATE_NET(None, num_conv_layers=0, num_conv_feature_maps=int(fl.shape[-1]), batch_size=1,
+                               device=fl.device, num_fc_layers=len(fc_layers) - 1,
+                               num_fc_units=int(np.shape(fc_layers[0][0])[1]))
+            net.set_layers([], fc_layers)
+            _DECISION_NETS.clear()
+            _DECISION_NETS[key] = net
+    route = ACCURATE_DECISION
+    if route != "library":
+        why = sd.decision_kernel_refusal(net, int(fl.shape[1]), int(ndisp))
+        if why is not None and route == "kernel":
+            raise ValueError("ACCURATE_DECISION='kernel': %s" % why)
+        if why is not None:
+            warnings.warn("accurate network: %s; the decision stage runs on the float32 library route" % why)
+        route = "library" if why is not None else (sd.DECISION_AUTO if route == "auto" else "kernel")
+    lcv, rcv = sd.cost_volume_accurate(net, fl, fr, int(ndisp), _CV_MODES[COST_VOLUME_MODE], decision=route,
+                                       pixel_major=False)
     return _ret(lcv, was_np), _ret(rcv, was_np)
 
 

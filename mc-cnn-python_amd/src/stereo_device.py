@@ -182,6 +182,114 @@ def cost_volume_hwd(fl, fr, ndisp, out=None, mode=hip.MCCNN_CV_EXACT):
     return lcv, rcv
 
 
+# ---- a2 for the accurate network: the decision MLP per (pixel, disparity) ------------------------------------------
+DECISION_UNITS = 384                     # csrc/decision_mfma.hip
+DECISION_MAPS = (64, 112)
+DECISION_FC_LAYERS = (3, 4)
+DECISION_MAX_D = 1024
+DECISION_LIBRARY_BYTES = 256 << 20       # library route: bytes one [voxels, units] float32 intermediate may take
+
+
+def decision_kernel_refusal(net, W, D):
+    """None when csrc/decision_mfma.hip serves this network and shape, else the limit it exceeds (a sentence)."""
+    if net.num_conv_feature_maps not in DECISION_MAPS:
+        return "%d feature maps (the decision kernel serves %s)" % (net.num_conv_feature_maps, " or ".join(
+            str(c) for c in DECISION_MAPS))
+    if net.num_fc_units != DECISION_UNITS:
+        return "%d units per hidden layer (the decision kernel is built for %d)" % (net.num_fc_units, DECISION_UNITS)
+    if net.num_fc_layers not in DECISION_FC_LAYERS:
+        return "%d fully-connected layers (the decision kernel serves 3 or 4)" % net.num_fc_layers
+    if D < 2 or D > DECISION_MAX_D:
+        return "ndisp=%d outside [2, %d]" % (D, DECISION_MAX_D)
+    if D > W - 2:
+        return "ndisp=%d needs an image at least ndisp + 2 pixels wide (W=%d)" % (D, W)
+    return None
+
+
+def decision_pack(weights, n_fc, mode):
+    """weights [n_fc-1, units, units] (torch layout [out,in]) of the hidden layers 2 .. n_fc -> (packed device buffer,
+    weight_scale) for mccnn_cost_volume_accurate*(mode).  Reads max |w| back to the host: once per weight set."""
+    lib = hip.load()
+    w = weights.detach().contiguous().float()
+    units = int(w.shape[-1])
+    nbytes = int(lib.mccnn_decision_pack_bytes(int(n_fc), units, int(mode)))
+    if nbytes == 0 or tuple(w.shape) != (n_fc - 1, units, units):
+        raise hip.MccnnHipError("mccnn_decision_pack: %d fc layers of %d units are outside the decision kernel's "
+                                "envelope (3 or 4 layers of %d units)" % (n_fc, units, DECISION_UNITS))
+    m = float(w.abs().max())
+    scale = 2.0 ** math.floor(math.log2(1024.0 / m)) if m > 0.0 and math.isfinite(m) else 1.0
+    packed = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
+    hip.check(lib.mccnn_decision_pack(hip.ptr(w), int(n_fc), units, scale, int(mode), hip.ptr(packed), hip.stream()),
+              "mccnn_decision_pack")
+    return packed, scale
+
+
+def cost_volume_fill(lcv, rcv, ndisp, pixel_major):
+    """The border recurrences (pf:94-95, 105-106) on volumes whose w >= d entries are written, in place."""
+    H, W = (lcv.shape[0], lcv.shape[1]) if pixel_major else (lcv.shape[1], lcv.shape[2])
+    hip.check(hip.load().mccnn_cost_volume_fill(hip.ptr(lcv), hip.ptr(rcv), int(ndisp), H, W, 1 if pixel_major else 0,
+                                                hip.stream()), "mccnn_cost_volume_fill")
+    return lcv, rcv
+
+
+def accurate_scores_library(net, aL, aR, ndisp, lcv, rcv, pixel_major, budget=DECISION_LIBRARY_BYTES):
+    """The decision network by torch matmuls, float32, on any device: writes -s(h,w,d) to lcv at (h,w,d) and rcv at
+    (h,w-d,d) for every w >= d (the other entries are left alone).  Disparity by disparity, in bands of image rows
+    sized so that one [voxels, units] intermediate stays under `budget` bytes."""
+    H, W, U = aL.shape
+    ws = [w.detach() for w in net.fc_weights]
+    bs = [b.detach() for b in net.fc_biases]
+    lv = lcv.permute(2, 0, 1) if pixel_major else lcv     # [d, h, w] views
+    rv = rcv.permute(2, 0, 1) if pixel_major else rcv
+    for d in range(int(ndisp)):
+        n = W - d
+        rows = max(1, min(H, int(budget) // (n * U * 4)))
+        for h0 in range(0, H, rows):
+            h1 = min(H, h0 + rows)
+            x = torch.relu(aL[h0:h1, d:, :] + aR[h0:h1, :n, :]).reshape(-1, U)
+            for k in range(1, net.num_fc_layers):
+                x = torch.relu(torch.addmm(bs[k], x, ws[k].t()))
+            z = torch.addmv(bs[-1].expand(x.shape[0]), x, ws[-1].reshape(-1))
+            s = torch.sigmoid(z).neg_().reshape(h1 - h0, n)
+            lv[d, h0:h1, d:] = s
+            rv[d, h0:h1, :n] = s
+    return lcv, rcv
+
+
+def cost_volume_accurate(net, fl, fr, ndisp, mode=hip.MCCNN_CV_EXACT, decision="kernel", pixel_major=True, out=None,
+                         halves=None, sat_flag=None, budget=DECISION_LIBRARY_BYTES):
+    """Both cost volumes of the accurate network from the tower outputs fl, fr [H,W,C]: lcv = -s at (h,w,d) for w >= d,
+    rcv = -s at (h,w-d,d), border columns by the fast network's recurrences (the same fill launch).
+    decision "kernel": csrc/decision_mfma.hip - mode MCCNN_CV_EXACT split operands (float32-accurate), MCCNN_CV_MFMA
+    plain f16; sat_flag as for conv3x3_split.  "library": torch matmuls in float32 (accurate_scores_library).
+    pixel_major: [H,W,Dp] volumes (else [D,H,W]); out: the two volumes; halves: the two [H,W,units] buffers of the
+    first layer's halves (allocated when None)."""
+    if decision not in ("kernel", "library"):
+        raise ValueError("decision must be 'kernel' or 'library'")
+    H, W, C = fl.shape
+    D = int(ndisp)
+    if out is None:
+        shape = (H, W, hwd_pitch(D)) if pixel_major else (D, H, W)
+        out = (torch.zeros(shape, dtype=torch.float32, device=fl.device),
+               torch.zeros(shape, dtype=torch.float32, device=fl.device))
+    lcv, rcv = out
+    why = decision_kernel_refusal(net, W, D) if decision == "kernel" else None
+    if why is not None:                       # before anything is launched
+        raise hip.MccnnHipError("cost_volume_accurate: %s" % why)
+    aL, aR = net.first_layer_halves(fl, fr, out=halves)
+    if decision == "library":
+        accurate_scores_library(net, aL, aR, D, lcv, rcv, pixel_major, budget)
+        return cost_volume_fill(lcv, rcv, D, pixel_major)
+    lib = hip.load()
+    packed, scale, biases, w_final, b_final = net.decision_operands(mode)
+    fn = lib.mccnn_cost_volume_accurate_hwd if pixel_major else lib.mccnn_cost_volume_accurate
+    hip.check(fn(hip.ptr(aL), hip.ptr(aR), H, W, C, net.num_fc_units, net.num_fc_layers, D, hip.ptr(packed),
+                 hip.ptr(biases), hip.ptr(w_final), b_final, scale, hip.ptr(lcv), hip.ptr(rcv), int(mode),
+                 hip.ptr(sat_flag) if sat_flag is not None else None, hip.stream()),
+              "mccnn_cost_volume_accurate_hwd" if pixel_major else "mccnn_cost_volume_accurate")
+    return lcv, rcv
+
+
 # ---- a0 ----------------------------------------------------------------------------------------------------------
 def ingest_scratch(H, W, device):
     """Scratch of one ingest call in flight (the chunk sums of both views): mccnn_ingest_scratch_bytes(H, W) bytes."""
@@ -886,6 +994,9 @@ DEFAULT_HP = dict(cbca_intensity=0.02, cbca_distance=14, cbca_num_iterations1=2,
 
 SGM_MAX_D = 1024               # mccnn_sgm_pass: four 256-disparity groups per lane
 COST_VOLUME_HWD_MAX_D = 1024   # mccnn_cost_volume_hwd (larger D: the plane-major volume + a layout change)
+# What decision="auto" runs where the decision kernel serves the pair (tools/bench_accurate.py, profiles/accurate.json:
+# the hand-written kernel is the default only while it is not slower than the library route)
+DECISION_AUTO = "kernel"
 
 
 def check_envelope(H, W, D):
@@ -900,12 +1011,14 @@ def check_envelope(H, W, D):
         raise ValueError("ndisp=%d needs an image at least ndisp + 2 = %d pixels wide, got W=%d" % (D, D + 2, W))
 
 
-def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flight=1):
+def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flight=1, arch="fast",
+                    fc_units=DECISION_UNITS):
     """Device bytes StereoMatcher.workspace(H, W, D) allocates, times `pairs_in_flight` (match.py --pairs_in_flight:
     one matcher per pair in flight): four volumes of H*W*Dp*4 bytes (Dp = hwd_pitch(D)), the SGM scratch and the flag
     planes of the four directions, both support planes, the status and map planes, and - on pixel-major volumes with
     cbca_kernel != "hwd" - the two aggregation program buffers where their programs encode the shape.  Not included:
-    the feature maps (2 x H*W*64*4 bytes while the cost volume is built) and the conv activations."""
+    the feature maps (2 x H*W*64*4 bytes while the cost volume is built) and the conv activations.
+    arch="accurate": plus the two [H,W,fc_units] float32 halves of the first fully-connected layer."""
     check_envelope(H, W, D)
     lib = hip.load()
     H, W, D = int(H), int(W), int(D)
@@ -916,6 +1029,10 @@ def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flig
     n += H * W * 4 + 6 * H * W * 4
     if pixel_major and cbca_kernel != "hwd":
         n += 2 * int(lib.mccnn_cbca_prog_bytes(D, H, W))
+    if arch not in ("fast", "accurate"):
+        raise ValueError("arch must be 'fast' or 'accurate'")
+    if arch == "accurate":
+        n += 2 * H * W * int(fc_units) * 4
     return n * max(1, int(pairs_in_flight))
 
 
@@ -931,7 +1048,9 @@ def _require_device_memory(nbytes, what):
 class StereoMatcher(object):
     """The timed region of match.py:129-179 for one stereo pair, resident on one GPU.
 
-    net: model.NET with weights loaded (kept resident; the reference re-restores per pair, pf:43).
+    net: model.NET with weights loaded (kept resident; the reference re-restores per pair, pf:43), or a
+    model.ACCURATE_NET: its cost volume comes from the decision network (cost_volume_accurate; `decision` selects the
+    hand-written kernel or the float32 library route, cv_mode the kernel's precision), every later stage is the same.
     cv_mode / cbca_order select the bit-exact (default, like process_functional and match.py) or the fast,
     tolerance-bounded variant of those two stages.  NOTE (round 3 on): the defaults are the bit-exact variants
     (MCCNN_CV_EXACT, MCCNN_CBCA_REFERENCE_ORDER: 13.7 ms per Middlebury-half pair); callers that relied on the
@@ -947,7 +1066,7 @@ class StereoMatcher(object):
     def __init__(self, net, hp=None, cv_mode=hip.MCCNN_CV_EXACT, cbca_order=hip.MCCNN_CBCA_REFERENCE_ORDER,
                  feature_tile_rows=None, extras=None, features="auto", layout="auto", cbca_kernel="auto",
                  on_saturation="fallback", skip_unit_regions=True, two_chains=True, free_chains=True, refresh_first=True,
-                 sgm_flags_once=True):
+                 sgm_flags_once=True, decision="auto"):
         self.device = hip.require_device()
         self.net = net
         self.hp = dict(DEFAULT_HP)
@@ -967,6 +1086,17 @@ class StereoMatcher(object):
         if features == "auto":
             features = "split_f16" if (feature_tile_rows is None and net.supports_split_features()) else "miopen"
         self.features = features
+        # An ACCURATE_NET (model.py) produces its cost volume with the decision network instead of the dot product;
+        # everything behind the cost volume is the same.  decision: "kernel" = csrc/decision_mfma.hip (cv_mode
+        # MCCNN_CV_EXACT: split operands, float32-accurate; MCCNN_CV_MFMA: plain f16), "library" = torch matmuls in
+        # float32, "auto" = DECISION_AUTO where the kernel serves the network and the shape, the library otherwise
+        # (with a warning that names the limit).  Ignored for the fast network.
+        if decision not in ("auto", "kernel", "library"):
+            raise ValueError("decision must be 'auto', 'kernel' or 'library'")
+        self.accurate = hasattr(net, "fc_weights")
+        self.decision = decision
+        if self.accurate and features == "split_f16":
+            raise ValueError("the split-operand feature kernels are built for the fast network")
         # "auto": the bit-exact variant runs on pixel-major volumes (pixel_major()); "plane_major" keeps every stage
         # on the reference's [D,H,W] layout (the round-2 kernels: cross-checks, and what the fast variant always uses)
         if layout not in ("auto", "plane_major"):
@@ -981,6 +1111,7 @@ class StereoMatcher(object):
             raise ValueError("on_saturation must be 'fallback', 'raise' or 'ignore'")
         self.on_saturation = on_saturation
         self._library_twin = None
+        self._decision_ran = None          # route of the last accurate cost volume: "kernel" raises the saturation flag
         # cbca_prog_pair's rule (iterations that leave unit-region pixels alone: same bits, fewer bytes); False runs the
         # full programs in every iteration - the content-independent cost of the aggregation (bench.py reports both)
         self.skip_unit_regions = bool(skip_unit_regions)
@@ -1026,11 +1157,26 @@ class StereoMatcher(object):
         """True when the split-operand feature kernels clamped an activation since the last reset (blocks the host)."""
         return self.net.split_saturated(reset)
 
+    def saturation_checked(self):
+        """True when the last pair ran a hand-written kernel that raises the saturation flag (the split-operand feature
+        kernels of the fast network, the decision kernel of the accurate one): features_saturated() then has news."""
+        return self.features == "split_f16" or (self.accurate and self._decision_ran == "kernel")
+
+    def saturation_notice(self):
+        """The sentence match.py prints when it repeats a pair whose saturation flag was raised: which kernel's range
+        was left and which library route takes the pair."""
+        if self.accurate:
+            return "activations left the matrix-core decision kernel's range: {} repeated on the float32 library decision route"
+        return ("activations left the matrix-core feature kernels' range: {} repeated with the float32 library "
+                "convolutions")
+
     def workspace(self, H, W, D):
         key = (H, W, D)
         ws = self._ws.get(key)
         if ws is None:
-            need = workspace_bytes(H, W, D, self.pixel_major(), self.workspace_cbca_kernel(H, W, D))
+            need = workspace_bytes(H, W, D, self.pixel_major(), self.workspace_cbca_kernel(H, W, D),
+                                   arch="accurate" if self.accurate else "fast",
+                                   fc_units=self.net.num_fc_units if self.accurate else DECISION_UNITS)
             self._ws, self._graphs = {}, {}          # one shape resident at a time: the previous one goes first
             _require_device_memory(need, "StereoMatcher: the workspace of a %dx%d pair with ndisp=%d" % (W, H, D))
             dp = hwd_pitch(D)
@@ -1044,6 +1190,9 @@ class StereoMatcher(object):
                 status=torch.empty((H, W), dtype=torch.int32, device=dev),
                 maps=torch.empty((6, H, W), dtype=torch.float32, device=dev),   # dl, dr, interp, subpixel, median, out
             )
+            if self.accurate:
+                ws["halves"] = tuple(torch.empty((H, W, self.net.num_fc_units), dtype=torch.float32, device=dev)
+                                     for _ in range(2))
             ws["progs"] = None
             # (distances above CBCA_HWD_MAX_DISTANCE: the aggregation programs do not encode such arms - the joined
             # two-volume path of mccnn_cbca_iter_hwd_long_pair runs, as for shapes the programs do not encode)
@@ -1076,17 +1225,19 @@ class StereoMatcher(object):
     def _saturated_pair(self, left_image, right_image, ndisp, out):
         """on_saturation for the pair that has just been launched: None when its features were fine (or nobody is to
         look), else the map of the same pair behind the float32 library convolutions (written to `out` if given)."""
-        if self.features != "split_f16" or self.on_saturation == "ignore" or torch.cuda.is_current_stream_capturing():
+        if not self.saturation_checked() or self.on_saturation == "ignore" or torch.cuda.is_current_stream_capturing():
             return None
         if not self.features_saturated():
             return None
         if self.on_saturation == "raise":
-            raise RuntimeError("StereoMatcher: an activation left the range of the split-operand feature kernels "
-                               "(|x| >= 255.9); match this pair with features='miopen'")
+            raise RuntimeError("StereoMatcher: an activation left the range of the split-operand %s "
+                               "(|x| >= 255.9); match this pair with %s" % (
+                                   ("decision kernel", "decision='library'") if self.accurate else
+                                   ("feature kernels", "features='miopen'")))
         if self._library_twin is None:
             self._library_twin = StereoMatcher(self.net, hp=self.hp, cv_mode=self.cv_mode, cbca_order=self.cbca_order,
                                                extras=self.extras, features="miopen", layout=self.layout,
-                                               cbca_kernel=self.cbca_kernel, on_saturation="ignore")
+                                               cbca_kernel=self.cbca_kernel, on_saturation="ignore", decision="library")
         return self._library_twin.match(left_image, right_image, ndisp, out=out)
 
     def match(self, left_image, right_image, ndisp, timer=_NO_TIMER, keep=None, _static_out=False, out=None):
@@ -1132,9 +1283,37 @@ class StereoMatcher(object):
             timer.stop()
         return sup_l, sup_r
 
-    def _cost_volumes(self, fl, fr, D, dhw, hwd, timer):
+    def decision_route(self, W, D):
+        """"kernel" or "library" for an accurate network's pair of this width and disparity range (class docstring of
+        __init__: decision).  "auto" falls back to the library, with a warning, where the kernel refuses."""
+        if self.decision == "library":
+            return "library"
+        why = decision_kernel_refusal(self.net, W, D)
+        if why is None:
+            return DECISION_AUTO if self.decision == "auto" else "kernel"
+        if self.decision == "kernel":
+            raise ValueError("decision='kernel': %s" % why)
+        import warnings
+        warnings.warn("accurate network: %s; the decision stage runs on the float32 library route" % why)
+        return "library"
+
+    def _cost_volumes_accurate(self, ws, fl, fr, D, dhw, hwd, timer):
+        """_cost_volumes for an ACCURATE_NET: the decision network on every (pixel, disparity) pair."""
+        direct = self.pixel_major() and D <= COST_VOLUME_HWD_MAX_D
+        route = self.decision_route(fl.shape[1], D)
+        self._decision_ran = route
+        timer.start("cost_volume")
+        left, right = cost_volume_accurate(self.net, fl, fr, D, mode=self.cv_mode, decision=route, pixel_major=direct,
+                                           out=(hwd[2], hwd[3]) if direct else (dhw[0], dhw[1]), halves=ws["halves"],
+                                           sat_flag=self.net._split_flag() if route == "kernel" else None)
+        timer.stop()
+        return left, right, direct
+
+    def _cost_volumes(self, fl, fr, D, dhw, hwd, timer, ws=None):
         """Returns (left, right, pixel_major): the bit-exact variant writes its cost volume pixel-major right away
         (nothing converts layouts after that) where the kernel serves D; everything else starts plane-major."""
+        if self.accurate:
+            return self._cost_volumes_accurate(ws, fl, fr, D, dhw, hwd, timer)
         direct = self.pixel_major() and D <= COST_VOLUME_HWD_MAX_D
         timer.start("cost_volume")
         if direct:
@@ -1325,7 +1504,7 @@ class StereoMatcher(object):
         timer.stop()
         if overlap:
             sup_l, sup_r, flag_planes, ready = self._side_work(ws, L, R, D, want_flags=free and self.sgm_flags_once)
-        lv, rv, pixel_major = self._cost_volumes(fl, fr, D, dhw, hwd, timer)
+        lv, rv, pixel_major = self._cost_volumes(fl, fr, D, dhw, hwd, timer, ws)
         del fl, fr
         if keep is not None:
             keep["cv"] = (hwd_to_dhw(lv, D), hwd_to_dhw(rv, D)) if pixel_major else (lv.clone(), rv.clone())

@@ -200,9 +200,31 @@ def load_fast_net_weights(checkpoint):
     return layers
 
 
-def save_npz(path, layers):
+def load_accurate_net_weights(checkpoint):
+    """Weights of the 'accurate' MC-CNN from an .npz: (conv layers as load_fast_net_weights returns them, fc layers as a
+    list of (weights [in,out], biases [out]) float32 pairs, fc1 .. fc<n_fc+1> - the last one is the 384 -> 1 layer)."""
+    if checkpoint is None or not str(checkpoint).endswith(".npz"):
+        raise ValueError("the accurate network's checkpoints are .npz files, got %r" % (checkpoint,))
+    blob = dict(np.load(checkpoint))
+    fc = []
+    k = 1
+    while "fc%d/weights" % k in blob:
+        fc.append((np.ascontiguousarray(blob["fc%d/weights" % k], dtype=np.float32),
+                   np.ascontiguousarray(blob["fc%d/biases" % k], dtype=np.float32)))
+        k += 1
+    if not fc:
+        raise ValueError("checkpoint %r holds no fc<k>/weights variables: it is not an accurate-network checkpoint"
+                         % checkpoint)
+    return load_fast_net_weights(checkpoint), fc
+
+
+def save_npz(path, layers, fc_layers=None):
+    """conv{k}/weights (HWIO), conv{k}/biases; with fc_layers also fc{k}/weights [in,out], fc{k}/biases."""
     blob = {}
     for k, (w, b) in enumerate(layers, start=1):
         blob["conv%d/weights" % k] = w
         blob["conv%d/biases" % k] = b
+    for k, (w, b) in enumerate(fc_layers or (), start=1):
+        blob["fc%d/weights" % k] = w
+        blob["fc%d/biases" % k] = b
     np.savez(path, **blob)

@@ -51,3 +51,14 @@ def fast_violations(pixels, flips_left, flips_right, frac_within_1e3, p99_abs_px
     if p99_abs_px > FAST_P99_ABS_PX:
         bad.append("99th percentile %.4f px (stated: <= %.2f)" % (p99_abs_px, FAST_P99_ABS_PX))
     return bad
+
+
+# ---- accurate network (decision stage, csrc/decision_mfma.hip) ---------------------------------------------------------
+# Scores s in (0,1) against a float64 evaluation of the decision network.  The bounds are multiples of errors the tests
+# compute on the same inputs, not numbers taken from the kernel:
+#   E32 = max error of a float32 torch-CPU evaluation, E16 = max error of a float64 evaluation whose weights and every
+#   layer's input activations are rounded to f16.
+ACCURATE_SCORE_ABS = 1e-5           # ACCURATE_NET's float32 torch forward (patch batches) vs float64: FEATURES_ABS's class
+ACCURATE_SPLIT_E32_FACTOR = 4       # default precision: <= 4 x E32 (a split operand carries 22 significand bits, float32 24)
+ACCURATE_F16_E16_FACTOR = 2         # f16 precision: <= 2 x E16 + 4 x E32 (float32 accumulation can move an activation
+                                    # across an f16 rounding boundary: twice the half-spacing error of the emulation)

@@ -52,6 +52,12 @@ parser.add_argument("--print_freq", type=int, default=10, help="log the training
 parser.add_argument("--save_freq", type=int, default=1, help="write a checkpoint every this many epochs")
 parser.add_argument("--val_freq", type=int, default=1, help="validate every this many epochs")
 parser.add_argument("--seed", type=int, default=0, help="seed of the weight initialisation and the patch sampler")
+parser.add_argument("--arch", choices=("fast", "accurate"), default="fast",
+                    help="'fast': the reference's network and hinge loss; 'accurate': the paper's other network (112-map "
+                         "tower, fully-connected decision network, sigmoid) trained with binary cross-entropy on the same "
+                         "triplets - (left, right+) -> 1, (left, right-) -> 0; scalars bce_loss / val_bce_loss")
+parser.add_argument("--num_fc_layers", type=int, default=3,
+                    help="with --arch accurate: hidden fully-connected layers (Middlebury 3, KITTI 4)")
 
 
 def hinge_loss(features, batch_size, margin):
@@ -60,6 +66,16 @@ def hinge_loss(features, batch_size, margin):
     cosine_pos = (f[0] * f[1]).sum(dim=-1)
     cosine_neg = (f[0] * f[2]).sum(dim=-1)
     return (margin - cosine_pos + cosine_neg).clamp(min=0.0).mean()
+
+
+def bce_loss(logits_pos, logits_neg):
+    """Binary cross-entropy of the accurate network (paper sec. 3.2): the mean of -log s over the (left, right+) pairs
+    and -log(1 - s) over the (left, right-) pairs, s = sigmoid(logit), evaluated on the logits."""
+    import torch
+    import torch.nn.functional as F
+    logits = torch.cat((logits_pos, logits_neg))
+    target = torch.cat((torch.ones_like(logits_pos), torch.zeros_like(logits_neg)))
+    return F.binary_cross_entropy_with_logits(logits, target)
 
 
 class Trainer(object):
@@ -74,12 +90,22 @@ class Trainer(object):
             net.weights[k] = torch.nn.Parameter(net.weights[k].clone())
             net.biases[k] = torch.nn.Parameter(net.biases[k].clone())
             self.params += [net.weights[k], net.biases[k]]
+        self.accurate = hasattr(net, "fc_weights")     # model.ACCURATE_NET: BCE on the decision network's logits
+        if self.accurate:
+            for k in range(len(net.fc_weights)):
+                net.fc_weights[k] = torch.nn.Parameter(net.fc_weights[k].clone())
+                net.fc_biases[k] = torch.nn.Parameter(net.fc_biases[k].clone())
+                self.params += [net.fc_weights[k], net.fc_biases[k]]
         self.opt = torch.optim.SGD(self.params, lr=learning_rate, momentum=beta, dampening=0.0, nesterov=False)
         self.margin = margin
 
     def loss(self, batch_left, batch_right_pos, batch_right_neg):
         import torch
         x = torch.from_numpy(np.concatenate([batch_left, batch_right_pos, batch_right_neg], axis=0)).to(self.net.device)
+        if self.accurate:
+            B = batch_left.shape[0]
+            f = self.net(x).reshape(3, B, -1)        # the three weight-shared towers as one batch
+            return bce_loss(self.net.decision_logits(f[0], f[1]), self.net.decision_logits(f[0], f[2]))
         return hinge_loss(self.net(x), batch_left.shape[0], self.margin)
 
     def step(self, batch_left, batch_right_pos, batch_right_neg):
@@ -106,6 +132,16 @@ class Trainer(object):
                 if buf is not None:
                     a = buf.detach().cpu().numpy()
                     out["conv%d/%s/Momentum" % (k + 1, name)] = np.transpose(a, (2, 3, 1, 0)) if a.ndim == 4 else a
+        if self.accurate:
+            for k, (w, b) in enumerate(self.net.get_fc_layers(), start=1):
+                out["fc%d/weights" % k] = w
+                out["fc%d/biases" % k] = b
+            for k in range(len(self.net.fc_weights)):
+                for name, p in (("weights", self.net.fc_weights[k]), ("biases", self.net.fc_biases[k])):
+                    buf = self.opt.state.get(p, {}).get("momentum_buffer")
+                    if buf is not None:
+                        a = buf.detach().cpu().numpy()
+                        out["fc%d/%s/Momentum" % (k + 1, name)] = a.T if a.ndim == 2 else a
         return out
 
     def load_state(self, path):
@@ -131,6 +167,18 @@ class Trainer(object):
                 if a is not None:
                     a = np.transpose(a, (3, 2, 0, 1)) if a.ndim == 4 else a
                     self.opt.state[p]["momentum_buffer"] = torch.from_numpy(np.ascontiguousarray(a)).to(p.device)
+        if self.accurate:
+            _conv, fc = tf_checkpoint.load_accurate_net_weights(path)
+            with torch.no_grad():
+                for k, (w, b) in enumerate(fc):
+                    self.net.fc_weights[k].copy_(torch.from_numpy(np.ascontiguousarray(w.T)))
+                    self.net.fc_biases[k].copy_(torch.from_numpy(np.ascontiguousarray(b)))
+            for k in range(len(self.net.fc_weights)):
+                for name, p in (("weights", self.net.fc_weights[k]), ("biases", self.net.fc_biases[k])):
+                    a = slots.get("fc%d/%s/Momentum" % (k + 1, name))
+                    if a is not None:
+                        a = a.T if a.ndim == 2 else a
+                        self.opt.state[p]["momentum_buffer"] = torch.from_numpy(np.ascontiguousarray(a)).to(p.device)
 
 
 def main(argv=None):
@@ -143,7 +191,7 @@ def main(argv=None):
     import torch
     import distributed as mgpu
     from datagenerator import ImageDataGenerator
-    from model import NET
+    from model import ACCURATE_NET, NET
 
     on_gpu = torch.cuda.is_available()
     if on_gpu:
@@ -161,8 +209,13 @@ def main(argv=None):
     train_batches_per_epoch = train_generator.data_size
     val_batches_per_epoch = val_generator.data_size
 
-    net = NET(None, input_patch_size=args.patch_size, num_conv_layers=(args.patch_size - 1) // 2,
-              batch_size=args.batch_size, device=device, seed=args.seed)
+    if args.arch == "accurate":
+        net = ACCURATE_NET(None, input_patch_size=args.patch_size, num_conv_layers=(args.patch_size - 1) // 2,
+                           batch_size=args.batch_size, device=device, seed=args.seed, num_fc_layers=args.num_fc_layers)
+    else:
+        net = NET(None, input_patch_size=args.patch_size, num_conv_layers=(args.patch_size - 1) // 2,
+                  batch_size=args.batch_size, device=device, seed=args.seed)
+    loss_tag = "bce_loss" if args.arch == "accurate" else "hinge_loss"
     trainer = Trainer(net, args.learning_rate, args.beta, args.margin)
     if args.resume is not None:
         trainer.load_state(args.resume)
@@ -179,7 +232,7 @@ def main(argv=None):
         for batch in range(train_batches_per_epoch):
             loss = trainer.step(*train_generator.next_batch(args.batch_size))
             if (batch + 1) % args.print_freq == 0:
-                scalar("hinge_loss", loss, epoch * train_batches_per_epoch + batch)        # train.py:169-173
+                scalar(loss_tag, loss, epoch * train_batches_per_epoch + batch)        # train.py:169-173
         if (epoch + 1) % args.save_freq == 0 and rank == 0:
             name = os.path.join(args.checkpoint_dir, "model_epoch" + str(epoch + 1) + ".ckpt.npz")
             np.savez(name, **trainer.state())
@@ -189,7 +242,7 @@ def main(argv=None):
                 val_ls = sum(float(trainer.loss(*val_generator.next_batch(args.batch_size)))
                              for _ in range(val_batches_per_epoch)) / (1. * max(val_batches_per_epoch, 1))
             print("[{}] {}: epoch {} validation loss: {}".format(rank, datetime.now(), epoch + 1, val_ls))
-            scalar("val_hinge_loss", val_ls, train_batches_per_epoch * (epoch + 1))        # train.py:196-197
+            scalar("val_" + loss_tag, val_ls, train_batches_per_epoch * (epoch + 1))        # train.py:196-197
         val_generator.reset_pointer()
         train_generator.reset_pointer()
     if log is not None:
