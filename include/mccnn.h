@@ -325,6 +325,26 @@ int mccnn_sgm_flags(const float *image_left, const float *image_right, int D, in
 int mccnn_sgm_pass_flagged(float *const *vol_hwd, const int *side, int n_jobs, int D, int H, int W, int rh, int rw, float p1,
                            float p2, float q1, float q2, const void *flags, size_t flags_bytes, mccnn_stream_t stream);
 
+/* The out-of-place, accumulating form of the pass: the paper's SGM, C_SGM = 1/4 sum_r L_r with every L_r computed from
+ * the SAME volume (the reference's SGM_average composes its four passes on one aliased array instead, pf:195-210; see
+ * StereoMatcher's extra sgm_independent_directions).  Job j reads its costs from src_hwd[j], which is never written,
+ * runs the recurrence of mccnn_sgm_pass along r in registers, and combines every line of L - the first line of the
+ * scan axis, where L = C, included - with acc_hwd[j] (same [H,W,Dp] layout):
+ *   MCCNN_SGM_ACC_STORE        acc  = L                       (what acc held is not read)
+ *   MCCNN_SGM_ACC_ADD          acc  = acc + L                 float32
+ *   MCCNN_SGM_ACC_ADD_QUARTER  acc  = (acc + L) / 4.f         float32, correctly rounded
+ * so store, add, add, add-and-quarter over the reference's four directions give (((L0 + L1) + L2) + L3) / 4.  An axis
+ * with a single line contributes L = C.  flags: mccnn_sgm_flags for the same H, W, D and r.  Refused (MCCNN_E_INVALID):
+ * null pointers, an unknown mode, an r that is not an axis-aligned unit step, and any overlap between an accumulator and
+ * a source or another accumulator; 2 <= D <= 1024 (MCCNN_E_UNSUPPORTED), flags_bytes >= mccnn_sgm_scratch_bytes
+ * (MCCNN_E_SCRATCH).  Every route of mccnn_sgm_pass, vertical scanlines of volumes of 4 GiB or more included. */
+#define MCCNN_SGM_ACC_STORE 0
+#define MCCNN_SGM_ACC_ADD 1
+#define MCCNN_SGM_ACC_ADD_QUARTER 2
+int mccnn_sgm_pass_accumulate(const float *const *src_hwd, float *const *acc_hwd, const int *side, int n_jobs, int D, int H,
+                              int W, int rh, int rw, float p1, float p2, float q1, float q2, int mode, const void *flags,
+                              size_t flags_bytes, mccnn_stream_t stream);
+
 /* The first direction of SGM_average, r = (0,1) (pf:194-195, 216-217), fused with the layout change: reads the
  * plane-major volumes vol_dhw[j] (left untouched) and writes the pixel-major vol_hwd[j], i.e. it replaces
  * mccnn_dhw_to_hwd + mccnn_sgm_pass(rh=0, rw=1) and saves one full read + write of every volume.  2 <= D <= 256.

@@ -136,13 +136,52 @@ template <int VPL> struct SgmVec {
 // touches: the PF steps it stores and the PF steps it prefetches (2 PF - 1 lines: at most 150 MB at W = 3072).
 // The per-lane voffset and the wave-uniform soffset stay 32-bit; soffset counts from the window's lowest scan position
 // (the descending direction's window starts at pos(tb)).  Loads in flight keep the descriptor they were issued with.
-template <int NG, int PF, bool FULL, int VPL = 4, bool FAR = false>
-__global__ __launch_bounds__(64) void sgm_pass_kernel(const SgmParams P)
+//
+// ACC != 0: the out-of-place, accumulating form (mccnn_sgm_pass_accumulate; the paper's four independent directions,
+// C_SGM = 1/4 sum_r L_r).  The costs come from a read-only source volume, the running L stays in registers exactly as
+// above, and every line of the scan - the seed line, which the pass leaves as it is, included - is combined with an
+// accumulator volume of the same layout: ACC = 1 stores L, ACC = 2 writes (acc + L) * scale with scale = 1 (add) or
+// 1/4 (add and quarter; x * 0.25f is x / 4.f correctly rounded, and x * 1.f is x for every x the contract admits).  The
+// accumulator vector of a step is prefetched with the step's costs (4 more VGPRs per group and step in flight).  FAR
+// rebases two descriptors, which share every offset because the two volumes share their layout.
+struct SgmAccJob {
+    const float *src;       // HWD volume the costs are read from (never written)
+    float *acc;             // HWD accumulator
+    const uint8_t *aplane;
+    const uint8_t *bplane;
+    int dsign;
+};
+struct SgmAccParams {
+    SgmAccJob job[2];
+    int D, Dp, H, W, pitch, pad, rh, rw;
+    float p1[3], p2[3];
+    float scale;            // ACC = 2: 1 or 1/4
+};
+__device__ __forceinline__ float *sgm_cost_volume(const SgmJob &J) { return J.vol; }
+__device__ __forceinline__ float *sgm_cost_volume(const SgmAccJob &J) { return const_cast<float *>(J.src); }
+__device__ __forceinline__ float *sgm_acc_volume(const SgmJob &J) { return J.vol; }
+__device__ __forceinline__ float *sgm_acc_volume(const SgmAccJob &J) { return J.acc; }
+__device__ __forceinline__ float sgm_acc_scale(const SgmParams &) { return 1.f; }
+__device__ __forceinline__ float sgm_acc_scale(const SgmAccParams &P) { return P.scale; }
+// Cache policy of the accumulating passes' source loads (SGM_ACC_SRC_AUX): the source is read by four passes, but a
+// pass still touches every voxel once and the next pass returns to it after the whole volume (384 MB at 750x500x256)
+// has gone by, more than any cache level holds; the accumulator's load and store are read-once / write-once like the
+// in-place traffic.  Both keep the non-temporal hint.
+#ifndef SGM_ACC_SRC_AUX
+#define SGM_ACC_SRC_AUX 2
+#endif
+
+template <int NG, int PF, bool FULL, int VPL = 4, bool FAR = false, int ACC = 0, typename Params = SgmParams>
+__global__ __launch_bounds__(64) void sgm_pass_kernel(const Params P)
 {
+    static_assert(ACC == 0 || ACC == 1 || ACC == 2, "in place, store, or add");
     static_assert(VPL == 4 || (VPL == 3 && NG == 1), "three disparities per lane: one group only");
     static_assert(!FAR || VPL == 4, "far scanlines: four disparities per lane");
     typedef SgmVec<VPL> vec;
-    const SgmJob J = P.job[blockIdx.y];
+    constexpr int kSrcAux = ACC ? SGM_ACC_SRC_AUX : kNT;
+    const auto J = P.job[blockIdx.y];
+    float *const vol_base = sgm_cost_volume(J);
+    [[maybe_unused]] float *const acc_base = sgm_acc_volume(J);
     const int lane = threadIdx.x;
     const int line = blockIdx.x;
     const bool horiz = P.rh == 0;
@@ -155,13 +194,19 @@ __global__ __launch_bounds__(64) void sgm_pass_kernel(const SgmParams P)
     const size_t line_pix = horiz ? (size_t)line * P.W : (size_t)line;              // pixel at scan position 0
     const size_t line_flag = horiz ? (size_t)line * P.pitch + P.pad : (size_t)P.pad + line;
     const unsigned span = FAR ? 0u : (unsigned)min((size_t)0xFFFFFFFFu, (size_t)nsteps * vstride + (size_t)P.Dp * 4u);
-    __amdgpu_buffer_rsrc_t rs_vol = __builtin_amdgcn_make_buffer_rsrc(J.vol + line_pix * P.Dp, 0, (int)span, 0x00020000);
+    __amdgpu_buffer_rsrc_t rs_vol = __builtin_amdgcn_make_buffer_rsrc(vol_base + line_pix * P.Dp, 0, (int)span, 0x00020000);
+    [[maybe_unused]] __amdgpu_buffer_rsrc_t rs_acc = rs_vol;   // ACC: the accumulator, same offsets as rs_vol
+    if constexpr (ACC != 0)
+        rs_acc = __builtin_amdgcn_make_buffer_rsrc(acc_base + line_pix * P.Dp, 0, (int)span, 0x00020000);
     unsigned vlo = 0;   // FAR: scan position at the base of rs_vol
     auto window = [&](int ta, int tb) {   // FAR: rs_vol over the scan positions of steps ta <= tb
         vlo = (unsigned)(fwd ? ta : nsteps - tb);
         const size_t pstride = horiz ? (size_t)P.Dp : (size_t)P.W * P.Dp;   // floats between scan positions
-        rs_vol = __builtin_amdgcn_make_buffer_rsrc(J.vol + line_pix * P.Dp + vlo * pstride, 0,
+        rs_vol = __builtin_amdgcn_make_buffer_rsrc(vol_base + line_pix * P.Dp + vlo * pstride, 0,
                                                    (int)((unsigned)(tb - ta) * vstride + (unsigned)P.Dp * 4u), 0x00020000);
+        if constexpr (ACC != 0)
+            rs_acc = __builtin_amdgcn_make_buffer_rsrc(acc_base + line_pix * P.Dp + vlo * pstride, 0,
+                                                       (int)((unsigned)(tb - ta) * vstride + (unsigned)P.Dp * 4u), 0x00020000);
     };
     const unsigned fspan = (unsigned)((size_t)nsteps * fstride + 1u);
     // the B lookups reach up to pad bytes to either side of the pixel: base the descriptor pad bytes early
@@ -210,19 +255,63 @@ __global__ __launch_bounds__(64) void sgm_pass_kernel(const SgmParams P)
     auto load_vol = [&](int g, int t) {
         vec r;
         if constexpr (VPL == 4) {
-            const sgm_u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(rs_vol, voff[g], soff(t), kNT);
+            const sgm_u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(rs_vol, voff[g], soff(t), kSrcAux);
             r.v[0] = __uint_as_float(u.x); r.v[1] = __uint_as_float(u.y); r.v[2] = __uint_as_float(u.z); r.v[3] = __uint_as_float(u.w);
         } else {
-            const sgm_u32x3 u = __builtin_amdgcn_raw_buffer_load_b96(rs_vol, voff[g], soff(t), kNT);
+            const sgm_u32x3 u = __builtin_amdgcn_raw_buffer_load_b96(rs_vol, voff[g], soff(t), kSrcAux);
             r.v[0] = __uint_as_float(u.x); r.v[1] = __uint_as_float(u.y); r.v[2] = __uint_as_float(u.z);
         }
         return r;
     };
+    [[maybe_unused]] auto load_acc = [&](int g, int t) {
+        vec r;
+        if constexpr (VPL == 4) {
+            const sgm_u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(rs_acc, voff[g], soff(t), kNT);
+            r.v[0] = __uint_as_float(u.x); r.v[1] = __uint_as_float(u.y); r.v[2] = __uint_as_float(u.z); r.v[3] = __uint_as_float(u.w);
+        } else {
+            const sgm_u32x3 u = __builtin_amdgcn_raw_buffer_load_b96(rs_acc, voff[g], soff(t), kNT);
+            r.v[0] = __uint_as_float(u.x); r.v[1] = __uint_as_float(u.y); r.v[2] = __uint_as_float(u.z);
+        }
+        return r;
+    };
+    // ACC: line t of the accumulator <- L (ACC = 1) or (what it holds + L) * scale (ACC = 2; `had` = what it holds)
+    [[maybe_unused]] const float scale = sgm_acc_scale(P);
+    [[maybe_unused]] auto store_acc = [&](int g, int t, const vec &l, const vec &had) {
+        vec o = l;
+        if constexpr (ACC == 2) {
+#pragma unroll
+            for (int j = 0; j < VPL; ++j) {
+                const float sum = had.v[j] + l.v[j];
+                o.v[j] = sum * scale;
+            }
+        }
+        if constexpr (VPL == 4) {
+            sgm_u32x4 ou;
+            ou.x = __float_as_uint(o.v[0]); ou.y = __float_as_uint(o.v[1]);
+            ou.z = __float_as_uint(o.v[2]); ou.w = __float_as_uint(o.v[3]);
+            buffer_store_b128<kNT>(ou, rs_acc, voff[g], soff(t));
+        } else {
+            sgm_u32x3 ou;
+            ou.x = __float_as_uint(o.v[0]); ou.y = __float_as_uint(o.v[1]); ou.z = __float_as_uint(o.v[2]);
+            buffer_store_b96<kNT>(ou, rs_acc, voff[g], soff(t));
+        }
+    };
 
     if constexpr (FAR) window(0, min(PF, nsteps));   // the seed line and the first PF steps
     vec prev[NG];
+    if constexpr (ACC != 0) {   // the seed line enters the sum like any other: L = C there
 #pragma unroll
-    for (int g = 0; g < NG; ++g) prev[g] = mask_tail(load_vol(g, 0), g);
+        for (int g = 0; g < NG; ++g) {
+            const vec c0 = load_vol(g, 0);
+            vec had = c0;
+            if constexpr (ACC == 2) had = load_acc(g, 0);
+            store_acc(g, 0, c0, had);
+            prev[g] = mask_tail(c0, g);
+        }
+    } else {
+#pragma unroll
+        for (int g = 0; g < NG; ++g) prev[g] = mask_tail(load_vol(g, 0), g);
+    }
     float m;
     {
         float lm = kInf;
@@ -232,6 +321,7 @@ __global__ __launch_bounds__(64) void sgm_pass_kernel(const SgmParams P)
     }
 
     vec cbuf[PF][NG];
+    [[maybe_unused]] vec hbuf[ACC == 2 ? PF : 1][NG];   // ACC = 2: the accumulator's vectors of the steps in flight
     uint32_t fbuf[PF][NG];
     uint32_t abuf[PF];
     auto issue = [&](int slot, int t) {
@@ -240,6 +330,7 @@ __global__ __launch_bounds__(64) void sgm_pass_kernel(const SgmParams P)
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
             cbuf[slot][g] = load_vol(g, t);
+            if constexpr (ACC == 2) hbuf[slot][g] = load_acc(g, t);
             fbuf[slot][g] = __builtin_amdgcn_raw_buffer_load_b32(rs_b, boff[g], fo, 0);
         }
     };
@@ -284,7 +375,9 @@ __global__ __launch_bounds__(64) void sgm_pass_kernel(const SgmParams P)
                     o.v[j] = sum - m;
                 }
                 nw[g] = o;
-                if constexpr (VPL == 4) {
+                if constexpr (ACC != 0) {
+                    store_acc(g, t, o, hbuf[ACC == 2 ? k : 0][g]);
+                } else if constexpr (VPL == 4) {
                     sgm_u32x4 ou;
                     ou.x = __float_as_uint(o.v[0]); ou.y = __float_as_uint(o.v[1]);
                     ou.z = __float_as_uint(o.v[2]); ou.w = __float_as_uint(o.v[3]);
@@ -755,6 +848,144 @@ extern "C" int mccnn_sgm_pass_flagged(float *const *vol_hwd, const int *side, in
 {
     return sgm_launch_pass("mccnn_sgm_pass_flagged", vol_hwd, side, n_jobs, D, H, W, rh, rw, p1, p2, q1, q2, flags,
                            flags_bytes, (hipStream_t)stream);
+}
+
+// ---- the out-of-place, accumulating pass (the paper's four independent directions) -------------------------------
+// Steps in flight of the accumulating kernels.  The store form (ACC = 1) holds what the in-place kernel holds and keeps
+// its depths; the add form (ACC = 2) holds one more 16-byte vector per group and step and runs at two thirds of those
+// depths (three quarters at D = 256): at least as many 16-byte loads in flight per wave as the in-place kernel has, no
+// scratch, 2-3 waves per SIMD by -Rpass-analysis=kernel-resource-usage (the table in DESIGN 4.1).
+#ifndef SGM_ACC_PF_FULL
+#define SGM_ACC_PF_FULL 12
+#endif
+#ifndef SGM_ACC_PF_PARTIAL
+#define SGM_ACC_PF_PARTIAL 16
+#endif
+#ifndef SGM_ACC_PF_2G
+#define SGM_ACC_PF_2G 8
+#endif
+#ifndef SGM_ACC_PF_3G
+#define SGM_ACC_PF_3G 5
+#endif
+#ifndef SGM_ACC_PF_4G
+#define SGM_ACC_PF_4G 4
+#endif
+
+namespace mccnn {
+// One route of the table below in the form the mode asks for: PFS steps in flight for the store form, PFA for the add form.
+template <int NG, int PFS, int PFA, bool FULL, int VPL, bool FAR>
+static void sgm_acc_launch(int mode, dim3 grid, hipStream_t s, const SgmAccParams &P)
+{
+    if (mode == MCCNN_SGM_ACC_STORE)
+        hipLaunchKernelGGL((sgm_pass_kernel<NG, PFS, FULL, VPL, FAR, 1, SgmAccParams>), grid, dim3(64), 0, s, P);
+    else
+        hipLaunchKernelGGL((sgm_pass_kernel<NG, PFA, FULL, VPL, FAR, 2, SgmAccParams>), grid, dim3(64), 0, s, P);
+}
+
+static bool sgm_overlap(const void *a, const void *b, size_t bytes)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + bytes && y < x + bytes;
+}
+}  // namespace mccnn
+
+extern "C" int mccnn_sgm_pass_accumulate(const float *const *src_hwd, float *const *acc_hwd, const int *side, int n_jobs,
+                                         int D, int H, int W, int rh, int rw, float p1, float p2, float q1, float q2,
+                                         int mode, const void *flags, size_t flags_bytes, mccnn_stream_t stream)
+{
+    using namespace mccnn;
+    const char *who = "mccnn_sgm_pass_accumulate";
+    hipStream_t s = (hipStream_t)stream;
+    MCCNN_REQUIRE(src_hwd && acc_hwd && side && flags, MCCNN_E_INVALID, "%s: null pointer", who);
+    MCCNN_REQUIRE(n_jobs == 1 || n_jobs == 2, MCCNN_E_INVALID, "%s: n_jobs=%d must be 1 or 2", who, n_jobs);
+    MCCNN_REQUIRE(mode == MCCNN_SGM_ACC_STORE || mode == MCCNN_SGM_ACC_ADD || mode == MCCNN_SGM_ACC_ADD_QUARTER,
+                  MCCNN_E_INVALID, "%s: mode=%d is not MCCNN_SGM_ACC_STORE, _ADD or _ADD_QUARTER", who, mode);
+    MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "%s: non-positive size", who);
+    MCCNN_REQUIRE(D >= 2 && D <= kSgmMaxD, MCCNN_E_UNSUPPORTED,
+                  "%s: D=%d outside [2,%d] (the reference itself needs D >= 2, pf:550)", who, D, kSgmMaxD);
+    MCCNN_REQUIRE((rh == 0 && (rw == 1 || rw == -1)) || (rw == 0 && (rh == 1 || rh == -1)), MCCNN_E_INVALID,
+                  "%s: r=(%d,%d) is not an axis-aligned unit step (pf:484)", who, rh, rw);
+    MCCNN_REQUIRE(flags_bytes >= mccnn_sgm_scratch_bytes(H, W, D), MCCNN_E_SCRATCH, "%s: scratch %zu < %zu bytes", who,
+                  flags_bytes, mccnn_sgm_scratch_bytes(H, W, D));
+    const int pad = flag_pad(D);
+    const int pitch = W + 2 * pad;
+    const int Dp = mccnn_hwd_pitch(D);
+    const size_t vol_bytes = (size_t)H * W * Dp * 4;
+    const uint8_t *plane_l = reinterpret_cast<const uint8_t *>(flags);
+    const uint8_t *plane_r = plane_l + (((size_t)H * pitch + 127) & ~(size_t)127);
+    for (int j = 0; j < n_jobs; ++j) {
+        MCCNN_REQUIRE(src_hwd[j] != nullptr && acc_hwd[j] != nullptr, MCCNN_E_INVALID, "%s: null volume", who);
+        MCCNN_REQUIRE(side[j] == MCCNN_SIDE_LEFT || side[j] == MCCNN_SIDE_RIGHT, MCCNN_E_INVALID,
+                      "%s: side must be MCCNN_SIDE_LEFT or MCCNN_SIDE_RIGHT", who);
+    }
+    // the pass reads a source line long after it has written other lines of the accumulator: the two never share memory
+    for (int j = 0; j < n_jobs; ++j) {
+        for (int k = 0; k < n_jobs; ++k)
+            MCCNN_REQUIRE(!sgm_overlap(src_hwd[k], acc_hwd[j], vol_bytes), MCCNN_E_INVALID,
+                          "%s: accumulator %d overlaps source %d (the pass is out of place)", who, j, k);
+        for (int k = 0; k < j; ++k)
+            MCCNN_REQUIRE(!sgm_overlap(acc_hwd[k], acc_hwd[j], vol_bytes), MCCNN_E_INVALID,
+                          "%s: accumulators %d and %d overlap", who, k, j);
+    }
+    SgmAccParams P;
+    for (int j = 0; j < 2; ++j) {
+        const int jj = j < n_jobs ? j : 0;
+        const bool left = side[jj] == MCCNN_SIDE_LEFT;
+        P.job[j].src = src_hwd[jj];
+        P.job[j].acc = acc_hwd[jj];
+        P.job[j].aplane = left ? plane_l : plane_r;
+        P.job[j].bplane = left ? plane_r : plane_l;
+        P.job[j].dsign = left ? -1 : +1;
+    }
+    P.D = D; P.Dp = Dp; P.H = H; P.W = W; P.pitch = pitch; P.pad = pad; P.rh = rh; P.rw = rw;
+    P.p1[0] = p1; P.p1[1] = p1 / q1; P.p1[2] = p1 / q2;  // pf:538-541 (float32 divisions)
+    P.p2[0] = p2; P.p2[1] = p2 / q1; P.p2[2] = p2 / q2;
+    P.scale = mode == MCCNN_SGM_ACC_ADD_QUARTER ? 0.25f : 1.f;
+    // (an axis with nothing to scan still launches: its single line is the seed line, and L = C enters the sum)
+    const dim3 grid(rh == 0 ? H : W, n_jobs);
+    // the routes of mccnn_sgm_pass (sgm_launch_pass), each in the form `mode` selects
+    if (rh != 0 && vol_bytes >= ((size_t)1 << 32)) {
+        const int ng = cdiv(Dp, 256);
+        const bool full = D == 256 * ng;
+        if (ng == 1 && full)
+            sgm_acc_launch<1, 16, SGM_ACC_PF_FULL, true, 4, true>(mode, grid, s, P);
+        else if (ng == 1)
+            sgm_acc_launch<1, SGM_PF_PARTIAL, SGM_ACC_PF_PARTIAL, false, 4, true>(mode, grid, s, P);
+        else if (ng == 2 && full)
+            sgm_acc_launch<2, SGM_PF_2G, SGM_ACC_PF_2G, true, 4, true>(mode, grid, s, P);
+        else if (ng == 2)
+            sgm_acc_launch<2, SGM_PF_2G, SGM_ACC_PF_2G, false, 4, true>(mode, grid, s, P);
+        else if (ng == 3 && full)
+            sgm_acc_launch<3, SGM_PF_3G, SGM_ACC_PF_3G, true, 4, true>(mode, grid, s, P);
+        else if (ng == 3)
+            sgm_acc_launch<3, SGM_PF_3G, SGM_ACC_PF_3G, false, 4, true>(mode, grid, s, P);
+        else if (full)
+            sgm_acc_launch<4, SGM_PF_4G, SGM_ACC_PF_4G, true, 4, true>(mode, grid, s, P);
+        else
+            sgm_acc_launch<4, SGM_PF_4G, SGM_ACC_PF_4G, false, 4, true>(mode, grid, s, P);
+        return check_launch(who);
+    }
+    if (D == 256)
+        sgm_acc_launch<1, 16, SGM_ACC_PF_FULL, true, 4, false>(mode, grid, s, P);
+    else if (D == 192)
+        sgm_acc_launch<1, SGM_PF_PARTIAL, SGM_ACC_PF_PARTIAL, true, 3, false>(mode, grid, s, P);
+    else if (D > 128 && D < 192 && Dp % 3 == 0)
+        sgm_acc_launch<1, SGM_PF_PARTIAL, SGM_ACC_PF_PARTIAL, false, 3, false>(mode, grid, s, P);
+    else if (D < 256)
+        sgm_acc_launch<1, SGM_PF_PARTIAL, SGM_ACC_PF_PARTIAL, false, 4, false>(mode, grid, s, P);
+    else if (D == 512)
+        sgm_acc_launch<2, SGM_PF_2G, SGM_ACC_PF_2G, true, 4, false>(mode, grid, s, P);
+    else if (D < 512)
+        sgm_acc_launch<2, SGM_PF_2G, SGM_ACC_PF_2G, false, 4, false>(mode, grid, s, P);
+    else if (D == 768)
+        sgm_acc_launch<3, SGM_PF_3G, SGM_ACC_PF_3G, true, 4, false>(mode, grid, s, P);
+    else if (D < 768)
+        sgm_acc_launch<3, SGM_PF_3G, SGM_ACC_PF_3G, false, 4, false>(mode, grid, s, P);
+    else if (D == 1024)
+        sgm_acc_launch<4, SGM_PF_4G, SGM_ACC_PF_4G, true, 4, false>(mode, grid, s, P);
+    else
+        sgm_acc_launch<4, SGM_PF_4G, SGM_ACC_PF_4G, false, 4, false>(mode, grid, s, P);
+    return check_launch(who);
 }
 
 extern "C" int mccnn_sgm_first_pass(const float *image_left, const float *image_right, const float *const *vol_dhw,

@@ -19,6 +19,9 @@ MCCNN_CBCA_SEPARABLE = 0
 MCCNN_CBCA_REFERENCE_ORDER = 1
 MCCNN_SIDE_LEFT = 0
 MCCNN_SIDE_RIGHT = 1
+MCCNN_SGM_ACC_STORE = 0        # mccnn_sgm_pass_accumulate: acc = L
+MCCNN_SGM_ACC_ADD = 1          # acc = acc + L
+MCCNN_SGM_ACC_ADD_QUARTER = 2  # acc = (acc + L) / 4
 MCCNN_E_INVALID = -1      # include/mccnn.h: bad argument
 MCCNN_E_UNSUPPORTED = -2  # shape / parameter the kernels are not built for
 MCCNN_E_SCRATCH = -3      # scratch buffer too small
@@ -74,6 +77,8 @@ SIGNATURES = {
     "mccnn_sgm_flags": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "mccnn_sgm_pass_flagged": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _vp, _sz,
                                     _vp]),
+    "mccnn_sgm_pass_accumulate": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i), _i, _i, _i, _i, _i, _i,
+                                       _f, _f, _f, _f, _i, _vp, _sz, _vp]),
     "mccnn_sgm_first_pass": (_i, [_vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i), _i, _i, _i,
                                   _i, _f, _f, _f, _f, _f, _vp, _sz, _vp]),
     "mccnn_wta": (_i, [_vp, _i, _i, _i, _vp, _vp]),

@@ -109,6 +109,10 @@ parser.add_argument("--paper_support_regions", action="store_true",
 parser.add_argument("--paper_interpolation", action="store_true",
                     help="fill mismatches from 16 rays and occlusions from the left (paper sec. 4.4; "
                          "process_functional.py:318, :361 note the reference uses 4 directions and the right)")
+parser.add_argument("--paper_sgm", action="store_true",
+                    help="semiglobal matching as the paper defines it: the four directions each computed from the same "
+                         "volume and averaged (the reference composes them one after the other on one array, "
+                         "process_functional.py:195-210, and its average is the identity)")
 parser.add_argument("--numpy1_promotion", action="store_true",
                     help="evaluate the sub-pixel formula as NumPy < 2 promotes its scalars (float64, rounded once), "
                          "i.e. as the reference's own Python 2.7 environment does; differs by <= 2.5e-5 px")
@@ -181,7 +185,8 @@ def main(argv=None):
             on_saturation="ignore",      # several pairs may be in flight: finish() polls the flag and repeats them
             extras=dict(both_view_support=args.paper_support_regions,
                         interpolation_directions=16 if args.paper_interpolation else 4,
-                        occlusion_from_left=args.paper_interpolation, numpy1_promotion=args.numpy1_promotion))
+                        occlusion_from_left=args.paper_interpolation, numpy1_promotion=args.numpy1_promotion,
+                        sgm_independent_directions=args.paper_sgm))
 
     matchers = [make_matcher("miopen" if args.features == "library" else "auto") for _ in range(in_flight)]
     footprint_kw = dict(pairs_in_flight=in_flight, arch=args.arch,

@@ -21,6 +21,12 @@ Opt-in departures from the reference's results (defaults reproduce it):
                                              names it and skips it as impractical; pf:661-729 is its dead attempt)
     INTERPOLATION_DIRECTIONS 4 | 16        - mismatches filled from 16 rays as in the paper (pf:318)
     OCCLUSION_FROM_LEFT      False | True  - occlusions filled from the nearest match on the left, as in the paper (pf:361)
+    SGM_INDEPENDENT_DIRECTIONS False | True - SGM_average as the paper defines it and pf:195-210 spells it: the four
+                                             directions each computed from the SAME input volume and averaged,
+                                             (((right + left) + up) + bottom) / 4. in float32.  The reference composes
+                                             the four passes on one aliased array (semi_global_matching returns its
+                                             argument) and its average is the identity; that stays the default.  With
+                                             the switch on SGM_average leaves its arguments unmodified.
     NUMPY1_PROMOTION         False | True  - sub-pixel formula evaluated as NumPy < 2 promotes its scalars (float64,
                                              rounded once): what the reference's own Python 2.7 + NumPy 1.14 computes;
                                              the default is NumPy >= 2's float32 chain, which the golden vectors pin
@@ -42,6 +48,7 @@ CBCA_BOTH_VIEWS = False
 INTERPOLATION_DIRECTIONS = 4
 OCCLUSION_FROM_LEFT = False
 NUMPY1_PROMOTION = False
+SGM_INDEPENDENT_DIRECTIONS = False
 
 _CV_MODES = {"exact": hip.MCCNN_CV_EXACT, "mfma": hip.MCCNN_CV_MFMA}
 _CBCA_ORDERS = {"separable": hip.MCCNN_CBCA_SEPARABLE, "reference": hip.MCCNN_CBCA_REFERENCE_ORDER,
@@ -237,7 +244,8 @@ def semi_global_matching(left_image, right_image, cost_volume, r, sgm_P1, sgm_P2
 def SGM_average(left_cost_volume, right_cost_volume, left_image, right_image,
                 sgm_P1, sgm_P2, sgm_Q1, sgm_Q2, sgm_D, sgm_V):
     """pf:187-235.  Like the reference, the two volume arguments end up holding the result as well (its four
-    semi_global_matching calls run in place on them) and new arrays are returned."""
+    semi_global_matching calls run in place on them) and new arrays are returned.  SGM_INDEPENDENT_DIRECTIONS: the
+    paper's average of four independent directions instead, and the arguments are left as they are."""
     L, _ = _img(left_image)
     R, _ = _img(right_image)
     vl, was_np = _dev(left_cost_volume)
@@ -247,6 +255,13 @@ def SGM_average(left_cost_volume, right_cost_volume, left_image, right_image,
     hl = torch.empty(hwd_shape, dtype=torch.float32, device=vl.device)
     hr = torch.empty(hwd_shape, dtype=torch.float32, device=vl.device)
     scratch = sd.sgm_scratch(H, W, D, vl.device)
+    if SGM_INDEPENDENT_DIRECTIONS:
+        # the four directions from the same volume, averaged: out of place, the arguments keep their values
+        sl, sr = sd.dhw_to_hwd(vl), sd.dhw_to_hwd(vr)
+        sd.sgm_average_independent_hwd(L, R, [sl, sr], [hl, hr], [hip.MCCNN_SIDE_LEFT, hip.MCCNN_SIDE_RIGHT], D, sgm_P1,
+                                       sgm_P2, sgm_Q1, sgm_Q2, sgm_D, sgm_V, scratch)
+        ol, orr = sd.hwd_to_dhw(hl, D), sd.hwd_to_dhw(hr, D)
+        return (ol.cpu().numpy(), orr.cpu().numpy()) if was_np else (ol, orr)
     sd.sgm_average_from_dhw(L, R, [vl, vr], [hl, hr], [hip.MCCNN_SIDE_LEFT, hip.MCCNN_SIDE_RIGHT], D, sgm_P1, sgm_P2,
                             sgm_Q1, sgm_Q2, sgm_D, sgm_V, scratch)
     ol, orr = sd.hwd_to_dhw(hl, D), sd.hwd_to_dhw(hr, D)

@@ -850,6 +850,43 @@ def sgm_average_hwd(image_left, image_right, vols_hwd, sides, D, sgm_P1, sgm_P2,
         timer.stop()
 
 
+def sgm_pass_accumulate_hwd(srcs_hwd, accs_hwd, sides, D, r, p1, p2, q1, q2, mode, flags):
+    """One direction out of place on 1 or 2 HWD volumes (mccnn_sgm_pass_accumulate): the costs come from `srcs_hwd`,
+    which are not written, and every line of the direction's L is combined with `accs_hwd` as `mode` says
+    (hip.MCCNN_SGM_ACC_STORE / _ADD / _ADD_QUARTER).  flags: the direction's planes (sgm_flag_planes)."""
+    H, W, _ = srcs_hwd[0].shape
+    n, side_arr, src_arr, acc_arr = _sgm_arrays(sides, srcs_hwd, accs_hwd)
+    hip.check(hip.load().mccnn_sgm_pass_accumulate(src_arr, acc_arr, side_arr, n, int(D), H, W, int(r[0]), int(r[1]), p1,
+                                                   p2, q1, q2, int(mode), hip.ptr(flags), flags.numel(), hip.stream()),
+              "mccnn_sgm_pass_accumulate")
+
+
+SGM_ACC_MODES = (hip.MCCNN_SGM_ACC_STORE, hip.MCCNN_SGM_ACC_ADD, hip.MCCNN_SGM_ACC_ADD, hip.MCCNN_SGM_ACC_ADD_QUARTER)
+
+
+def sgm_average_independent_hwd(image_left, image_right, vols_hwd, spares_hwd, sides, D, sgm_P1, sgm_P2, sgm_Q1, sgm_Q2,
+                                sgm_D, sgm_V, scratch, timer=_NO_TIMER, flags=None):
+    """The paper's SGM on HWD volumes: the four directions of SGM_DIRECTIONS each computed from the SAME volume and
+    averaged, (((L0 + L1) + L2) + L3) / 4. in float32 - what pf:195-210 spells and, because semi_global_matching
+    returns its argument, does not compute (sgm_average_hwd is what it computes).  Four out-of-place passes read
+    `vols_hwd` (left unmodified) and accumulate into `spares_hwd`: store, add, add, add-and-quarter.  Returns
+    (results, spares) with the roles swapped: the results are the former spares, the former inputs are now spare.
+    flags: sgm_flag_planes() of the same images, D and sgm_D; without them every direction's planes are built into
+    `scratch` in front of its pass."""
+    p1h, p1v, p2, q1, q2, thr = _sgm_penalties(sgm_P1, sgm_P2, sgm_Q1, sgm_Q2, sgm_D, sgm_V)
+    H, W = image_left.shape
+    for i, (r, mode) in enumerate(zip(SGM_DIRECTIONS, SGM_ACC_MODES)):
+        timer.start("sgm_pass_accumulate" if len(vols_hwd) == 2 else "sgm_pass_accumulate_one_volume")
+        planes = flags[i] if flags is not None else scratch
+        if flags is None:
+            hip.check(hip.load().mccnn_sgm_flags(hip.ptr(image_left), hip.ptr(image_right), int(D), H, W, int(r[0]),
+                                                 int(r[1]), thr, hip.ptr(scratch), scratch.numel(), hip.stream()),
+                      "mccnn_sgm_flags")
+        sgm_pass_accumulate_hwd(vols_hwd, spares_hwd, sides, D, r, p1h if r[0] == 0 else p1v, p2, q1, q2, mode, planes)
+        timer.stop()
+    return list(spares_hwd), list(vols_hwd)
+
+
 SGM_FIRST_PASS_MAX_D = 256  # mccnn_sgm_first_pass gathers one [256 d][16 w] tile per wave
 
 
@@ -1132,8 +1169,10 @@ class StereoMatcher(object):
         self.sgm_flags_once = bool(sgm_flags_once)
         # opt-in departures from the reference (they change the output): the paper's rules it leaves out, and the
         # scalar promotion of the NumPy it was written for
+        # sgm_independent_directions: the paper's SGM - the four directions each from the same volume, averaged
+        # (sgm_average_independent_hwd) - instead of the reference's four passes composed on one array
         self.extras = dict(both_view_support=False, interpolation_directions=4, occlusion_from_left=False,
-                           numpy1_promotion=False)
+                           numpy1_promotion=False, sgm_independent_directions=False)
         if extras:
             unknown = set(extras) - set(self.extras)
             if unknown:
@@ -1360,7 +1399,13 @@ class StereoMatcher(object):
                 # (the flag planes of the four directions were built once, on the side stream beside the cost volume:
                 # both chains read them and launch no flag kernels of their own - 8 launches of 11 us off the two
                 # critical chains)
-                sgm_average_hwd(L, R, [v], [side], D, *self._sgm_hp(), scr, timer, flags=flag_planes)
+                if self.extras["sgm_independent_directions"]:
+                    # (result in the former spare; the aggregation behind it starts with a launch that rewrites every
+                    # pixel of its output, so it asks nothing of what the spare - now the pre-SGM volume - holds)
+                    (v,), (t,) = sgm_average_independent_hwd(L, R, [v], [t], [side], D, *self._sgm_hp(), scr, timer,
+                                                             flags=flag_planes)
+                else:
+                    sgm_average_hwd(L, R, [v], [side], D, *self._sgm_hp(), scr, timer, flags=flag_planes)
                 timer.span_stop("sgm")
                 timer.span_start("aggregation_2")
                 v, t = cbca_prog_chain(v, t, sup, prog, D, n2 - 1 if fuse else n2, dist, total=n2, fused_last=fuse, **chain)
@@ -1397,7 +1442,11 @@ class StereoMatcher(object):
         if keep is not None:
             keep["cbca1"] = (hwd_to_dhw(lh, D), hwd_to_dhw(rh, D))
         timer.span_start("sgm")
-        sgm_average_hwd(L, R, [lh, rh], sides, D, *self._sgm_hp(), ws["scratch"], timer)
+        if self.extras["sgm_independent_directions"]:
+            (lh, rh), (lt, rt) = sgm_average_independent_hwd(L, R, [lh, rh], [lt, rt], sides, D, *self._sgm_hp(),
+                                                             ws["scratch"], timer)
+        else:
+            sgm_average_hwd(L, R, [lh, rh], sides, D, *self._sgm_hp(), ws["scratch"], timer)
         timer.span_stop("sgm")
         if keep is not None:
             keep["sgm"] = (hwd_to_dhw(lh, D), hwd_to_dhw(rh, D))
@@ -1433,12 +1482,29 @@ class StereoMatcher(object):
             keep["cbca1"] = (lcv.clone(), rcv.clone())
         lh = next(h for b, h in zip(ws["vol"], hwd) if b.data_ptr() == t1d.data_ptr())
         rh = next(h for b, h in zip(ws["vol"], hwd) if b.data_ptr() == t2d.data_ptr())
-        sgm_average_from_dhw(L, R, [lcv, rcv], [lh, rh], [hip.MCCNN_SIDE_LEFT, hip.MCCNN_SIDE_RIGHT], D, *self._sgm_hp(),
-                             ws["scratch"], timer)
-        timer.start("hwd_to_dhw")
-        hwd_to_dhw(lh, D, lcv)
-        hwd_to_dhw(rh, D, rcv)
-        timer.stop()
+        sides = [hip.MCCNN_SIDE_LEFT, hip.MCCNN_SIDE_RIGHT]
+        if self.extras["sgm_independent_directions"]:
+            # layout change into the spares, four passes from there into the buffers the plane-major volumes have just
+            # left, change back into the spares: the volumes and their spares swap roles (no fused first pass here: it
+            # composes in place)
+            timer.start("dhw_to_hwd")
+            dhw_to_hwd(lcv, lh)
+            dhw_to_hwd(rcv, rh)
+            timer.stop()
+            la = next(h for b, h in zip(ws["vol"], hwd) if b.data_ptr() == lcv.data_ptr())
+            ra = next(h for b, h in zip(ws["vol"], hwd) if b.data_ptr() == rcv.data_ptr())
+            sgm_average_independent_hwd(L, R, [lh, rh], [la, ra], sides, D, *self._sgm_hp(), ws["scratch"], timer)
+            timer.start("hwd_to_dhw")
+            hwd_to_dhw(la, D, t1d)
+            hwd_to_dhw(ra, D, t2d)
+            timer.stop()
+            lcv, t1d, rcv, t2d = t1d, lcv, t2d, rcv
+        else:
+            sgm_average_from_dhw(L, R, [lcv, rcv], [lh, rh], sides, D, *self._sgm_hp(), ws["scratch"], timer)
+            timer.start("hwd_to_dhw")
+            hwd_to_dhw(lh, D, lcv)
+            hwd_to_dhw(rh, D, rcv)
+            timer.stop()
         if keep is not None:
             keep["sgm"] = (lcv.clone(), rcv.clone())
         (lcv, t1d), (rcv, t2d) = self._aggregate_dhw((lcv, t1d), (rcv, t2d), sups, hp["cbca_num_iterations2"], timer)
