@@ -45,7 +45,7 @@ extern "C" {
 
 typedef void *mccnn_stream_t; /* hipStream_t */
 
-#define MCCNN_ABI_VERSION 7 /* 2: window-mask plane, *_hwd entry points; 3: saturation flags; 4: program-driven CBCA; 5: skip programs; 6: one-volume launches; 7: refresh launches, SGM flag planes as a call of their own; still 7 with the mccnn_ingest_* and the mccnn_decision_* / mccnn_cost_volume_accurate* entry points: purely additive, nothing that existed changed */
+#define MCCNN_ABI_VERSION 7 /* 2: window-mask plane, *_hwd entry points; 3: saturation flags; 4: program-driven CBCA; 5: skip programs; 6: one-volume launches; 7: refresh launches, SGM flag planes as a call of their own; still 7 with the mccnn_ingest_* and the mccnn_decision_* / mccnn_cost_volume_accurate* entry points and mccnn_sample_patches: purely additive, nothing that existed changed */
 
 #define MCCNN_E_INVALID (-1)     /* bad argument (null pointer, non-positive size, unsupported shape) */
 #define MCCNN_E_UNSUPPORTED (-2) /* shape outside what the kernels were built for (e.g. D > 1024 for SGM) */
@@ -419,6 +419,34 @@ int mccnn_ingest_u8(const uint8_t *image_u8, int H, int W, int C, float *out, vo
                     mccnn_stream_t stream);
 int mccnn_ingest_u8_pair(const uint8_t *left_u8, const uint8_t *right_u8, int H, int W, int C, float *out_left,
                          float *out_right, void *scratch, size_t scratch_bytes, mccnn_stream_t stream);
+
+/* ---- training patches cut on the device (datagenerator.py:137-216; the paper's data set augmentation) -------------
+ * N sample records -> N patches out[N][ps][ps], gathered from `pool`, a flat float32 buffer that holds n_images
+ * standardised images of any sizes, UNPADDED; images[k] gives image k's offset in floats into the pool and its size.
+ * A record names its image, the centre (cy, cx) of the patch in it, the row-major 2 x 2 matrix m that maps an offset in
+ * the patch (x first) to an offset in the image, and a gain and a bias.  For output pixel (i, j), c = (ps - 1) / 2,
+ * u = j - c, v = i - c, float32 throughout, every operation rounded on its own, in this order:
+ *     x  = cx + ((m[0]*u) + (m[1]*v))          y  = cy + ((m[2]*u) + (m[3]*v))
+ *     x0 = floorf(x), fx = x - x0              y0 = floorf(y), fy = y - y0
+ *     tap(yf, xf) = I[(int)yf][(int)xf] if 0 <= yf <= H-1 and 0 <= xf <= W-1 (compared as floats, before any conversion),
+ *                   else +0.0f: the reference's zero padding
+ *     row(yy) = tap(yy, x0)                                        if fx == 0   (the second tap is not read)
+ *             = (tap(yy,x0) * (1 - fx)) + (tap(yy,x0+1) * fx)      otherwise
+ *     val     = row(y0)                                            if fy == 0
+ *             = (row(y0) * (1 - fy)) + (row(y0+1) * fy)            otherwise
+ *     out     = val                                                if gain == 1 and bias == 0
+ *             = (val * gain) + bias                                otherwise
+ * An identity record (integer centre, m = identity, gain 1, bias 0) is therefore a plain copy, -0.0 pixels included,
+ * and a centre far outside the image (+-1e30) reads nothing and yields zeros.
+ * records[n].image is TRUSTED (the kernel cannot report an error): the caller checks 0 <= image < n_images before the
+ * upload.  One launch, one workgroup per patch in a grid-stride loop, so N is limited by the output's size alone.
+ * Refused: null pointers, N < 1, n_images < 1, an even or non-positive ps (MCCNN_E_INVALID); ps > 31
+ * (MCCNN_E_UNSUPPORTED). */
+typedef struct { int64_t offset; int32_t H, W; } mccnn_sample_image_t;                        /* 16 bytes */
+typedef struct { int32_t image; float cy, cx; float m[4]; float gain, bias; } mccnn_sample_t; /* 36 bytes */
+int mccnn_sample_patches(const float *pool, const mccnn_sample_image_t *images, int n_images,
+                         const mccnn_sample_t *records, int N, int ps, float *out /* [N][ps][ps] */,
+                         mccnn_stream_t stream);
 
 /* ---- a1 epilogues of the conv stack (model.py:51-64, 111-125) ------------------------------------------------
  * mccnn_bias_act: x[n][c][i] = act(x[n][c][i] + bias[c]) in place on an NCHW tensor (plane = H*W elements) -

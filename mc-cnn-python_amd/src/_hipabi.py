@@ -99,6 +99,7 @@ SIGNATURES = {
     "mccnn_ingest_scratch_bytes": (_sz, [_i, _i]),
     "mccnn_ingest_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "mccnn_ingest_u8_pair": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mccnn_sample_patches": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
 }
 
 _lib = None

@@ -20,6 +20,12 @@ TensorBoard is not in this image: the two scalars the reference logs (hinge_loss
 `<tensorboard_dir>/scalars.jsonl`, one JSON object per point with the reference's step numbering.
 Multi-GPU (not in the reference): under torchrun every rank draws its own batches and the gradients are averaged with
 all_reduce (RCCL) before the step - synchronous data parallelism; rank 0 writes logs and checkpoints.
+Training the paper's way (not in the reference; off unless asked for): --sampler device keeps the images on the GPU and
+cuts every batch there (datagenerator.DevicePatchSampler, csrc/sample.hip); with it --sampling pool shuffles every valid
+ground-truth pixel of train.txt into one pool (an epoch is n_valid // batch_size steps instead of one per image),
+--augment middlebury|kitti applies the paper's data set augmentation (every key has an --aug_<key> override),
+--subpixel_centres keeps the fractional disparity; --lr_drop_epoch E --lr_drop_factor F divides the learning rate by F
+from epoch E on (the paper: one tenfold drop).  Validation keeps pair sampling on val.txt, without augmentation.
 """
 import argparse
 import json
@@ -29,6 +35,7 @@ from datetime import datetime
 import numpy as np
 
 import util
+from datagenerator import AUGMENT_KEYS      # NumPy only: torch is imported in main(), after the GPU is pinned
 
 parser = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                                  description="training of the MC-CNN matching network (fast architecture)")
@@ -58,6 +65,39 @@ parser.add_argument("--arch", choices=("fast", "accurate"), default="fast",
                          "triplets - (left, right+) -> 1, (left, right-) -> 0; scalars bce_loss / val_bce_loss")
 parser.add_argument("--num_fc_layers", type=int, default=3,
                     help="with --arch accurate: hidden fully-connected layers (Middlebury 3, KITTI 4)")
+parser.add_argument("--sampler", choices=("host", "device"), default="host",
+                    help="'host': the reference's sampler, patches cut with NumPy and copied to the GPU; 'device': the "
+                         "images live on the GPU and one HIP launch cuts each batch (needs a GPU)")
+parser.add_argument("--sampling", choices=("pair", "pool"), default="pair",
+                    help="'pair': one mini-batch per training image per epoch (the reference); 'pool': mini-batches from "
+                         "one shuffled pool of every valid pixel of the training set (the paper; needs --sampler device)")
+parser.add_argument("--augment", choices=("none", "middlebury", "kitti"), default="none",
+                    help="the paper's data set augmentation with the preset of that data set (needs --sampler device)")
+for _key in AUGMENT_KEYS:
+    parser.add_argument("--aug_" + _key, type=float, default=None,
+                        help="overrides '%s' of the --augment preset (needs --sampler device)" % _key)
+parser.add_argument("--subpixel_centres", action="store_true",
+                    help="keep the fractional ground-truth disparity and the fractional displaced columns instead of the "
+                         "reference's int() (the paper's rule; needs --sampler device)")
+parser.add_argument("--lr_drop_epoch", type=int, default=None,
+                    help="from this epoch on the learning rate is learning_rate / lr_drop_factor (default: never)")
+parser.add_argument("--lr_drop_factor", type=float, default=10.0, help="see --lr_drop_epoch")
+
+
+def parse_args(argv=None):
+    """parser.parse_args plus the rules between the flags: what only the device sampler can do asks for it by name."""
+    args = parser.parse_args(argv)
+    overrides = {k: getattr(args, "aug_" + k) for k in AUGMENT_KEYS if getattr(args, "aug_" + k) is not None}
+    if args.sampler != "device":
+        for given, flag in ((args.sampling == "pool", "--sampling pool"), (args.augment != "none", "--augment"),
+                            (args.subpixel_centres, "--subpixel_centres")) + \
+                tuple((True, "--aug_" + k) for k in overrides):
+            if given:
+                parser.error("%s requires --sampler device" % flag)
+    if args.lr_drop_factor <= 0:
+        parser.error("--lr_drop_factor must be positive")
+    args.augment_overrides = overrides
+    return args
 
 
 def hinge_loss(features, batch_size, margin):
@@ -99,19 +139,29 @@ class Trainer(object):
         self.opt = torch.optim.SGD(self.params, lr=learning_rate, momentum=beta, dampening=0.0, nesterov=False)
         self.margin = margin
 
-    def loss(self, batch_left, batch_right_pos, batch_right_neg):
+    def _stacked(self, batch_left, batch_right_pos, batch_right_neg):
         import torch
         x = torch.from_numpy(np.concatenate([batch_left, batch_right_pos, batch_right_neg], axis=0)).to(self.net.device)
+        return x, batch_left.shape[0]
+
+    def loss_stacked(self, x, B):
+        """x: [3B,ps,ps,1] tensor on the network's device, the (left, right+, right-) batches stacked in that order
+        (what DevicePatchSampler.next_batch returns)."""
         if self.accurate:
-            B = batch_left.shape[0]
             f = self.net(x).reshape(3, B, -1)        # the three weight-shared towers as one batch
             return bce_loss(self.net.decision_logits(f[0], f[1]), self.net.decision_logits(f[0], f[2]))
-        return hinge_loss(self.net(x), batch_left.shape[0], self.margin)
+        return hinge_loss(self.net(x), B, self.margin)
+
+    def loss(self, batch_left, batch_right_pos, batch_right_neg):
+        return self.loss_stacked(*self._stacked(batch_left, batch_right_pos, batch_right_neg))
 
     def step(self, batch_left, batch_right_pos, batch_right_neg):
+        return self.step_stacked(*self._stacked(batch_left, batch_right_pos, batch_right_neg))
+
+    def step_stacked(self, x, B):
         import torch.distributed as dist
         self.opt.zero_grad(set_to_none=True)
-        loss = self.loss(batch_left, batch_right_pos, batch_right_neg)
+        loss = self.loss_stacked(x, B)
         loss.backward()
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             for p in self.params:            # synchronous data parallelism: average the gradients, then the same step
@@ -182,7 +232,7 @@ class Trainer(object):
 
 
 def main(argv=None):
-    args = parser.parse_args(argv)
+    args = parse_args(argv)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -190,6 +240,7 @@ def main(argv=None):
 
     import torch
     import distributed as mgpu
+    import datagenerator
     from datagenerator import ImageDataGenerator
     from model import ACCURATE_NET, NET
 
@@ -202,11 +253,31 @@ def main(argv=None):
     os.makedirs(args.tensorboard_dir, exist_ok=True)
     os.makedirs(args.checkpoint_dir, exist_ok=True)
     ps = (args.patch_size, args.patch_size)
-    train_generator = ImageDataGenerator(os.path.join(args.list_dir, "train.txt"), shuffle=True, patch_size=ps,
-                                         rng=np.random.default_rng(args.seed + 1000 * rank))
-    val_generator = ImageDataGenerator(os.path.join(args.list_dir, "val.txt"), shuffle=False, patch_size=ps,
-                                       rng=np.random.default_rng(args.seed + 7))
-    train_batches_per_epoch = train_generator.data_size
+    if args.sampler == "device":
+        import _hipabi
+        _hipabi.require_device()                  # the cut is a HIP kernel; there is no CPU fallback
+        augment = None
+        if args.augment != "none" or args.augment_overrides:
+            augment = dict({"none": datagenerator.AUGMENT_NONE, "middlebury": datagenerator.AUGMENT_MIDDLEBURY,
+                            "kitti": datagenerator.AUGMENT_KITTI}[args.augment], **args.augment_overrides)
+        train_generator = datagenerator.DevicePatchSampler(
+            os.path.join(args.list_dir, "train.txt"), shuffle=True, patch_size=ps,
+            rng=np.random.default_rng(args.seed + 1000 * rank), device=device, sampling=args.sampling,
+            truncate=not args.subpixel_centres, augment=augment, batch_size=args.batch_size, world_size=world)
+        val_generator = datagenerator.DevicePatchSampler(
+            os.path.join(args.list_dir, "val.txt"), shuffle=False, patch_size=ps,
+            rng=np.random.default_rng(args.seed + 7), device=device)
+        train_batches_per_epoch = train_generator.steps_per_epoch
+        train_step = lambda: trainer.step_stacked(train_generator.next_batch(args.batch_size), args.batch_size)
+        val_loss = lambda: trainer.loss_stacked(val_generator.next_batch(args.batch_size), args.batch_size)
+    else:
+        train_generator = ImageDataGenerator(os.path.join(args.list_dir, "train.txt"), shuffle=True, patch_size=ps,
+                                             rng=np.random.default_rng(args.seed + 1000 * rank))
+        val_generator = ImageDataGenerator(os.path.join(args.list_dir, "val.txt"), shuffle=False, patch_size=ps,
+                                           rng=np.random.default_rng(args.seed + 7))
+        train_batches_per_epoch = train_generator.data_size
+        train_step = lambda: trainer.step(*train_generator.next_batch(args.batch_size))
+        val_loss = lambda: trainer.loss(*val_generator.next_batch(args.batch_size))
     val_batches_per_epoch = val_generator.data_size
 
     if args.arch == "accurate":
@@ -226,11 +297,19 @@ def main(argv=None):
             log.write(json.dumps({"tag": tag, "value": float(value), "step": int(step)}) + "\n")
             log.flush()
 
-    print("[{}] {}: {} training pairs, {} validation pairs, {} rank(s) on {}".format(
-        rank, datetime.now(), train_batches_per_epoch, val_batches_per_epoch, world, device))
+    if args.sampling == "pool":
+        print("[{}] {}: {} training pairs, {} steps per epoch from a pool of {} pixels, {} validation pairs, {} rank(s) "
+              "on {}".format(rank, datetime.now(), train_generator.data_size, train_batches_per_epoch,
+                             train_generator.n_valid, val_batches_per_epoch, world, device))
+    else:
+        print("[{}] {}: {} training pairs, {} validation pairs, {} rank(s) on {}".format(
+            rank, datetime.now(), train_batches_per_epoch, val_batches_per_epoch, world, device))
     for epoch in range(args.start_epoch, args.end_epoch):
+        if args.lr_drop_epoch is not None:
+            for group in trainer.opt.param_groups:
+                group["lr"] = args.learning_rate / (args.lr_drop_factor if epoch >= args.lr_drop_epoch else 1.0)
         for batch in range(train_batches_per_epoch):
-            loss = trainer.step(*train_generator.next_batch(args.batch_size))
+            loss = train_step()
             if (batch + 1) % args.print_freq == 0:
                 scalar(loss_tag, loss, epoch * train_batches_per_epoch + batch)        # train.py:169-173
         if (epoch + 1) % args.save_freq == 0 and rank == 0:
@@ -239,7 +318,7 @@ def main(argv=None):
             print("[{}] {}: epoch {} saved to {}".format(rank, datetime.now(), epoch + 1, name))
         if (epoch + 1) % args.val_freq == 0:
             with torch.no_grad():
-                val_ls = sum(float(trainer.loss(*val_generator.next_batch(args.batch_size)))
+                val_ls = sum(float(val_loss())
                              for _ in range(val_batches_per_epoch)) / (1. * max(val_batches_per_epoch, 1))
             print("[{}] {}: epoch {} validation loss: {}".format(rank, datetime.now(), epoch + 1, val_ls))
             scalar("val_" + loss_tag, val_ls, train_batches_per_epoch * (epoch + 1))        # train.py:196-197
