@@ -20,6 +20,7 @@
 //            looked up at column w -/+ d.  Planes are padded by >= D columns of the "skipped" value on both sides
 //            so the lookup needs no bounds test.  class = a + b: 0 -> P, 1 -> P/Q1, 2 -> P/Q2.
 #include "common.h"
+#include "sgm_route.h"
 
 namespace mccnn {
 // Cache policy of the in-place scanline passes: every voxel is read once and written once per pass and the next pass
@@ -641,7 +642,8 @@ __global__ __launch_bounds__(256) void transpose_f4_kernel(const float *__restri
     }
 }
 
-constexpr int kSgmMaxD = 1024;   // four 256-disparity groups per lane (sgm_pass_kernel<4, ...>)
+constexpr int kSgmMaxD = 1024;        // four 256-disparity groups per lane (sgm_pass_kernel<4, ...>)
+constexpr int kSgmFirstMaxD = 256;    // sgm_first_pass_kernel: one group
 static inline int flag_pad(int D) { return (D + 3 + 15) & ~15; }  // >= D+3: the packed 4-byte read may start 3 early
 
 }  // namespace mccnn
@@ -692,194 +694,117 @@ extern "C" size_t mccnn_sgm_scratch_bytes(int H, int W, int D)
     return 2 * (size_t)H * pitch + 256;  // one flag plane per image
 }
 
-// The flag planes of one direction (both images) into `flags` (layout of the scratch buffer of mccnn_sgm_pass).
-static int sgm_launch_flags(const char *who, const float *image_left, const float *image_right, int D, int H, int W, int rh,
-                            int rw, float thr, void *flags, size_t flags_bytes, hipStream_t s)
+namespace mccnn {
+// What every entry point derives from (D, H, W) and its flag buffer (layout of mccnn_sgm_scratch_bytes).  The planes are
+// written by sgm_launch_flags alone, also where the entry point received the buffer as const.
+struct SgmGeometry {
+    int Dp, pad, pitch;
+    uint8_t *plane_l, *plane_r;   // flags of the left and of the right image
+};
+typedef const void *const *sgm_vols;   // the 1 or 2 volumes of a call, whatever their element type
+
+// The validation of every SGM entry point, in front of anything it launches, and the geometry.  pointers: the entry
+// point's array and buffer arguments are all non-null.  side == nullptr: an entry point without volumes (mccnn_sgm_flags);
+// vol_b: the second volume list of those that take two, else nullptr.  has_r = false: the first pass - r = (0, 1) by
+// definition, a row needs something to scan, and the tile gather holds 256 disparities.
+static int sgm_validate(const char *who, bool pointers, int n_jobs, sgm_vols vol_a, sgm_vols vol_b, const int *side, int D,
+                        int H, int W, bool has_r, int rh, int rw, const void *flags, size_t flags_bytes, SgmGeometry &g)
 {
-    using namespace mccnn;
-    MCCNN_REQUIRE(image_left && image_right && flags, MCCNN_E_INVALID, "%s: null pointer", who);
+    MCCNN_REQUIRE(pointers, MCCNN_E_INVALID, "%s: null pointer", who);
+    MCCNN_REQUIRE(n_jobs == 1 || n_jobs == 2, MCCNN_E_INVALID, "%s: n_jobs=%d must be 1 or 2", who, n_jobs);
     MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "%s: non-positive size", who);
-    MCCNN_REQUIRE(D >= 2 && D <= kSgmMaxD, MCCNN_E_UNSUPPORTED,
-                  "%s: D=%d outside [2,%d] (the reference itself needs D >= 2, pf:550)", who, D, kSgmMaxD);
-    MCCNN_REQUIRE((rh == 0 && (rw == 1 || rw == -1)) || (rw == 0 && (rh == 1 || rh == -1)), MCCNN_E_INVALID,
+    MCCNN_REQUIRE(has_r || W > 1, MCCNN_E_INVALID, "%s: bad size (W=1 leaves the pass nothing to scan)", who);
+    const int max_d = has_r ? kSgmMaxD : kSgmFirstMaxD;
+    MCCNN_REQUIRE(D >= 2 && D <= max_d, MCCNN_E_UNSUPPORTED, "%s: D=%d outside [2,%d]%s", who, D, max_d,
+                  has_r ? " (the reference itself needs D >= 2, pf:550)" : "; use mccnn_dhw_to_hwd + mccnn_sgm_pass");
+    MCCNN_REQUIRE(!has_r || (rh == 0 && (rw == 1 || rw == -1)) || (rw == 0 && (rh == 1 || rh == -1)), MCCNN_E_INVALID,
                   "%s: r=(%d,%d) is not an axis-aligned unit step (pf:484)", who, rh, rw);
     MCCNN_REQUIRE(flags_bytes >= mccnn_sgm_scratch_bytes(H, W, D), MCCNN_E_SCRATCH, "%s: scratch %zu < %zu bytes", who,
                   flags_bytes, mccnn_sgm_scratch_bytes(H, W, D));
-    const int pad = flag_pad(D);
-    const int pitch = W + 2 * pad;
-    uint8_t *plane_l = reinterpret_cast<uint8_t *>(flags);
-    uint8_t *plane_r = plane_l + (((size_t)H * pitch + 127) & ~(size_t)127);
-    const dim3 fgrid(cdiv(pitch, 256), H, 2), fblock(256);
-    hipLaunchKernelGGL(sgm_flags_kernel, fgrid, fblock, 0, s, image_left, image_right, H, W, rh, rw, thr, pitch, pad,
-                       plane_l, plane_r);
+    for (int j = 0; side && j < n_jobs; ++j) {
+        MCCNN_REQUIRE(vol_a[j] != nullptr && (!vol_b || vol_b[j] != nullptr), MCCNN_E_INVALID, "%s: null volume", who);
+        MCCNN_REQUIRE(side[j] == MCCNN_SIDE_LEFT || side[j] == MCCNN_SIDE_RIGHT, MCCNN_E_INVALID,
+                      "%s: side must be MCCNN_SIDE_LEFT or MCCNN_SIDE_RIGHT", who);
+    }
+    g.Dp = mccnn_hwd_pitch(D); g.pad = flag_pad(D); g.pitch = W + 2 * g.pad;
+    g.plane_l = reinterpret_cast<uint8_t *>(const_cast<void *>(flags));
+    g.plane_r = g.plane_l + (((size_t)H * g.pitch + 127) & ~(size_t)127);
+    return 0;
+}
+
+// A volume's own image gives its A plane, the other image its B plane, looked up at w - d (left) or w + d (right).
+template <typename Job> static void sgm_job_planes(Job &job, int side, const SgmGeometry &g)
+{
+    const bool left = side == MCCNN_SIDE_LEFT;
+    job.aplane = left ? g.plane_l : g.plane_r;
+    job.bplane = left ? g.plane_r : g.plane_l;
+    job.dsign = left ? -1 : +1;
+}
+
+// The fields the three parameter blocks share; the penalty classes {P, P/Q1, P/Q2} are float32 divisions (pf:538-541).
+template <typename Params>
+static void sgm_shape_and_penalties(Params &P, const SgmGeometry &g, int D, int H, int W, float p1, float p2, float q1,
+                                    float q2)
+{
+    P.D = D; P.Dp = g.Dp; P.H = H; P.W = W; P.pitch = g.pitch; P.pad = g.pad;
+    P.p1[0] = p1; P.p1[1] = p1 / q1; P.p1[2] = p1 / q2;
+    P.p2[0] = p2; P.p2[1] = p2 / q1; P.p2[2] = p2 / q2;
+}
+
+// The flag planes of one direction (both images).
+static int sgm_launch_flags(const char *who, const float *image_left, const float *image_right, int H, int W, int rh, int rw,
+                            float thr, const SgmGeometry &g, hipStream_t s)
+{
+    hipLaunchKernelGGL(sgm_flags_kernel, dim3(cdiv(g.pitch, 256), H, 2), dim3(256), 0, s, image_left, image_right, H, W, rh,
+                       rw, thr, g.pitch, g.pad, g.plane_l, g.plane_r);
     return check_launch(who);
 }
 
-// One direction on 1 or 2 volumes with the flag planes already in `flags`.
-static int sgm_launch_pass(const char *who, float *const *vol_hwd, const int *side, int n_jobs, int D, int H, int W, int rh,
-                           int rw, float p1, float p2, float q1, float q2, const void *flags, size_t flags_bytes,
-                           hipStream_t s)
+// The only launch site of sgm_pass_kernel.  A route's fields become template arguments one call at a time (-1: not yet),
+// and the innermost call launches with the depth sgm_steps_in_flight gives.  Three disparities per lane exist for one near
+// group only - what sgm_route hands out and the kernel's static_asserts demand - so no other VPL = 3 kernel is instantiated.
+template <int ACC, typename Params, int NG = -1, int FULL = -1, int VPL = -1, int FAR = -1>
+static void sgm_launch_route(const SgmRoute &rt, dim3 grid, hipStream_t s, const Params &P)
 {
-    using namespace mccnn;
-    MCCNN_REQUIRE(vol_hwd && side && flags, MCCNN_E_INVALID, "%s: null pointer", who);
-    MCCNN_REQUIRE(n_jobs == 1 || n_jobs == 2, MCCNN_E_INVALID, "%s: n_jobs=%d must be 1 or 2", who, n_jobs);
-    MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "%s: non-positive size", who);
-    MCCNN_REQUIRE(D >= 2 && D <= kSgmMaxD, MCCNN_E_UNSUPPORTED,
-                  "%s: D=%d outside [2,%d] (the reference itself needs D >= 2, pf:550)", who, D, kSgmMaxD);
-    MCCNN_REQUIRE((rh == 0 && (rw == 1 || rw == -1)) || (rw == 0 && (rh == 1 || rh == -1)), MCCNN_E_INVALID,
-                  "%s: r=(%d,%d) is not an axis-aligned unit step (pf:484)", who, rh, rw);
-    MCCNN_REQUIRE(flags_bytes >= mccnn_sgm_scratch_bytes(H, W, D), MCCNN_E_SCRATCH, "%s: scratch %zu < %zu bytes", who,
-                  flags_bytes, mccnn_sgm_scratch_bytes(H, W, D));
-    const int pad = flag_pad(D);
-    const int pitch = W + 2 * pad;
-    const uint8_t *plane_l = reinterpret_cast<const uint8_t *>(flags);
-    const uint8_t *plane_r = plane_l + (((size_t)H * pitch + 127) & ~(size_t)127);
+    if constexpr (NG < 0) {
+        switch (rt.ng) {
+        case 1: return sgm_launch_route<ACC, Params, 1>(rt, grid, s, P);
+        case 2: return sgm_launch_route<ACC, Params, 2>(rt, grid, s, P);
+        case 3: return sgm_launch_route<ACC, Params, 3>(rt, grid, s, P);
+        default: return sgm_launch_route<ACC, Params, 4>(rt, grid, s, P);
+        }
+    } else if constexpr (FULL < 0) {
+        rt.full ? sgm_launch_route<ACC, Params, NG, 1>(rt, grid, s, P) : sgm_launch_route<ACC, Params, NG, 0>(rt, grid, s, P);
+    } else if constexpr (VPL < 0) {
+        rt.vpl == 3 ? sgm_launch_route<ACC, Params, NG, FULL, 3>(rt, grid, s, P)
+                    : sgm_launch_route<ACC, Params, NG, FULL, 4>(rt, grid, s, P);
+    } else if constexpr (FAR < 0) {
+        rt.far ? sgm_launch_route<ACC, Params, NG, FULL, VPL, 1>(rt, grid, s, P)
+               : sgm_launch_route<ACC, Params, NG, FULL, VPL, 0>(rt, grid, s, P);
+    } else if constexpr (VPL == 4 || (NG == 1 && !FAR)) {
+        hipLaunchKernelGGL((sgm_pass_kernel<NG, sgm_steps_in_flight(NG, FULL != 0, VPL, ACC), FULL != 0, VPL, FAR != 0, ACC,
+                                            Params>), grid, dim3(64), 0, s, P);
+    }
+}
+
+// One direction in place on 1 or 2 volumes, the flag planes already built.
+static int sgm_launch_pass(const char *who, float *const *vol_hwd, const int *side, int n_jobs, int D, int H, int W, int rh,
+                           int rw, float p1, float p2, float q1, float q2, const SgmGeometry &g, hipStream_t s)
+{
+    if ((rh == 0 ? W : H) < 2) return 0;  // nothing to scan
     SgmParams P;
     for (int j = 0; j < 2; ++j) {
         const int jj = j < n_jobs ? j : 0;
-        MCCNN_REQUIRE(vol_hwd[jj] != nullptr, MCCNN_E_INVALID, "%s: null volume", who);
-        MCCNN_REQUIRE(side[jj] == MCCNN_SIDE_LEFT || side[jj] == MCCNN_SIDE_RIGHT, MCCNN_E_INVALID,
-                      "%s: side must be MCCNN_SIDE_LEFT or MCCNN_SIDE_RIGHT", who);
         P.job[j].vol = vol_hwd[jj];
-        const bool left = side[jj] == MCCNN_SIDE_LEFT;
-        P.job[j].aplane = left ? plane_l : plane_r;
-        P.job[j].bplane = left ? plane_r : plane_l;
-        P.job[j].dsign = left ? -1 : +1;
+        sgm_job_planes(P.job[j], side[jj], g);
     }
-    P.D = D; P.Dp = mccnn_hwd_pitch(D); P.H = H; P.W = W; P.pitch = pitch; P.pad = pad; P.rh = rh; P.rw = rw;
-    P.p1[0] = p1; P.p1[1] = p1 / q1; P.p1[2] = p1 / q2;  // pf:538-541 (float32 divisions)
-    P.p2[0] = p2; P.p2[1] = p2 / q1; P.p2[2] = p2 / q2;
-    const int nlines = rh == 0 ? H : W;
-    if ((rh == 0 ? W : H) < 2) return 0;  // nothing to scan
-    const dim3 grid(nlines, n_jobs), block(64);
-    // steps in flight: 8, 12 and 16 measure the same at 750x500x256 (0.30 / 0.29 ms per pass: 1000-1500 scanline waves);
-    // a 1242x375 pair has only 750 row scanlines - fewer waves than SIMDs - and its horizontal passes gain from 24 steps
-    // (0.388 -> 0.342 ms); two disparity groups per lane (D > 256) take 12 (vertical 2.17 -> 2.06 ms at 1500x1000x400)
-#ifndef SGM_PF_PARTIAL
-#define SGM_PF_PARTIAL 24
-#endif
-#ifndef SGM_PF_2G
-#define SGM_PF_2G 12
-#endif
-    // three and four groups (512 < D <= 1024): the step buffers cost 5 VGPRs per group and step (a 16-byte vector + the
-    // packed flags), so 24 group-steps in flight - the 2 x 12 of two groups - hold the kernels at 3 waves per SIMD
-    // (<= 168 VGPRs by the register-file table of the MI355X): 3 x 8 -> 160 VGPRs, 4 x 6 -> 168.  One more step (3 x 9, 4 x 7)
-    // needs 176 / 189 and drops to 2 waves.  Unmeasured: chosen from the register budget alone.
-#ifndef SGM_PF_3G
-#define SGM_PF_3G 8
-#endif
-#ifndef SGM_PF_4G
-#define SGM_PF_4G 6
-#endif
+    sgm_shape_and_penalties(P, g, D, H, W, p1, p2, q1, q2);
+    P.rh = rh; P.rw = rw;
     // vertical scanlines of volumes of 4 GiB or more: the rebasing variants (FAR = true); horizontal ones span a
-    // row and every shape below 4 GiB keeps the kernels above
-    if (rh != 0 && (size_t)H * W * P.Dp * 4 >= ((size_t)1 << 32)) {
-        const int ng = cdiv(P.Dp, 256);
-        const bool full = D == 256 * ng;
-        if (ng == 1 && full)
-            hipLaunchKernelGGL((sgm_pass_kernel<1, 16, true, 4, true>), grid, block, 0, s, P);
-        else if (ng == 1)
-            hipLaunchKernelGGL((sgm_pass_kernel<1, SGM_PF_PARTIAL, false, 4, true>), grid, block, 0, s, P);
-        else if (ng == 2 && full)
-            hipLaunchKernelGGL((sgm_pass_kernel<2, SGM_PF_2G, true, 4, true>), grid, block, 0, s, P);
-        else if (ng == 2)
-            hipLaunchKernelGGL((sgm_pass_kernel<2, SGM_PF_2G, false, 4, true>), grid, block, 0, s, P);
-        else if (ng == 3 && full)
-            hipLaunchKernelGGL((sgm_pass_kernel<3, SGM_PF_3G, true, 4, true>), grid, block, 0, s, P);
-        else if (ng == 3)
-            hipLaunchKernelGGL((sgm_pass_kernel<3, SGM_PF_3G, false, 4, true>), grid, block, 0, s, P);
-        else if (full)
-            hipLaunchKernelGGL((sgm_pass_kernel<4, SGM_PF_4G, true, 4, true>), grid, block, 0, s, P);
-        else
-            hipLaunchKernelGGL((sgm_pass_kernel<4, SGM_PF_4G, false, 4, true>), grid, block, 0, s, P);
-        return check_launch(who);
-    }
-    if (D == 256)
-        hipLaunchKernelGGL((sgm_pass_kernel<1, 16, true>), grid, block, 0, s, P);
-    else if (D == 192)                                   // three disparities per lane: all 64 lanes, no tail masks
-        hipLaunchKernelGGL((sgm_pass_kernel<1, SGM_PF_PARTIAL, true, 3>), grid, block, 0, s, P);
-    else if (D > 128 && D < 192 && P.Dp % 3 == 0)
-        hipLaunchKernelGGL((sgm_pass_kernel<1, SGM_PF_PARTIAL, false, 3>), grid, block, 0, s, P);
-    else if (D < 256)
-        hipLaunchKernelGGL((sgm_pass_kernel<1, SGM_PF_PARTIAL, false>), grid, block, 0, s, P);
-    else if (D == 512)
-        hipLaunchKernelGGL((sgm_pass_kernel<2, SGM_PF_2G, true>), grid, block, 0, s, P);
-    else if (D < 512)
-        hipLaunchKernelGGL((sgm_pass_kernel<2, SGM_PF_2G, false>), grid, block, 0, s, P);
-    else if (D == 768)
-        hipLaunchKernelGGL((sgm_pass_kernel<3, SGM_PF_3G, true>), grid, block, 0, s, P);
-    else if (D < 768)
-        hipLaunchKernelGGL((sgm_pass_kernel<3, SGM_PF_3G, false>), grid, block, 0, s, P);
-    else if (D == 1024)
-        hipLaunchKernelGGL((sgm_pass_kernel<4, SGM_PF_4G, true>), grid, block, 0, s, P);
-    else
-        hipLaunchKernelGGL((sgm_pass_kernel<4, SGM_PF_4G, false>), grid, block, 0, s, P);
+    // row and every shape below 4 GiB keeps the plain kernels
+    const bool far_volume = rh != 0 && (size_t)H * W * g.Dp * 4 >= ((size_t)1 << 32);
+    sgm_launch_route<0>(sgm_route(D, far_volume), dim3(rh == 0 ? H : W, n_jobs), s, P);
     return check_launch(who);
-}
-
-extern "C" int mccnn_sgm_pass(const float *image_left, const float *image_right, float *const *vol_hwd, const int *side,
-                              int n_jobs, int D, int H, int W, int rh, int rw, float p1, float p2, float q1, float q2,
-                              float thr, void *scratch, size_t scratch_bytes, mccnn_stream_t stream)
-{
-    using namespace mccnn;
-    MCCNN_REQUIRE(image_left && image_right && vol_hwd && side && scratch, MCCNN_E_INVALID,
-                  "mccnn_sgm_pass: null pointer");
-    MCCNN_REQUIRE(n_jobs == 1 || n_jobs == 2, MCCNN_E_INVALID, "mccnn_sgm_pass: n_jobs=%d must be 1 or 2", n_jobs);
-    const int rc = sgm_launch_flags("mccnn_sgm_pass", image_left, image_right, D, H, W, rh, rw, thr, scratch, scratch_bytes,
-                                    (hipStream_t)stream);
-    if (rc) return rc;
-    return sgm_launch_pass("mccnn_sgm_pass", vol_hwd, side, n_jobs, D, H, W, rh, rw, p1, p2, q1, q2, scratch, scratch_bytes,
-                           (hipStream_t)stream);
-}
-
-// The two halves of mccnn_sgm_pass as calls of their own (round 6): the flag planes depend on the images, the direction
-// and the threshold only - a caller that advances the two volumes of a pair in separate launches (or on separate
-// streams) builds them once per direction and hands them to every pass.
-extern "C" int mccnn_sgm_flags(const float *image_left, const float *image_right, int D, int H, int W, int rh, int rw,
-                               float thr, void *flags, size_t flags_bytes, mccnn_stream_t stream)
-{
-    return sgm_launch_flags("mccnn_sgm_flags", image_left, image_right, D, H, W, rh, rw, thr, flags, flags_bytes,
-                            (hipStream_t)stream);
-}
-
-extern "C" int mccnn_sgm_pass_flagged(float *const *vol_hwd, const int *side, int n_jobs, int D, int H, int W, int rh, int rw,
-                                      float p1, float p2, float q1, float q2, const void *flags, size_t flags_bytes,
-                                      mccnn_stream_t stream)
-{
-    return sgm_launch_pass("mccnn_sgm_pass_flagged", vol_hwd, side, n_jobs, D, H, W, rh, rw, p1, p2, q1, q2, flags,
-                           flags_bytes, (hipStream_t)stream);
-}
-
-// ---- the out-of-place, accumulating pass (the paper's four independent directions) -------------------------------
-// Steps in flight of the accumulating kernels.  The store form (ACC = 1) holds what the in-place kernel holds and keeps
-// its depths; the add form (ACC = 2) holds one more 16-byte vector per group and step and runs at two thirds of those
-// depths (three quarters at D = 256): at least as many 16-byte loads in flight per wave as the in-place kernel has, no
-// scratch, 2-3 waves per SIMD by -Rpass-analysis=kernel-resource-usage (the table in DESIGN 4.1).
-#ifndef SGM_ACC_PF_FULL
-#define SGM_ACC_PF_FULL 12
-#endif
-#ifndef SGM_ACC_PF_PARTIAL
-#define SGM_ACC_PF_PARTIAL 16
-#endif
-#ifndef SGM_ACC_PF_2G
-#define SGM_ACC_PF_2G 8
-#endif
-#ifndef SGM_ACC_PF_3G
-#define SGM_ACC_PF_3G 5
-#endif
-#ifndef SGM_ACC_PF_4G
-#define SGM_ACC_PF_4G 4
-#endif
-
-namespace mccnn {
-// One route of the table below in the form the mode asks for: PFS steps in flight for the store form, PFA for the add form.
-template <int NG, int PFS, int PFA, bool FULL, int VPL, bool FAR>
-static void sgm_acc_launch(int mode, dim3 grid, hipStream_t s, const SgmAccParams &P)
-{
-    if (mode == MCCNN_SGM_ACC_STORE)
-        hipLaunchKernelGGL((sgm_pass_kernel<NG, PFS, FULL, VPL, FAR, 1, SgmAccParams>), grid, dim3(64), 0, s, P);
-    else
-        hipLaunchKernelGGL((sgm_pass_kernel<NG, PFA, FULL, VPL, FAR, 2, SgmAccParams>), grid, dim3(64), 0, s, P);
 }
 
 static bool sgm_overlap(const void *a, const void *b, size_t bytes)
@@ -889,35 +814,64 @@ static bool sgm_overlap(const void *a, const void *b, size_t bytes)
 }
 }  // namespace mccnn
 
+extern "C" int mccnn_sgm_pass(const float *image_left, const float *image_right, float *const *vol_hwd, const int *side,
+                              int n_jobs, int D, int H, int W, int rh, int rw, float p1, float p2, float q1, float q2,
+                              float thr, void *scratch, size_t scratch_bytes, mccnn_stream_t stream)
+{
+    using namespace mccnn;
+    const char *who = "mccnn_sgm_pass";
+    SgmGeometry g;
+    int rc = sgm_validate(who, image_left && image_right && vol_hwd && side && scratch, n_jobs, (sgm_vols)vol_hwd, nullptr,
+                          side, D, H, W, true, rh, rw, scratch, scratch_bytes, g);
+    if (rc) return rc;
+    rc = sgm_launch_flags(who, image_left, image_right, H, W, rh, rw, thr, g, (hipStream_t)stream);
+    if (rc) return rc;
+    return sgm_launch_pass(who, vol_hwd, side, n_jobs, D, H, W, rh, rw, p1, p2, q1, q2, g, (hipStream_t)stream);
+}
+
+// The two halves of mccnn_sgm_pass as calls of their own (round 6): the flag planes depend on the images, the direction
+// and the threshold only - a caller that advances the two volumes of a pair in separate launches (or on separate
+// streams) builds them once per direction and hands them to every pass.
+extern "C" int mccnn_sgm_flags(const float *image_left, const float *image_right, int D, int H, int W, int rh, int rw,
+                               float thr, void *flags, size_t flags_bytes, mccnn_stream_t stream)
+{
+    using namespace mccnn;
+    const char *who = "mccnn_sgm_flags";
+    SgmGeometry g;
+    const int rc = sgm_validate(who, image_left && image_right && flags, 1, nullptr, nullptr, nullptr, D, H, W, true, rh, rw,
+                                flags, flags_bytes, g);
+    if (rc) return rc;
+    return sgm_launch_flags(who, image_left, image_right, H, W, rh, rw, thr, g, (hipStream_t)stream);
+}
+
+extern "C" int mccnn_sgm_pass_flagged(float *const *vol_hwd, const int *side, int n_jobs, int D, int H, int W, int rh, int rw,
+                                      float p1, float p2, float q1, float q2, const void *flags, size_t flags_bytes,
+                                      mccnn_stream_t stream)
+{
+    using namespace mccnn;
+    const char *who = "mccnn_sgm_pass_flagged";
+    SgmGeometry g;
+    const int rc = sgm_validate(who, vol_hwd && side && flags, n_jobs, (sgm_vols)vol_hwd, nullptr, side, D, H, W, true, rh, rw,
+                                flags, flags_bytes, g);
+    if (rc) return rc;
+    return sgm_launch_pass(who, vol_hwd, side, n_jobs, D, H, W, rh, rw, p1, p2, q1, q2, g, (hipStream_t)stream);
+}
+
+// The out-of-place, accumulating pass (the paper's four independent directions): the routes of mccnn_sgm_pass, each in
+// the form `mode` selects.
 extern "C" int mccnn_sgm_pass_accumulate(const float *const *src_hwd, float *const *acc_hwd, const int *side, int n_jobs,
                                          int D, int H, int W, int rh, int rw, float p1, float p2, float q1, float q2,
                                          int mode, const void *flags, size_t flags_bytes, mccnn_stream_t stream)
 {
     using namespace mccnn;
     const char *who = "mccnn_sgm_pass_accumulate";
-    hipStream_t s = (hipStream_t)stream;
-    MCCNN_REQUIRE(src_hwd && acc_hwd && side && flags, MCCNN_E_INVALID, "%s: null pointer", who);
-    MCCNN_REQUIRE(n_jobs == 1 || n_jobs == 2, MCCNN_E_INVALID, "%s: n_jobs=%d must be 1 or 2", who, n_jobs);
     MCCNN_REQUIRE(mode == MCCNN_SGM_ACC_STORE || mode == MCCNN_SGM_ACC_ADD || mode == MCCNN_SGM_ACC_ADD_QUARTER,
                   MCCNN_E_INVALID, "%s: mode=%d is not MCCNN_SGM_ACC_STORE, _ADD or _ADD_QUARTER", who, mode);
-    MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "%s: non-positive size", who);
-    MCCNN_REQUIRE(D >= 2 && D <= kSgmMaxD, MCCNN_E_UNSUPPORTED,
-                  "%s: D=%d outside [2,%d] (the reference itself needs D >= 2, pf:550)", who, D, kSgmMaxD);
-    MCCNN_REQUIRE((rh == 0 && (rw == 1 || rw == -1)) || (rw == 0 && (rh == 1 || rh == -1)), MCCNN_E_INVALID,
-                  "%s: r=(%d,%d) is not an axis-aligned unit step (pf:484)", who, rh, rw);
-    MCCNN_REQUIRE(flags_bytes >= mccnn_sgm_scratch_bytes(H, W, D), MCCNN_E_SCRATCH, "%s: scratch %zu < %zu bytes", who,
-                  flags_bytes, mccnn_sgm_scratch_bytes(H, W, D));
-    const int pad = flag_pad(D);
-    const int pitch = W + 2 * pad;
-    const int Dp = mccnn_hwd_pitch(D);
-    const size_t vol_bytes = (size_t)H * W * Dp * 4;
-    const uint8_t *plane_l = reinterpret_cast<const uint8_t *>(flags);
-    const uint8_t *plane_r = plane_l + (((size_t)H * pitch + 127) & ~(size_t)127);
-    for (int j = 0; j < n_jobs; ++j) {
-        MCCNN_REQUIRE(src_hwd[j] != nullptr && acc_hwd[j] != nullptr, MCCNN_E_INVALID, "%s: null volume", who);
-        MCCNN_REQUIRE(side[j] == MCCNN_SIDE_LEFT || side[j] == MCCNN_SIDE_RIGHT, MCCNN_E_INVALID,
-                      "%s: side must be MCCNN_SIDE_LEFT or MCCNN_SIDE_RIGHT", who);
-    }
+    SgmGeometry g;
+    const int rc = sgm_validate(who, src_hwd && acc_hwd && side && flags, n_jobs, (sgm_vols)src_hwd, (sgm_vols)acc_hwd, side,
+                                D, H, W, true, rh, rw, flags, flags_bytes, g);
+    if (rc) return rc;
+    const size_t vol_bytes = (size_t)H * W * g.Dp * 4;
     // the pass reads a source line long after it has written other lines of the accumulator: the two never share memory
     for (int j = 0; j < n_jobs; ++j) {
         for (int k = 0; k < n_jobs; ++k)
@@ -930,61 +884,20 @@ extern "C" int mccnn_sgm_pass_accumulate(const float *const *src_hwd, float *con
     SgmAccParams P;
     for (int j = 0; j < 2; ++j) {
         const int jj = j < n_jobs ? j : 0;
-        const bool left = side[jj] == MCCNN_SIDE_LEFT;
         P.job[j].src = src_hwd[jj];
         P.job[j].acc = acc_hwd[jj];
-        P.job[j].aplane = left ? plane_l : plane_r;
-        P.job[j].bplane = left ? plane_r : plane_l;
-        P.job[j].dsign = left ? -1 : +1;
+        sgm_job_planes(P.job[j], side[jj], g);
     }
-    P.D = D; P.Dp = Dp; P.H = H; P.W = W; P.pitch = pitch; P.pad = pad; P.rh = rh; P.rw = rw;
-    P.p1[0] = p1; P.p1[1] = p1 / q1; P.p1[2] = p1 / q2;  // pf:538-541 (float32 divisions)
-    P.p2[0] = p2; P.p2[1] = p2 / q1; P.p2[2] = p2 / q2;
+    sgm_shape_and_penalties(P, g, D, H, W, p1, p2, q1, q2);
+    P.rh = rh; P.rw = rw;
     P.scale = mode == MCCNN_SGM_ACC_ADD_QUARTER ? 0.25f : 1.f;
     // (an axis with nothing to scan still launches: its single line is the seed line, and L = C enters the sum)
     const dim3 grid(rh == 0 ? H : W, n_jobs);
-    // the routes of mccnn_sgm_pass (sgm_launch_pass), each in the form `mode` selects
-    if (rh != 0 && vol_bytes >= ((size_t)1 << 32)) {
-        const int ng = cdiv(Dp, 256);
-        const bool full = D == 256 * ng;
-        if (ng == 1 && full)
-            sgm_acc_launch<1, 16, SGM_ACC_PF_FULL, true, 4, true>(mode, grid, s, P);
-        else if (ng == 1)
-            sgm_acc_launch<1, SGM_PF_PARTIAL, SGM_ACC_PF_PARTIAL, false, 4, true>(mode, grid, s, P);
-        else if (ng == 2 && full)
-            sgm_acc_launch<2, SGM_PF_2G, SGM_ACC_PF_2G, true, 4, true>(mode, grid, s, P);
-        else if (ng == 2)
-            sgm_acc_launch<2, SGM_PF_2G, SGM_ACC_PF_2G, false, 4, true>(mode, grid, s, P);
-        else if (ng == 3 && full)
-            sgm_acc_launch<3, SGM_PF_3G, SGM_ACC_PF_3G, true, 4, true>(mode, grid, s, P);
-        else if (ng == 3)
-            sgm_acc_launch<3, SGM_PF_3G, SGM_ACC_PF_3G, false, 4, true>(mode, grid, s, P);
-        else if (full)
-            sgm_acc_launch<4, SGM_PF_4G, SGM_ACC_PF_4G, true, 4, true>(mode, grid, s, P);
-        else
-            sgm_acc_launch<4, SGM_PF_4G, SGM_ACC_PF_4G, false, 4, true>(mode, grid, s, P);
-        return check_launch(who);
-    }
-    if (D == 256)
-        sgm_acc_launch<1, 16, SGM_ACC_PF_FULL, true, 4, false>(mode, grid, s, P);
-    else if (D == 192)
-        sgm_acc_launch<1, SGM_PF_PARTIAL, SGM_ACC_PF_PARTIAL, true, 3, false>(mode, grid, s, P);
-    else if (D > 128 && D < 192 && Dp % 3 == 0)
-        sgm_acc_launch<1, SGM_PF_PARTIAL, SGM_ACC_PF_PARTIAL, false, 3, false>(mode, grid, s, P);
-    else if (D < 256)
-        sgm_acc_launch<1, SGM_PF_PARTIAL, SGM_ACC_PF_PARTIAL, false, 4, false>(mode, grid, s, P);
-    else if (D == 512)
-        sgm_acc_launch<2, SGM_PF_2G, SGM_ACC_PF_2G, true, 4, false>(mode, grid, s, P);
-    else if (D < 512)
-        sgm_acc_launch<2, SGM_PF_2G, SGM_ACC_PF_2G, false, 4, false>(mode, grid, s, P);
-    else if (D == 768)
-        sgm_acc_launch<3, SGM_PF_3G, SGM_ACC_PF_3G, true, 4, false>(mode, grid, s, P);
-    else if (D < 768)
-        sgm_acc_launch<3, SGM_PF_3G, SGM_ACC_PF_3G, false, 4, false>(mode, grid, s, P);
-    else if (D == 1024)
-        sgm_acc_launch<4, SGM_PF_4G, SGM_ACC_PF_4G, true, 4, false>(mode, grid, s, P);
+    const SgmRoute route = sgm_route(D, rh != 0 && vol_bytes >= ((size_t)1 << 32));
+    if (mode == MCCNN_SGM_ACC_STORE)
+        sgm_launch_route<1>(route, grid, (hipStream_t)stream, P);
     else
-        sgm_acc_launch<4, SGM_PF_4G, SGM_ACC_PF_4G, false, 4, false>(mode, grid, s, P);
+        sgm_launch_route<2>(route, grid, (hipStream_t)stream, P);
     return check_launch(who);
 }
 
@@ -994,55 +907,35 @@ extern "C" int mccnn_sgm_first_pass(const float *image_left, const float *image_
                                     mccnn_stream_t stream)
 {
     using namespace mccnn;
-    MCCNN_REQUIRE(image_left && image_right && vol_dhw && vol_hwd && side && scratch, MCCNN_E_INVALID,
-                  "mccnn_sgm_first_pass: null pointer");
-    MCCNN_REQUIRE(n_jobs == 1 || n_jobs == 2, MCCNN_E_INVALID, "mccnn_sgm_first_pass: n_jobs=%d must be 1 or 2", n_jobs);
-    MCCNN_REQUIRE(H > 0 && W > 1, MCCNN_E_INVALID, "mccnn_sgm_first_pass: bad size");
-    MCCNN_REQUIRE(D >= 2 && D <= 256, MCCNN_E_UNSUPPORTED,
-                  "mccnn_sgm_first_pass: D=%d outside [2,256]; use mccnn_dhw_to_hwd + mccnn_sgm_pass", D);
-    MCCNN_REQUIRE(scratch_bytes >= mccnn_sgm_scratch_bytes(H, W, D), MCCNN_E_SCRATCH,
-                  "mccnn_sgm_first_pass: scratch %zu < %zu bytes", scratch_bytes, mccnn_sgm_scratch_bytes(H, W, D));
+    const char *who = "mccnn_sgm_first_pass";
+    SgmGeometry g;
+    int rc = sgm_validate(who, image_left && image_right && vol_dhw && vol_hwd && side && scratch, n_jobs, (sgm_vols)vol_dhw,
+                          (sgm_vols)vol_hwd, side, D, H, W, false, 0, 1, scratch, scratch_bytes, g);
+    if (rc) return rc;
     if ((size_t)D * H * W * 4 >= ((size_t)1 << 32)) {
         // the tile gather addresses all D planes from one descriptor: past its 4 GiB reach the layout change and the
         // pass run apart (same bits: the pass leaves the seed column as the layout change wrote it)
         for (int j = 0; j < n_jobs; ++j) {
-            MCCNN_REQUIRE(vol_dhw[j] && vol_hwd[j], MCCNN_E_INVALID, "mccnn_sgm_first_pass: null volume");
-            const int rc = mccnn_dhw_to_hwd(vol_dhw[j], vol_hwd[j], D, H, W, stream);
+            rc = mccnn_dhw_to_hwd(vol_dhw[j], vol_hwd[j], D, H, W, stream);
             if (rc) return rc;
         }
         return mccnn_sgm_pass(image_left, image_right, vol_hwd, side, n_jobs, D, H, W, 0, 1, p1, p2, q1, q2, thr, scratch,
                               scratch_bytes, stream);
     }
-    hipStream_t s = (hipStream_t)stream;
-    const int pad = flag_pad(D);
-    const int pitch = W + 2 * pad;
-    uint8_t *plane_l = reinterpret_cast<uint8_t *>(scratch);
-    uint8_t *plane_r = plane_l + (((size_t)H * pitch + 127) & ~(size_t)127);
-    const dim3 fgrid(cdiv(pitch, 256), H, 2), fblock(256);
-    hipLaunchKernelGGL(sgm_flags_kernel, fgrid, fblock, 0, s, image_left, image_right, H, W, 0, 1, thr, pitch, pad,
-                       plane_l, plane_r);
-    int rc = check_launch("mccnn_sgm_first_pass(flags)");
+    rc = sgm_launch_flags("mccnn_sgm_first_pass(flags)", image_left, image_right, H, W, 0, 1, thr, g, (hipStream_t)stream);
     if (rc) return rc;
     SgmFirstParams P;
     for (int j = 0; j < 2; ++j) {
         const int jj = j < n_jobs ? j : 0;
-        MCCNN_REQUIRE(vol_dhw[jj] && vol_hwd[jj], MCCNN_E_INVALID, "mccnn_sgm_first_pass: null volume");
-        MCCNN_REQUIRE(side[jj] == MCCNN_SIDE_LEFT || side[jj] == MCCNN_SIDE_RIGHT, MCCNN_E_INVALID,
-                      "mccnn_sgm_first_pass: side must be MCCNN_SIDE_LEFT or MCCNN_SIDE_RIGHT");
-        const bool left = side[jj] == MCCNN_SIDE_LEFT;
         P.job[j].src = vol_dhw[jj];
         P.job[j].dst = vol_hwd[jj];
-        P.job[j].aplane = left ? plane_l : plane_r;
-        P.job[j].bplane = left ? plane_r : plane_l;
-        P.job[j].dsign = left ? -1 : +1;
+        sgm_job_planes(P.job[j], side[jj], g);
     }
-    P.D = D; P.Dp = mccnn_hwd_pitch(D); P.H = H; P.W = W; P.pitch = pitch; P.pad = pad;
-    P.p1[0] = p1; P.p1[1] = p1 / q1; P.p1[2] = p1 / q2;
-    P.p2[0] = p2; P.p2[1] = p2 / q1; P.p2[2] = p2 / q2;
+    sgm_shape_and_penalties(P, g, D, H, W, p1, p2, q1, q2);
     const dim3 grid(H, n_jobs), block(64);
     if (D == 256)
-        hipLaunchKernelGGL((sgm_first_pass_kernel<true>), grid, block, 0, s, P);
+        hipLaunchKernelGGL((sgm_first_pass_kernel<true>), grid, block, 0, (hipStream_t)stream, P);
     else
-        hipLaunchKernelGGL((sgm_first_pass_kernel<false>), grid, block, 0, s, P);
-    return check_launch("mccnn_sgm_first_pass");
+        hipLaunchKernelGGL((sgm_first_pass_kernel<false>), grid, block, 0, (hipStream_t)stream, P);
+    return check_launch(who);
 }

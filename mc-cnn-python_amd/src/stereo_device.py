@@ -797,6 +797,10 @@ def _sgm_penalties(sgm_P1, sgm_P2, sgm_Q1, sgm_Q2, sgm_D, sgm_V):
     return _f32(sgm_P1), _f32(sgm_P1 / sgm_V), _f32(sgm_P2), _f32(sgm_Q1), _f32(sgm_Q2), _f32(sgm_D)
 
 
+def _sgm_p1(r, p1h, p1v):
+    return p1h if r[0] == 0 else p1v
+
+
 def sgm_pass_hwd(image_left, image_right, vols_hwd, sides, D, r, p1, p2, q1, q2, thr, scratch):
     """One direction, in place on 1 or 2 HWD volumes.  p1..thr are already float32-rounded Python floats."""
     H, W = image_left.shape
@@ -809,16 +813,21 @@ def sgm_pass_hwd(image_left, image_right, vols_hwd, sides, D, r, p1, p2, q1, q2,
 SGM_DIRECTIONS = ((0, 1), (0, -1), (-1, 0), (1, 0))  # right, left, up, bottom (pf:194-208)
 
 
+def sgm_flags_hwd(image_left, image_right, D, r, thr, flags):
+    """The flag planes of one direction into `flags` (mccnn_sgm_flags); thr is already float32-rounded."""
+    H, W = image_left.shape
+    hip.check(hip.load().mccnn_sgm_flags(hip.ptr(image_left), hip.ptr(image_right), int(D), H, W, int(r[0]), int(r[1]), thr,
+                                         hip.ptr(flags), flags.numel(), hip.stream()), "mccnn_sgm_flags")
+
+
 def sgm_flag_planes(image_left, image_right, D, sgm_D, out=None):
     """The flag planes of all four directions (mccnn_sgm_flags: which pixels' intensity step along r reaches sgm_D,
     pf:504-533), one buffer per direction: they depend on the images only, so a pair builds them once - off the critical
     path - and every pass of both volumes reads them (sgm_average_hwd(flags=...))."""
     H, W = image_left.shape
-    thr = _f32(sgm_D)
     planes = out if out is not None else [sgm_scratch(H, W, D, image_left.device) for _ in SGM_DIRECTIONS]
     for r, buf in zip(SGM_DIRECTIONS, planes):
-        hip.check(hip.load().mccnn_sgm_flags(hip.ptr(image_left), hip.ptr(image_right), int(D), H, W, int(r[0]), int(r[1]),
-                                             thr, hip.ptr(buf), buf.numel(), hip.stream()), "mccnn_sgm_flags")
+        sgm_flags_hwd(image_left, image_right, D, r, _f32(sgm_D), buf)
     return planes
 
 
@@ -843,10 +852,9 @@ def sgm_average_hwd(image_left, image_right, vols_hwd, sides, D, sgm_P1, sgm_P2,
         # two-volume launch: half the bytes, and it runs beside whatever the other volume's chain is doing)
         timer.start("sgm_pass" if len(vols_hwd) == 2 else "sgm_pass_one_volume")
         if flags is not None:
-            sgm_pass_flagged_hwd(vols_hwd, sides, D, r, p1h if r[0] == 0 else p1v, p2, q1, q2, flags[i])
+            sgm_pass_flagged_hwd(vols_hwd, sides, D, r, _sgm_p1(r, p1h, p1v), p2, q1, q2, flags[i])
         else:
-            sgm_pass_hwd(image_left, image_right, vols_hwd, sides, D, r, p1h if r[0] == 0 else p1v, p2, q1, q2, thr,
-                         scratch)
+            sgm_pass_hwd(image_left, image_right, vols_hwd, sides, D, r, _sgm_p1(r, p1h, p1v), p2, q1, q2, thr, scratch)
         timer.stop()
 
 
@@ -874,15 +882,12 @@ def sgm_average_independent_hwd(image_left, image_right, vols_hwd, spares_hwd, s
     flags: sgm_flag_planes() of the same images, D and sgm_D; without them every direction's planes are built into
     `scratch` in front of its pass."""
     p1h, p1v, p2, q1, q2, thr = _sgm_penalties(sgm_P1, sgm_P2, sgm_Q1, sgm_Q2, sgm_D, sgm_V)
-    H, W = image_left.shape
     for i, (r, mode) in enumerate(zip(SGM_DIRECTIONS, SGM_ACC_MODES)):
         timer.start("sgm_pass_accumulate" if len(vols_hwd) == 2 else "sgm_pass_accumulate_one_volume")
         planes = flags[i] if flags is not None else scratch
         if flags is None:
-            hip.check(hip.load().mccnn_sgm_flags(hip.ptr(image_left), hip.ptr(image_right), int(D), H, W, int(r[0]),
-                                                 int(r[1]), thr, hip.ptr(scratch), scratch.numel(), hip.stream()),
-                      "mccnn_sgm_flags")
-        sgm_pass_accumulate_hwd(vols_hwd, spares_hwd, sides, D, r, p1h if r[0] == 0 else p1v, p2, q1, q2, mode, planes)
+            sgm_flags_hwd(image_left, image_right, D, r, thr, scratch)
+        sgm_pass_accumulate_hwd(vols_hwd, spares_hwd, sides, D, r, _sgm_p1(r, p1h, p1v), p2, q1, q2, mode, planes)
         timer.stop()
     return list(spares_hwd), list(vols_hwd)
 
@@ -913,8 +918,7 @@ def sgm_average_from_dhw(image_left, image_right, vols_dhw, vols_hwd, sides, D, 
         timer.stop()
     for r in rest:
         timer.start("sgm_pass")
-        sgm_pass_hwd(image_left, image_right, vols_hwd, sides, D, r, p1h if r[0] == 0 else p1v, p2, q1, q2, thr,
-                     scratch)
+        sgm_pass_hwd(image_left, image_right, vols_hwd, sides, D, r, _sgm_p1(r, p1h, p1v), p2, q1, q2, thr, scratch)
         timer.stop()
 
 

@@ -361,3 +361,43 @@ def test_sgm_flag_planes_built_once_equal_the_pass_that_builds_its_own(sd, H, W,
     for name, (x, y) in (("planes built once", (a, b)), ("one-volume launches on two streams", (c, d)), ("mccnn_sgm_pass", (e, f))):
         assert_bits(sd.hwd_to_dhw(x, D).cpu().numpy(), want[0], "SGM_average, %s (left)" % name)
         assert_bits(sd.hwd_to_dhw(y, D).cpu().numpy(), want[1], "SGM_average, %s (right)" % name)
+
+
+@pytest.mark.parametrize("D", [2, 5, 64, 130, 150, 192, 255, 256, 257, 400, 512, 700, 768, 1000, 1024])
+def test_in_place_pass_on_every_route_against_the_oracle(sd, D):
+    """mccnn_sgm_pass and mccnn_sgm_pass_flagged, one direction at a time, on every route of the envelope (the disparity
+    counts, shapes and inputs of test_paper_sgm_gpu.test_every_route_of_the_envelope_against_the_helper: ragged H and W
+    longer than twice the deepest pipeline, all three penalty classes, about 1 % of the costs +inf): each direction and
+    side, as a two-job launch and as two one-job launches, against oracle.semi_global_matching on a copy - every bit."""
+    import oracle as o
+    from test_paper_sgm_gpu import CHOICE, SGM_HP, _images_np, _volume_np
+    H, W = 41 + D % 7, 67 + D % 5
+    L, R = _images_np(H, W, seed=D)
+    l, r = dev(L[:, :, 0]), dev(R[:, :, 0])
+    vols = [dev(_volume_np(D, H, W, seed=D + 1 + side, inf=0.01)) for side in (0, 1)]
+    p1h, p1v, p2, q1, q2, thr = sd._sgm_penalties(*SGM_HP)
+    scratch = sd.sgm_scratch(H, W, D, l.device)
+    planes = sd.sgm_flag_planes(l, r, D, SGM_HP[4])
+    for i, rr in enumerate(sd.SGM_DIRECTIONS):
+        p1 = p1h if rr[0] == 0 else p1v
+        want = []
+        for side in (0, 1):
+            v = vols[side].cpu().numpy().copy()
+            sgm_p1 = SGM_HP[0] if rr[0] == 0 else SGM_HP[0] / SGM_HP[5]           # P1, along a column P1 / V (pf:204)
+            o.semi_global_matching(L, R, v, rr, sgm_p1, *SGM_HP[1:5], CHOICE[side])
+            want.append(v)
+        for flagged in (False, True):
+            def run(hwd, sides):
+                if flagged:
+                    sd.sgm_pass_flagged_hwd(hwd, sides, D, rr, p1, p2, q1, q2, planes[i])
+                else:
+                    sd.sgm_pass_hwd(l, r, hwd, sides, D, rr, p1, p2, q1, q2, thr, scratch)
+            both = [sd.dhw_to_hwd(v) for v in vols]
+            run(both, [0, 1])
+            ones = [sd.dhw_to_hwd(v) for v in vols]
+            for side in (1, 0):
+                run([ones[side]], [side])
+            for side in (0, 1):
+                what = "D=%d r=%s side %d%s" % (D, rr, side, ", planes built once" if flagged else "")
+                assert_bits(sd.hwd_to_dhw(both[side], D).cpu().numpy(), want[side], what + ", two jobs")
+                assert_bits(sd.hwd_to_dhw(ones[side], D).cpu().numpy(), want[side], what + ", one job")

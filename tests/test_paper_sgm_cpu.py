@@ -1,6 +1,6 @@
 """CPU: the paper-faithful SGM stage (four independent directions, averaged; tests/paper_sgm_reference.py) pinned
-against the real reference's single-direction volumes in tests/golden/, the argument validation of
-mccnn_sgm_pass_accumulate without a GPU, the command-line flag and the matcher extra, and the reason for having it:
+against the real reference's single-direction volumes in tests/golden/, the argument validation of the five SGM entry
+points without a GPU, the command-line flag and the matcher extra, and the reason for having it:
 on synthetic pairs the paper's stage beats the reference's sequential composition."""
 import ctypes
 import os
@@ -42,13 +42,28 @@ def test_both_sides_helper_has_the_signature_of_sgm_average(golden_cases):
     assert_bits(r, ps.average4([g["sgm_%s_r" % d] for d in ps.NAMES]), name + " right")
 
 
-# ---- mccnn_sgm_pass_accumulate: validation before any launch -------------------------------------------------------
-class _Args(object):
-    """A valid call on fake addresses (nothing is dereferenced before validation ends; every case below fails it)."""
+# ---- the SGM entry points: validation before any launch ------------------------------------------------------------
+# the pointer arguments of each entry point, by the names _Args gives them
+POINTERS = {
+    "mccnn_sgm_pass": ("left", "right", "src", "side", "flags"),
+    "mccnn_sgm_flags": ("left", "right", "flags"),
+    "mccnn_sgm_pass_flagged": ("src", "side", "flags"),
+    "mccnn_sgm_pass_accumulate": ("src", "acc", "side", "flags"),
+    "mccnn_sgm_first_pass": ("left", "right", "src", "acc", "side", "flags"),
+}
+ENTRIES = tuple(POINTERS)
+WITH_JOBS = tuple(e for e in ENTRIES if "side" in POINTERS[e])
+WITH_DIRECTION = tuple(e for e in ENTRIES if e != "mccnn_sgm_first_pass")
 
-    def __init__(self, hip, n_jobs=1, D=8, H=4, W=12):
+
+class _Args(object):
+    """A valid call of one entry point on fake addresses (nothing is dereferenced before validation ends; every case below
+    fails it).  src / acc: the volume lists - the in-place passes have `src` only (their vol_hwd), the first pass reads
+    `src` (plane-major) and writes `acc`."""
+
+    def __init__(self, hip, n_jobs=1, D=8, H=4, W=12, entry="mccnn_sgm_pass_accumulate"):
         lib = hip.load()
-        self.lib, self.hip = lib, hip
+        self.lib, self.hip, self.entry = lib, hip, entry
         self.D, self.H, self.W, self.n = D, H, W, n_jobs
         vol = H * W * lib.mccnn_hwd_pitch(D) * 4
         self.vol = vol
@@ -58,17 +73,27 @@ class _Args(object):
         self.side = [hip.MCCNN_SIDE_LEFT, hip.MCCNN_SIDE_RIGHT]
         self.r = (0, 1)
         self.mode = hip.MCCNN_SGM_ACC_STORE
+        self.images = [0x60000000, 0x68000000]
         self.flags = 0x70000000
         self.flags_bytes = lib.mccnn_sgm_scratch_bytes(H, W, D)
 
-    def call(self, src_null=False, acc_null=False, side_null=False):
+    def call(self, src_null=False, acc_null=False, side_null=False, left_null=False, right_null=False):
         vp2, i2 = ctypes.c_void_p * 2, ctypes.c_int * 2
         src = None if src_null else vp2(*self.src)
         acc = None if acc_null else vp2(*self.acc)
         side = None if side_null else i2(*self.side)
-        rc = self.lib.mccnn_sgm_pass_accumulate(src, acc, side, self.n, self.D, self.H, self.W, self.r[0], self.r[1], 2.3,
-                                                55.9, 4.0, 8.0, self.mode, ctypes.c_void_p(self.flags), self.flags_bytes,
-                                                None)
+        left = None if left_null else ctypes.c_void_p(self.images[0])
+        right = None if right_null else ctypes.c_void_p(self.images[1])
+        shape, r, pen = (self.D, self.H, self.W), (self.r[0], self.r[1]), (2.3, 55.9, 4.0, 8.0)
+        tail = (ctypes.c_void_p(self.flags), self.flags_bytes, None)
+        args = {
+            "mccnn_sgm_pass": (left, right, src, side, self.n) + shape + r + pen + (0.08,) + tail,
+            "mccnn_sgm_flags": (left, right) + shape + r + (0.08,) + tail,
+            "mccnn_sgm_pass_flagged": (src, side, self.n) + shape + r + pen + tail,
+            "mccnn_sgm_pass_accumulate": (src, acc, side, self.n) + shape + r + pen + (self.mode,) + tail,
+            "mccnn_sgm_first_pass": (left, right, src, acc, side, self.n) + shape + pen + (0.08,) + tail,
+        }[self.entry]
+        rc = getattr(self.lib, self.entry)(*args)
         return rc, self.lib.mccnn_last_error_string().decode()
 
 
@@ -159,6 +184,65 @@ def test_accumulate_refuses_bad_job_counts_and_sides(hip):
     a.side[0] = 7
     rc, msg = a.call()
     assert rc == hip.MCCNN_E_INVALID and "side" in msg
+
+
+# the same cases on every entry point (an entry point without the argument leaves the case out)
+@pytest.mark.parametrize("entry", ENTRIES)
+def test_every_entry_point_refuses_null_pointers(hip, entry):
+    for name in POINTERS[entry]:
+        a = _Args(hip, entry=entry)
+        if name == "flags":
+            a.flags = None
+            rc, msg = a.call()
+        else:
+            rc, msg = a.call(**{name + "_null": True})
+        assert rc == hip.MCCNN_E_INVALID and "null pointer" in msg and msg.startswith(entry + ":"), (name, rc, msg)
+    for which in ("src", "acc"):                             # a null second volume
+        if which in POINTERS[entry]:
+            a = _Args(hip, n_jobs=2, entry=entry)
+            getattr(a, which)[1] = None
+            rc, msg = a.call()
+            assert rc == hip.MCCNN_E_INVALID and "null volume" in msg, (which, rc, msg)
+
+
+@pytest.mark.parametrize("entry", WITH_JOBS)
+def test_every_entry_point_refuses_bad_job_counts_and_sides(hip, entry):
+    for n in (0, 3):
+        a = _Args(hip, entry=entry)
+        a.n = n
+        rc, msg = a.call()
+        assert rc == hip.MCCNN_E_INVALID and "n_jobs" in msg, (n, rc, msg)
+    a = _Args(hip, entry=entry)
+    a.side[0] = 7
+    rc, msg = a.call()
+    assert rc == hip.MCCNN_E_INVALID and "side" in msg, (rc, msg)
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+def test_every_entry_point_refuses_disparity_counts_outside_its_range(hip, entry):
+    first = entry == "mccnn_sgm_first_pass"                  # one 256-disparity group
+    for D in ((0, 1, 257) if first else (0, 1, 1025, 4096)):
+        a = _Args(hip, entry=entry)
+        a.D = D
+        rc, msg = a.call()
+        assert rc == hip.MCCNN_E_UNSUPPORTED and ("outside [2,256]" if first else "outside [2,1024]") in msg, (D, rc, msg)
+
+
+@pytest.mark.parametrize("entry", WITH_DIRECTION)
+def test_every_entry_point_refuses_directions_that_are_not_unit_axis_steps(hip, entry):
+    for r in ((0, 0), (1, 1), (-1, 1), (0, 2), (2, 0), (1, -1)):
+        a = _Args(hip, entry=entry)
+        a.r = r
+        rc, msg = a.call()
+        assert rc == hip.MCCNN_E_INVALID and "axis-aligned unit step" in msg, (r, rc, msg)
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+def test_every_entry_point_refuses_short_flag_planes(hip, entry):
+    a = _Args(hip, entry=entry)
+    a.flags_bytes -= 1
+    rc, msg = a.call()
+    assert rc == hip.MCCNN_E_SCRATCH and "scratch" in msg, (rc, msg)
 
 
 def test_abi_version_is_unchanged(hip):
