@@ -6,8 +6,13 @@
  * (mc-cnn-python_amd/) never links or imports anything under oracle/ and fails loudly without its HIP library.
  *
  * Every function restates one reference function, loop for loop in the reference's own evaluation order so that
- * float32 results are bit-identical to the reference run under NumPy 2.x (pinned by the .npz files in tests/golden, which
- * were produced by executing /root/reference/src/process_functional.py itself - see tests/golden/gen_golden.py).
+ * float32 results are bit-identical to the reference run under NumPy 2.x.  Pinned by the .npz files in tests/golden, which
+ * were produced by executing /root/reference/src/process_functional.py itself: ref_*.npz (tests/golden/gen_golden.py,
+ * whole pairs at the default settings, D <= 16; tests/test_oracle_golden.py) and route_*.npz
+ * (tests/golden/gen_route_golden.py: D up to 1024, arms up to 31, all penalty classes, +-inf / -0.0, W = 255 .. 257;
+ * tests/test_reference_routes_cpu.py), and by tests/test_oracle_vs_reference_cpu.py, which runs the reference beside
+ * these functions wherever it is present.  One stated departure: a NaN cost in orc_sgm_pass (the reference's np.amin
+ * propagates it to the whole line, the `<` chain here does not).
  * "pf:" abbreviates /root/reference/src/process_functional.py.
  *
  * Build: gcc -O2 -ffp-contract=off -fno-fast-math -shared -fPIC (see oracle/Makefile).  -ffp-contract=off is

@@ -75,6 +75,35 @@ def assert_bits(a, b, what):
     assert_bits_strict(a, b, what)
 
 
+class Tally(object):
+    """Collects the comparisons of one stage or fixture so that every case runs and the failures are reported together:
+    bits() for float32 (bits_strict), equal() for integer arrays (values and dtype), settle() asserts."""
+
+    def __init__(self, what):
+        self.what, self.failures, self.total = what, [], 0
+
+    def bits(self, got, want, what):
+        self.total += 1
+        if not bits_strict(got, want):
+            self.failures.append("%s: %s" % (what, _describe(got, want)))
+
+    def equal(self, got, want, what):
+        self.total += 1
+        got, want = np.asarray(got), np.asarray(want)
+        if got.dtype != want.dtype or not np.array_equal(got, want):
+            self.failures.append("%s: %s %s against %s %s" % (what, got.dtype, got.shape, want.dtype, want.shape))
+
+    def check(self, ok, what):
+        self.total += 1
+        if not ok:
+            self.failures.append(what)
+
+    def settle(self, floor=1):
+        assert not self.failures, "%s: %d of %d comparisons differ:\n%s" % (self.what, len(self.failures), self.total,
+                                                                            "\n".join(self.failures[:40]))
+        assert self.total >= floor, "%s: %d comparisons, the matrix has %d" % (self.what, self.total, floor)
+
+
 @contextlib.contextmanager
 def module_setting(module, name, value):
     """Sets a module-level switch (process_functional.CBCA_ORDER, ...) for a block and puts back whatever stood there,

@@ -1,5 +1,8 @@
 """CPU: the C oracle (oracle/mccnn_oracle.c) against the golden vectors that were produced by RUNNING the reference
-(tests/golden/gen_golden.py).  Every stage a2..a11 must be bit-identical; this is what pins the oracle."""
+(tests/golden/gen_golden.py).  Every stage a2..a11 must be bit-identical.  What is pinned here: whole pairs of one scene
+class at the default hyper-parameters, D <= 16, W <= 48, cbca_distance 14.  The rest of what pins the oracle:
+test_reference_routes_cpu.py (tests/golden/route_*.npz: D up to 1024, arms up to 31, every SGM penalty class, special
+values, made by gen_route_golden.py) and test_oracle_vs_reference_cpu.py (the reference run live, where it is present)."""
 import numpy as np
 import pytest
 
