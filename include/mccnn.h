@@ -45,7 +45,7 @@ extern "C" {
 
 typedef void *mccnn_stream_t; /* hipStream_t */
 
-#define MCCNN_ABI_VERSION 7 /* 2: window-mask plane, *_hwd entry points; 3: saturation flags; 4: program-driven CBCA; 5: skip programs; 6: one-volume launches; 7: refresh launches, SGM flag planes as a call of their own; still 7 with the mccnn_ingest_* and the mccnn_decision_* / mccnn_cost_volume_accurate* entry points and mccnn_sample_patches: purely additive, nothing that existed changed */
+#define MCCNN_ABI_VERSION 7 /* 2: window-mask plane, *_hwd entry points; 3: saturation flags; 4: program-driven CBCA; 5: skip programs; 6: one-volume launches; 7: refresh launches, SGM flag planes as a call of their own; still 7 with the mccnn_ingest_* and the mccnn_decision_* / mccnn_cost_volume_accurate* entry points and mccnn_sample_patches, and with mccnn_evaluate: purely additive, nothing that existed changed */
 
 #define MCCNN_E_INVALID (-1)     /* bad argument (null pointer, non-positive size, unsupported shape) */
 #define MCCNN_E_UNSUPPORTED (-2) /* shape outside what the kernels were built for (e.g. D > 1024 for SGM) */
@@ -447,6 +447,35 @@ typedef struct { int32_t image; float cy, cx; float m[4]; float gain, bias; } mc
 int mccnn_sample_patches(const float *pool, const mccnn_sample_image_t *images, int n_images,
                          const mccnn_sample_t *records, int N, int ps, float *out /* [N][ps][ps] */,
                          mccnn_stream_t stream);
+
+/* ---- evaluation of a disparity map against ground truth, on the device (the Middlebury SDK's evaldisp, as remembered) ---
+ * Regions.  A pixel belongs to `all` when gt is finite (+inf is Middlebury's "unknown"; NaN and -inf are treated the
+ *   same), to `nonocc` when it is also mask == 255 (every other mask value - 0 unknown, 128 occluded, anything else -
+ *   excludes it); with mask == NULL nonocc equals all.
+ * Per pixel of a region: n_valid += 1.  disp not finite or disp < 0 (the pipeline's -1 for "no winner", any NaN; -0.0f is
+ *   valid): n_invalid += 1 and nothing else.  Otherwise err = fabsf(disp - gt), one float32 subtraction; n_bad[k] += 1
+ *   when err > thresholds[k] (strict float32 compare); the pixel's terms are a = (double)err and q = (double)err *
+ *   (double)err (exact in float64).
+ * Sums, defined to the bit.  Pixels are numbered i = h*W + w and cut into chunks of 1024 consecutive indices.  A chunk's
+ *   1024 terms (+0.0 for a pixel outside the region, invalid or past the end) are reduced by the stride-halving tree
+ *   for s = 512, 256, ..., 1: x[j] += x[j+s] for j < s; the chunk partials are added in ascending chunk order starting
+ *   from +0.0.  The same tree serves sum_abs (terms a) and sum_sq (terms q) of both regions.
+ * accumulate == 0: result is overwritten, n_bad[k] for k >= n_thr written as 0.  Otherwise the counts are added to what
+ *   result holds (n_bad[k], k >= n_thr, left untouched) and each sum becomes old + this call's total, one float64
+ *   addition: a list's totals build up on the device with no read-back per pair.
+ * thresholds: HOST array of n_thr values, read at call time and passed to the kernel by value.
+ * scratch: mccnn_evaluate_scratch_bytes(H, W) bytes (per chunk: four float64 partials and twenty uint32 counts), 8-byte
+ *   aligned like result, private to one call in flight.  Two launches, no synchronisation, no atomics: capturable.
+ * Refused before any HIP call: null disp / gt / thresholds / result / scratch, non-positive sizes, n_thr outside 1..8, a
+ *   NaN threshold, misaligned scratch / result (MCCNN_E_INVALID); scratch_bytes too small (MCCNN_E_SCRATCH); H*W above
+ *   1024 * (2^31 - 1), the chunk index being the workgroup index of the first launch (MCCNN_E_UNSUPPORTED). */
+#define MCCNN_EVAL_MAX_THRESHOLDS 8
+typedef struct { uint64_t n_valid, n_invalid, n_bad[MCCNN_EVAL_MAX_THRESHOLDS]; double sum_abs, sum_sq; } mccnn_eval_region_t; /* 96 bytes */
+typedef struct { mccnn_eval_region_t all, nonocc; } mccnn_eval_t;                                                              /* 192 bytes */
+size_t mccnn_evaluate_scratch_bytes(int H, int W); /* 0 for non-positive sizes */
+int mccnn_evaluate(const float *disp, const float *gt, const uint8_t *mask /* may be NULL */, int H, int W,
+                   const float *thresholds /* HOST, n_thr values */, int n_thr, int accumulate,
+                   mccnn_eval_t *result /* device */, void *scratch, size_t scratch_bytes, mccnn_stream_t stream);
 
 /* ---- a1 epilogues of the conv stack (model.py:51-64, 111-125) ------------------------------------------------
  * mccnn_bias_act: x[n][c][i] = act(x[n][c][i] + bias[c]) in place on an NCHW tensor (plane = H*W elements) -

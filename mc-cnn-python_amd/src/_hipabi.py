@@ -26,6 +26,8 @@ MCCNN_E_INVALID = -1      # include/mccnn.h: bad argument
 MCCNN_E_UNSUPPORTED = -2  # shape / parameter the kernels are not built for
 MCCNN_E_SCRATCH = -3      # scratch buffer too small
 
+MCCNN_EVAL_MAX_THRESHOLDS = 8
+
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _f = ctypes.c_float
@@ -100,7 +102,23 @@ SIGNATURES = {
     "mccnn_ingest_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "mccnn_ingest_u8_pair": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "mccnn_sample_patches": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    "mccnn_evaluate_scratch_bytes": (_sz, [_i, _i]),
+    "mccnn_evaluate": (_i, [_vp, _vp, _vp, _i, _i, ctypes.POINTER(_f), _i, _i, _vp, _vp, _sz, _vp]),
 }
+
+
+
+class EvalRegion(ctypes.Structure):
+    """mccnn_eval_region_t, 96 bytes."""
+    _fields_ = [("n_valid", ctypes.c_uint64), ("n_invalid", ctypes.c_uint64),
+                ("n_bad", ctypes.c_uint64 * MCCNN_EVAL_MAX_THRESHOLDS), ("sum_abs", ctypes.c_double),
+                ("sum_sq", ctypes.c_double)]
+
+
+class EvalResult(ctypes.Structure):
+    """mccnn_eval_t, 192 bytes: what mccnn_evaluate writes."""
+    _fields_ = [("all", EvalRegion), ("nonocc", EvalRegion)]
+
 
 _lib = None
 

@@ -199,10 +199,17 @@ def pinned_u8(a):
     return t
 
 
-def make_reader(paths, check_shape, to_host_buffer=pinned_u8):
+def pinned(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).pin_memory()
+
+
+def make_reader(paths, check_shape, to_host_buffer=pinned_u8, truth=None):
     """read(index) for ListPipeline on top of match.py's file layout.  `paths(index)` -> dict(left, right, calib, out,
     out_time, out_img, res_dir, img_dir); `check_shape(H, W, ndisp)` raises for a pair outside the envelope - before
-    anything of that pair is decoded, let alone reaches the GPU."""
+    anything of that pair is decoded, let alone reaches the GPU.  `truth(left_path)` (match.py --evaluate:
+    evaluation.load_ground_truth) -> (ground truth, mask or None) or None: read here as well, into pinned memory beside
+    the images (job.gt, job.mask; job.gt None = a pair without ground truth)."""
     def read(index):
         p = paths(index)
         height, width, ndisp = util.parseCalib(p["calib"])
@@ -216,13 +223,21 @@ def make_reader(paths, check_shape, to_host_buffer=pinned_u8):
             if a.shape[:2] != (height, width):
                 raise ValueError("%s is %dx%d, its calib.txt says %dx%d" % (which, a.shape[1], a.shape[0], width, height))
         channels = 1 if left.ndim == 2 else left.shape[2]
+        gt = mask = None
+        found = truth(p["left"]) if truth is not None else None
+        if found is not None:
+            if found[0].shape != (height, width):
+                raise ValueError("%s: the ground truth is %s, the disparity map %s (resampling is not supported)"
+                                 % (p["left"], found[0].shape, (height, width)))
+            gt, mask = pinned(found[0]), (pinned(found[1]) if found[1] is not None else None)
         return Job(index, p["left"], (height, width, ndisp, channels), height=height, width=width, ndisp=ndisp,
-                   left=to_host_buffer(left), right=to_host_buffer(right), paths=p)
+                   left=to_host_buffer(left), right=to_host_buffer(right), paths=p, gt=gt, mask=mask)
     return read
 
 
-def make_writer(rank=0, log=print):
-    """write(job, map, seconds) for ListPipeline: the three files of match.py, with the existing util functions."""
+def make_writer(rank=0, log=print, report=None, eval_file="evalMCCNN.json"):
+    """write(job, map, seconds) for ListPipeline: the three files of match.py, with the existing util functions; with a
+    `report` (evaluation.ListReport) also the pair's evaluation, once its 192 bytes are on the host."""
     from datetime import datetime
 
     def write(job, disparity, seconds):
@@ -231,18 +246,22 @@ def make_writer(rank=0, log=print):
         util.writePfm(disparity, p["out"])
         util.saveTimeFile(seconds, p["out_time"])
         log("[{}] {}: {:.3f} s -> {}".format(rank, datetime.now(), seconds, p["out"]))
+        score = getattr(job, "score", None)       # of the map these files hold, or of the repeat that replaces it
+        if report is not None and score is not None:
+            report.pair(job.index, job.name, score.metrics(), os.path.join(p["res_dir"], eval_file))
     return write
 
 
 class Ticket(object):
-    def __init__(self, host, done):
-        self.host, self.done = host, done
+    def __init__(self, host, done, device_map=None):
+        self.host, self.done, self.device_map = host, done, device_map
+        self.truth = None            # with --evaluate: the pair's (ground truth, mask) on the device
 
 
 class MatcherBackend(object):
     """ListPipeline's backend on StereoMatchers: one matcher and one stream per slot, as match.py --pairs_in_flight."""
 
-    def __init__(self, matchers, streams, make_library_matcher, rank=0, log=print):
+    def __init__(self, matchers, streams, make_library_matcher, rank=0, log=print, report=None):
         import torch
         self.torch = torch
         self.matchers, self.streams = matchers, streams
@@ -251,6 +270,11 @@ class MatcherBackend(object):
         self.rank, self.log = rank, log
         self._redo_left = 0
         self._redo_matcher = None
+        # match.py --evaluate (evaluation.ListReport).  The evaluation is enqueued behind the graph replay on the slot's
+        # stream, NOT inside the captured graph: the thresholds stay call-time arguments, and the running total takes a
+        # pair only in retire(), once it is known which map is kept (the saturation redo) - in list order.
+        self.report = report
+        self.evaluator = report.evaluator if report is not None else None
 
     def thread_init(self):
         self.torch.cuda.set_device(self.device)      # the current device is a per-thread setting
@@ -266,7 +290,12 @@ class MatcherBackend(object):
         host.copy_(disparity, non_blocking=True)
         done = torch.cuda.Event()
         done.record()
-        return Ticket(host, done)
+        return Ticket(host, done, disparity)
+
+    def _score(self, slot, job, ticket, truth):
+        """The evaluation of ticket.device_map behind it on the current stream; the writer finds it as job.score."""
+        ticket.truth = truth
+        job.score = self.evaluator.score(ticket.device_map, truth[0], truth[1], slot)
 
     def submit(self, slot, job, mode):
         self.log("[{}] pair {}: {}  ({}x{}, ndisp {}, {} byte(s) per pixel, {})".format(
@@ -277,7 +306,15 @@ class MatcherBackend(object):
                 disparity = m.match_u8(job.left, job.right, job.ndisp)
             else:
                 disparity = m.match_graph_u8(job.left, job.right, job.ndisp)
-            return self._to_host(disparity)
+            ticket = self._to_host(disparity)
+            if self.evaluator is not None:
+                if getattr(job, "gt", None) is None:
+                    self.report.skip(job.index, job.name)
+                else:
+                    dev = m.device
+                    self._score(slot, job, ticket, (job.gt.to(dev, non_blocking=True),
+                                                    job.mask.to(dev, non_blocking=True) if job.mask is not None else None))
+            return ticket
 
     def wait(self, ticket):
         ticket.done.synchronize()
@@ -292,6 +329,7 @@ class MatcherBackend(object):
         if m0.saturation_checked() and m0.features_saturated():
             self._redo_left = len(self.matchers)
         if self._redo_left <= 0:
+            self._commit(slot, ticket)
             return None
         self._redo_left -= 1
         if self._redo_matcher is None:
@@ -300,4 +338,16 @@ class MatcherBackend(object):
         disparity = self._redo_matcher.match_u8(job.left, job.right, job.ndisp)
         again = self._to_host(disparity)
         self.torch.cuda.synchronize()
+        if ticket.truth is not None:
+            with self._stream(slot):     # the slot's result buffer and scratch belong to the slot's stream
+                self._score(slot, job, again, ticket.truth)      # the redone map, not the discarded one
+            self._commit(slot, again)
+            self.torch.cuda.synchronize()    # the library matcher's output is overwritten by the next repeat
         return again
+
+    def _commit(self, slot, ticket):
+        """The kept map into the running total, on the slot's stream (in front of the slot's next pair, which overwrites
+        a replayed graph's static output)."""
+        if ticket.truth is not None:
+            with self._stream(slot):
+                self.evaluator.commit(ticket.device_map, ticket.truth[0], ticket.truth[1])

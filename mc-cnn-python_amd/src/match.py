@@ -116,6 +116,14 @@ parser.add_argument("--paper_sgm", action="store_true",
 parser.add_argument("--numpy1_promotion", action="store_true",
                     help="evaluate the sub-pixel formula as NumPy < 2 promotes its scalars (float64, rounded once), "
                          "i.e. as the reference's own Python 2.7 environment does; differs by <= 2.5e-5 px")
+parser.add_argument("--evaluate", action="store_true",
+                    help="score every map against the disp0GT.pfm (and mask0nocc.png) beside its im0.png, on the device "
+                         "(src/evaluation.py): bad-pixel rates, invalid pixels, average and RMS error over all pixels with "
+                         "ground truth and over the non-occluded ones.  Writes evalMCCNN.json beside each disp0MCCNN.pfm and "
+                         "submit_<tag>/eval.json (eval_rank<r>.json under torchrun) with the pooled totals; a pair without "
+                         "ground truth is matched as usual and listed as skipped.  Every other output stays byte-identical")
+parser.add_argument("--eval_thresholds", type=str, default="0.5,1,2,4",
+                    help="with --evaluate: the bad-pixel thresholds in pixels, 1 to 8 comma-separated values")
 
 # different file names
 left_image_suffix = "im0.png"
@@ -127,6 +135,7 @@ calib_suffix = "calib.txt"
 out_file = "disp0MCCNN.pfm"
 out_img_file = "disp0MCCNN.pgm"
 out_time_file = "timeMCCNN.txt"
+out_eval_file = "evalMCCNN.json"
 
 
 def hyper_parameters(args):
@@ -141,6 +150,11 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.fast and args.exact:
         parser.error("--fast and --exact exclude each other")
+    import evaluation as ev
+    try:
+        eval_thresholds = ev.parse_thresholds(args.eval_thresholds)
+    except ValueError as e:
+        parser.error("--eval_thresholds: %s" % e)
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -192,6 +206,10 @@ def main(argv=None):
     footprint_kw = dict(pairs_in_flight=in_flight, arch=args.arch,
                         fc_units=net.num_fc_units if accurate else sd.DECISION_UNITS)
     streams = [torch.cuda.Stream() for _ in range(in_flight)] if in_flight > 1 else [None]
+    # --evaluate: one result buffer and scratch per slot, the list's running total on the device (src/evaluation.py)
+    report = ev.ListReport(ev.Evaluator(thresholds=eval_thresholds, slots=in_flight)) if args.evaluate else None
+    evaluator = report.evaluator if report is not None else None
+    eval_path = os.path.join(result_root, "eval.json" if world == 1 else "eval_rank{}.json".format(rank))
     if args.pipeline:
         import list_matcher as lm
 
@@ -209,13 +227,17 @@ def main(argv=None):
             sd.workspace_bytes(height, width, ndisp, matchers[0].pixel_major(),
                                matchers[0].workspace_cbca_kernel(height, width, ndisp), **footprint_kw)
 
-        backend = lm.MatcherBackend(matchers, streams, lambda: make_matcher("miopen", "library"), rank=rank)
-        pipeline = lm.ListPipeline(lm.make_reader(paths, check_shape), backend, lm.make_writer(rank), slots=in_flight,
-                                   readers=args.readers)
+        backend = lm.MatcherBackend(matchers, streams, lambda: make_matcher("miopen", "library"), rank=rank,
+                                    report=report)
+        reader = lm.make_reader(paths, check_shape, truth=ev.load_ground_truth if args.evaluate else None)
+        pipeline = lm.ListPipeline(reader, backend, lm.make_writer(rank, report=report, eval_file=out_eval_file),
+                                   slots=in_flight, readers=args.readers)
         try:
             pipeline.run(shard_indices(args.start, args.end, len(left_paths), rank, world))
         finally:
             print("[{}] {}".format(rank, pipeline.summary()))
+        if report is not None:
+            report.write(eval_path)
         return pipeline
 
     pending = []          # pairs launched and not yet written: (device map, done event, start time, output paths)
@@ -225,8 +247,9 @@ def main(argv=None):
     redo = {"left": 0, "matcher": None}
 
     def finish(entry):
-        disparity, done, stTime, out_path, out_time_path, out_img_path, images = entry
+        disparity, done, stTime, out_path, out_time_path, out_img_path, images, scored = entry
         done.synchronize()
+        redone = False
         # the hand-written feature kernels report an activation beyond the range of their stored records (never seen
         # on standardised images with the trained weights): that pair - and, with several in flight, the ones that
         # shared the flag with it - is matched again with the float32 library convolutions
@@ -239,12 +262,24 @@ def main(argv=None):
             print("[{}] ".format(rank) + matchers[0].saturation_notice().format(out_path))
             disparity = redo["matcher"].match(images[0], images[1], images[2])
             torch.cuda.synchronize()
+            redone = True
+        if scored is not None:
+            # the total takes the map that is kept, once, in list order; a repeated pair is scored again
+            index, name, score, gt, mask, slot, json_path = scored
+            with torch.cuda.stream(streams[slot]) if in_flight > 1 else contextlib.nullcontext():
+                if redone:
+                    score = evaluator.score(disparity, gt, mask, slot)
+                evaluator.commit(disparity, gt, mask)
+            if redone:
+                torch.cuda.synchronize()     # the library matcher's output is overwritten by the next repeat
         left_disparity_map = disparity.cpu().numpy()
         endTime = time.time()
         util.saveDisparity(left_disparity_map, out_img_path)
         util.writePfm(left_disparity_map, out_path)
         util.saveTimeFile(endTime - stTime, out_time_path)
         print("[{}] {}: {:.3f} s -> {}".format(rank, datetime.now(), endTime - stTime, out_path))
+        if scored is not None:
+            report.pair(index, name, score.metrics(), json_path)
 
     for index in shard_indices(args.start, args.end, len(left_paths), rank, world):
         left_path = left_paths[index]
@@ -270,6 +305,12 @@ def main(argv=None):
             print("[{}] workspace {:.2f} GB ({} pair(s) in flight)".format(rank, footprint / 1e9, in_flight))
             last_shape = (height, width, ndisp)
 
+        truth = ev.load_ground_truth(left_path) if args.evaluate else None
+        if truth is not None:
+            ev.check_shape(truth[0], (height, width), left_path)
+        elif args.evaluate:
+            report.skip(index, left_path)
+
         # decode + standardise (match.py:118-125): population std, no /255
         views = []
         for path in (left_path, right_path):
@@ -292,13 +333,21 @@ def main(argv=None):
             dev_l = torch.from_numpy(left_image).cuda()
             dev_r = torch.from_numpy(right_image).cuda()
             disparity = matchers[slot].match(dev_l, dev_r, ndisp)
+            scored = None
+            if truth is not None:        # behind the map, on the pair's stream
+                gt = torch.from_numpy(truth[0]).cuda()
+                mask = torch.from_numpy(truth[1]).cuda() if truth[1] is not None else None
+                scored = (index, left_path, evaluator.score(disparity, gt, mask, slot), gt, mask, slot,
+                          os.path.join(res_dir, out_eval_file))
             done = torch.cuda.Event()
             done.record()
-        pending.append((disparity, done, stTime, out_path, out_time_path, out_img_path, (dev_l, dev_r, ndisp)))
+        pending.append((disparity, done, stTime, out_path, out_time_path, out_img_path, (dev_l, dev_r, ndisp), scored))
         if in_flight == 1:
             finish(pending.pop(0))
     while pending:
         finish(pending.pop(0))
+    if report is not None:
+        report.write(eval_path)
 
 
 if __name__ == "__main__":

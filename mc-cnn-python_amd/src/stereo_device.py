@@ -329,6 +329,57 @@ def ingest_u8_pair(left_u8, right_u8, out_l=None, out_r=None, scratch=None):
     return out_l, out_r
 
 
+# ---- evaluation against ground truth ---------------------------------------------------------------------------------
+EVAL_BYTES = 192             # sizeof(mccnn_eval_t)
+EVAL_THRESHOLDS = (0.5, 1.0, 2.0, 4.0)
+
+
+def evaluate_scratch(H, W, device):
+    """Scratch of one evaluate() in flight (per-chunk partials and counts): mccnn_evaluate_scratch_bytes(H, W) bytes."""
+    nbytes = int(hip.load().mccnn_evaluate_scratch_bytes(H, W))
+    return torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=device)
+
+
+def evaluate_result(device):
+    """A zeroed mccnn_eval_t on the device: 192 bytes as 24 int64 words (an accumulator starts here)."""
+    return torch.zeros((EVAL_BYTES // 8,), dtype=torch.int64, device=device)
+
+
+def evaluate(disp, gt, mask=None, thresholds=EVAL_THRESHOLDS, out=None, accumulate=False, scratch=None):
+    """disp, gt: float32 device maps [H,W]; mask: uint8 [H,W] or None (255 = non-occluded) -> the 192-byte device tensor
+    (24 int64 words) holding mccnn_eval_t: counts and error sums of the regions `all` (gt finite) and `nonocc` (also mask
+    == 255), defined to the bit in include/mccnn.h.  accumulate: add into `out` (which is then required) instead of
+    overwriting it.  The thresholds are read here, on the host, at call time - inside a captured graph they and
+    `accumulate` are baked in.  No synchronisation; evaluation.Metrics.from_result reads the bytes once they are on the
+    host.  `scratch`: an evaluate_scratch()."""
+    if disp.dim() != 2 or disp.dtype != torch.float32 or gt.dtype != torch.float32:
+        raise ValueError("evaluate: expected float32 maps [H,W], got %s %s and %s %s"
+                         % (disp.dtype, tuple(disp.shape), gt.dtype, tuple(gt.shape)))
+    if tuple(gt.shape) != tuple(disp.shape):
+        raise ValueError("evaluate: the map is %s, the ground truth %s" % (tuple(disp.shape), tuple(gt.shape)))
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(disp.shape)):
+        raise ValueError("evaluate: expected a uint8 mask %s, got %s %s" % (tuple(disp.shape), mask.dtype, tuple(mask.shape)))
+    for t in (gt, mask, out, scratch):
+        if t is not None and t.device != disp.device:
+            raise ValueError("evaluate: every tensor must live on the map's device")
+    thr = [float(t) for t in thresholds]
+    if not 1 <= len(thr) <= hip.MCCNN_EVAL_MAX_THRESHOLDS:
+        raise ValueError("evaluate: %d thresholds, expected 1..%d" % (len(thr), hip.MCCNN_EVAL_MAX_THRESHOLDS))
+    H, W = disp.shape
+    if out is None:
+        if accumulate:
+            raise ValueError("evaluate: accumulate needs the `out` to accumulate into")
+        out = torch.empty((EVAL_BYTES // 8,), dtype=torch.int64, device=disp.device)
+    elif out.numel() * out.element_size() != EVAL_BYTES:
+        raise ValueError("evaluate: `out` must hold %d bytes" % EVAL_BYTES)
+    scratch = scratch if scratch is not None else evaluate_scratch(H, W, disp.device)
+    hip.check(hip.load().mccnn_evaluate(hip.ptr(disp), hip.ptr(gt), hip.ptr(mask) if mask is not None else None, H, W,
+                                        (ctypes.c_float * len(thr))(*thr), len(thr), 1 if accumulate else 0, hip.ptr(out),
+                                        hip.ptr(scratch), scratch.numel() * scratch.element_size(), hip.stream()),
+              "mccnn_evaluate")
+    return out
+
+
 # ---- a3 ----------------------------------------------------------------------------------------------------------
 def support_buffer(H, W, device):
     """An empty support plane (see cross_arms): the [H,W] view of a mccnn_support_bytes(H, W) allocation."""

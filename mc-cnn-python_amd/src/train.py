@@ -26,6 +26,11 @@ ground-truth pixel of train.txt into one pool (an epoch is n_valid // batch_size
 --augment middlebury|kitti applies the paper's data set augmentation (every key has an --aug_<key> override),
 --subpixel_centres keeps the fractional disparity; --lr_drop_epoch E --lr_drop_factor F divides the learning rate by F
 from epoch E on (the paper: one tenfold drop).  Validation keeps pair sampling on val.txt, without augmentation.
+Validation by error rate (the paper's model selection; not in the reference): --val_error matches every pair of val.txt
+with the current weights (stereo_device.StereoMatcher, default hyper-parameters, ndisp from the calib.txt beside im0.png)
+and scores the maps against disp0GT.pfm / mask0nocc.png on the device (evaluation.py), every --val_error_freq epochs on
+rank 0; the pooled val_bad1.0_nonocc, val_bad2.0_nonocc, val_bad2.0_all and val_avgerr_all go to scalars.jsonl, and
+--save_best keeps the checkpoint with the lowest val_bad2.0_nonocc as model_best.ckpt.npz.  Needs a GPU.
 """
 import argparse
 import json
@@ -82,6 +87,12 @@ parser.add_argument("--subpixel_centres", action="store_true",
 parser.add_argument("--lr_drop_epoch", type=int, default=None,
                     help="from this epoch on the learning rate is learning_rate / lr_drop_factor (default: never)")
 parser.add_argument("--lr_drop_factor", type=float, default=10.0, help="see --lr_drop_epoch")
+parser.add_argument("--val_error", action="store_true",
+                    help="validate by the error rate of the whole pipeline: match every pair of val.txt with the current "
+                         "weights and score it against its ground truth on the device (needs a GPU; rank 0)")
+parser.add_argument("--val_error_freq", type=int, default=1, help="with --val_error: every this many epochs")
+parser.add_argument("--save_best", action="store_true",
+                    help="with --val_error: copy the checkpoint with the lowest val_bad2.0_nonocc to model_best.ckpt.npz")
 
 
 def parse_args(argv=None):
@@ -96,6 +107,10 @@ def parse_args(argv=None):
                 parser.error("%s requires --sampler device" % flag)
     if args.lr_drop_factor <= 0:
         parser.error("--lr_drop_factor must be positive")
+    if args.save_best and not args.val_error:
+        parser.error("--save_best requires --val_error")
+    if args.val_error_freq < 1:
+        parser.error("--val_error_freq must be positive")
     args.augment_overrides = overrides
     return args
 
@@ -231,6 +246,46 @@ class Trainer(object):
                         self.opt.state[p]["momentum_buffer"] = torch.from_numpy(np.ascontiguousarray(a)).to(p.device)
 
 
+VAL_ERROR_TAGS = ("val_bad1.0_nonocc", "val_bad2.0_nonocc", "val_bad2.0_all", "val_avgerr_all")
+
+
+class PipelineValidator(object):
+    """--val_error: the pairs of a list matched with `net` as it stands and scored on the device.  One StereoMatcher
+    serves every epoch: it reads the net's own tensors, and the nets' packed-weight caches are keyed by the tensors'
+    _version, which every optimiser step advances."""
+
+    def __init__(self, net, list_file):
+        import evaluation
+        import stereo_device as sd
+        self.ev = evaluation
+        self.matcher = sd.StereoMatcher(net)
+        with open(list_file, "r") as f:
+            self.left_paths = [line.strip() for line in f if line.strip()]
+
+    def run(self):
+        """-> {tag: pooled value or None} over the pairs that have ground truth."""
+        import torch
+        ev = self.ev
+        evaluator = ev.Evaluator(self.matcher.device, ev.DEFAULT_THRESHOLDS)
+        with torch.no_grad():
+            for left_path in self.left_paths:
+                truth = ev.load_ground_truth(left_path)
+                if truth is None:
+                    continue
+                height, width, ndisp = util.parseCalib(left_path.replace("im0.png", "calib.txt"))
+                ev.check_shape(truth[0], (height, width), left_path)
+                views = []
+                for path in (left_path, left_path.replace("im0.png", "im1.png")):       # as match.py standardises
+                    g = util.read_gray(path).astype(np.float32)
+                    views.append(torch.from_numpy((g - np.mean(g, axis=(0, 1))) / np.std(g, axis=(0, 1))).cuda())
+                disparity = self.matcher.match(views[0], views[1], ndisp)
+                evaluator.pair(disparity, torch.from_numpy(truth[0]).cuda(),
+                               torch.from_numpy(truth[1]).cuda() if truth[1] is not None else None)
+        pooled = evaluator.report()
+        return {"val_bad1.0_nonocc": pooled.bad(1.0, "nonocc"), "val_bad2.0_nonocc": pooled.bad(2.0, "nonocc"),
+                "val_bad2.0_all": pooled.bad(2.0, "all"), "val_avgerr_all": pooled.figures["all"]["avgerr"]}
+
+
 def main(argv=None):
     args = parse_args(argv)
     rank = int(os.environ.get("RANK", "0"))
@@ -245,6 +300,9 @@ def main(argv=None):
     from model import ACCURATE_NET, NET
 
     on_gpu = torch.cuda.is_available()
+    if args.val_error and not on_gpu:
+        parser.error("--val_error matches and scores the validation pairs on the GPU and no HIP device is visible "
+                     "(there is no CPU fallback)")
     if on_gpu:
         torch.cuda.set_device(local_rank if world > 1 else 0)
     device = torch.device("cuda", torch.cuda.current_device()) if on_gpu else torch.device("cpu")
@@ -291,6 +349,8 @@ def main(argv=None):
     if args.resume is not None:
         trainer.load_state(args.resume)
     log = open(os.path.join(args.tensorboard_dir, "scalars.jsonl"), "a") if rank == 0 else None
+    validator = PipelineValidator(net, os.path.join(args.list_dir, "val.txt")) if args.val_error and rank == 0 else None
+    best = None          # the lowest val_bad2.0_nonocc so far
 
     def scalar(tag, value, step):
         if log is not None:
@@ -316,6 +376,19 @@ def main(argv=None):
             name = os.path.join(args.checkpoint_dir, "model_epoch" + str(epoch + 1) + ".ckpt.npz")
             np.savez(name, **trainer.state())
             print("[{}] {}: epoch {} saved to {}".format(rank, datetime.now(), epoch + 1, name))
+        if validator is not None and (epoch + 1) % args.val_error_freq == 0:
+            errors = validator.run()
+            print("[{}] {}: epoch {} validation error: {}".format(rank, datetime.now(), epoch + 1, errors))
+            for tag in VAL_ERROR_TAGS:
+                if errors[tag] is not None:
+                    scalar(tag, errors[tag], train_batches_per_epoch * (epoch + 1))
+            key = errors["val_bad2.0_nonocc"]
+            if args.save_best and key is not None and (best is None or key < best):
+                best = key
+                name = os.path.join(args.checkpoint_dir, "model_best.ckpt.npz")
+                np.savez(name, **trainer.state())
+                print("[{}] {}: epoch {} is the best so far (val_bad2.0_nonocc {}), saved to {}".format(
+                    rank, datetime.now(), epoch + 1, key, name))
         if (epoch + 1) % args.val_freq == 0:
             with torch.no_grad():
                 val_ls = sum(float(val_loss())
