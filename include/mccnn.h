@@ -171,7 +171,11 @@ int mccnn_cbca_iter_pair(const float *in_left, float *out_left, const mccnn_supp
  * Opt-in, changes the output: at disparity d every arm used at a pixel q is min(own arm at q, the other view's arm at
  * the partner q -/+ d) (side LEFT: x - d, RIGHT: x + d; partner outside the image: own arms).  Flat float32 running
  * sum in the reference's order, region size counted on the way.  support_self / support_other: planes built by
- * mccnn_cross_arms on the volume's own view and on the other view. */
+ * mccnn_cross_arms on the volume's own view and on the other view.  Own arms are first clamped to R (13 for L <= 14,
+ * 31 above), then intersected.  Refused: in == out, a side other than MCCNN_SIDE_LEFT / _RIGHT (MCCNN_E_INVALID); L
+ * outside [1,32], D > 65535 (MCCNN_E_UNSUPPORTED); and, as in mccnn_cbca_iter, either plane when this library built it
+ * for another image size or with a distance larger than L (MCCNN_E_INVALID).  Addresses it has never seen pass: for
+ * those the clamp to R is what keeps every read inside the staged tile. */
 int mccnn_cbca_iter_both(const float *in, float *out, const mccnn_support_t *support_self,
                          const mccnn_support_t *support_other, int D, int H, int W, int L, int side,
                          mccnn_stream_t stream);
@@ -367,7 +371,10 @@ int mccnn_wta_hwd(const float *vol_hwd, int D, int H, int W, float *disparity, m
  * disparities may hold anything (NaN, +-inf, negative, >= D match nothing).  Rows wider than 16384 pixels put the image
  * rows on grid.y: H <= 65535 there (MCCNN_E_UNSUPPORTED beyond).
  * mccnn_interpolate: status 1 -> median (np.median: a median of -0.0 is +0.0) of the nearest status-0 pixel
- * right/left/below/above, status 2 -> nearest status-0 pixel to the right, else raw.  `out` must alias neither
+ * right/left/below/above, status 2 -> nearest status-0 pixel to the right, else raw.  As in np.median, one NaN among
+ * the neighbours makes the median NaN (the status map is the caller's: mccnn_lr_status never marks a NaN disparity as a
+ * match, other status maps may); any status word other than 0 is "no match", other than 1 / 2 leaves the raw value.
+ * The same holds for mccnn_interpolate_ex.  `out` must alias neither
  * disp_left nor status (MCCNN_E_INVALID: other threads still read both); H <= 65535 (MCCNN_E_UNSUPPORTED beyond), also
  * for mccnn_interpolate_ex. */
 int mccnn_lr_status(const float *disp_left, const float *disp_right, int H, int W, int D, int32_t *status,

@@ -1022,6 +1022,10 @@ extern "C" int mccnn_cbca_iter_both(const float *in, float *out, const mccnn_sup
     MCCNN_REQUIRE(side == MCCNN_SIDE_LEFT || side == MCCNN_SIDE_RIGHT, MCCNN_E_INVALID,
                   "mccnn_cbca_iter_both: side %d", side);
     MCCNN_REQUIRE(L >= 1 && L <= 32, MCCNN_E_UNSUPPORTED, "mccnn_cbca_iter_both: L=%d outside [1,32]", L);
+    // as mccnn_cbca_iter: a plane this library built for another image size or with longer arms is refused, not clamped
+    // (addresses the registry has never seen pass; the kernel's min(arm, R) keeps those inside the staged tile)
+    if (const int rc = check_support_record(support_self, H, W, L, "mccnn_cbca_iter_both")) return rc;
+    if (const int rc = check_support_record(support_other, H, W, L, "mccnn_cbca_iter_both")) return rc;
     const int dsign = side == MCCNN_SIDE_LEFT ? -1 : 1;
     hipStream_t s = (hipStream_t)stream;
     if (L <= 14) {

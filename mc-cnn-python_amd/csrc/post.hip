@@ -105,7 +105,11 @@ __device__ __forceinline__ float median_upto4(float *v, int n)
 {
     // np.median of 1..n float32 values (n <= 4 in the reference's rule, <= 16 in the paper's): sort, middle element or
     // mean of the two middle ones.  np.median ends in np.mean, whose float32 sum starts from +0: a median of -0.0 comes
-    // out as +0.0 (0.f + x; every other value, NaN and inf included, is unchanged by it)
+    // out as +0.0 (0.f + x; every other value, NaN and inf included, is unchanged by it).  np.median returns NaN as soon as
+    // one value is NaN, wherever it stands; the insertion sort below leaves a NaN where it is (v[j] > NaN is false) and
+    // would pick whatever lands in the middle, so NaN is looked for first.  NaN-free sets take the path they always took.
+    for (int i = 0; i < n; ++i)
+        if (v[i] != v[i]) return v[i];
     for (int i = 1; i < n; ++i) {
         const float x = v[i];
         int j = i - 1;
@@ -268,7 +272,7 @@ __global__ __launch_bounds__(256) void interpolate_row_kernel(const float *__res
                 if (below != 0xffffu) nb[c++] = dl[(size_t)below * W + w];
                 if (above != 0xffffu) nb[c++] = dl[(size_t)above * W + w];
                 if (c > 0) res = median_upto4(nb, c);
-            } else if (xr >= 0) {  // pf:358-373: nearest match to the right
+            } else if (s == 2 && xr >= 0) {  // pf:358-373: nearest match to the right (any other word: the raw value)
                 res = dl[row + xr];
             }
         }

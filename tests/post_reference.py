@@ -80,7 +80,7 @@ def _first_match(values, status, positions):
 
 def interpolate(left_map, status):
     """Status 1: np.median of the nearest status-0 values to the right, left, below, above (in that order); status 2:
-    the nearest status-0 value to the right; the raw value where there is none."""
+    the nearest status-0 value to the right; the raw value where there is none, and for any other status word."""
     dl = _a32(left_map)
     H, W = dl.shape
     out = np.empty((H, W), dtype=np.float32)
@@ -95,9 +95,11 @@ def interpolate(left_map, status):
                       + _first_match(dl, status, [(y, w) for y in range(h + 1, H)])
                       + _first_match(dl, status, [(y, w) for y in range(h - 1, -1, -1)]))
                 out[h, w] = np.median(np.array(nb, dtype=np.float32)) if nb else dl[h, w]
-            else:
+            elif s == 2:
                 nb = _first_match(dl, status, [(h, x) for x in range(w + 1, W)])
                 out[h, w] = nb[0] if nb else dl[h, w]
+            else:                              # a word lr_status never writes: no match, and nothing to fill it from
+                out[h, w] = dl[h, w]
     return out
 
 

@@ -1,63 +1,20 @@
 """GPU: the opt-in extras - rules of the MC-CNN paper that the reference names and leaves out, and the
 scalar promotion of the NumPy it was written for.  None of this is reference behaviour, so the checkers are plain
-Python restatements of the definitions in include/mccnn.h, kept here with the tests; the defaults (extras off) are
-covered by the parity tests."""
-import math
-
+Python restatements of the definitions in include/mccnn.h (tests/paper_rules_reference.py, which test_paper_rules_cpu.py
+pins; test_paper_rules_gpu.py takes the same kernels to their edges); the defaults (extras off) are covered by the
+parity tests."""
 import numpy as np
 import pytest
 import torch
 
 from helpers import assert_bits
+from paper_rules_reference import cbca_both_check, interpolate_check, numpy1_subpixel_check
 
 pytestmark = pytest.mark.gpu
-
-RAYS = [(1, 0), (1, 0.5), (1, 1), (0.5, 1), (0, 1), (-0.5, 1), (-1, 1), (-1, 0.5), (-1, 0), (-1, -0.5), (-1, -1),
-        (-0.5, -1), (0, -1), (0.5, -1), (1, -1), (1, -0.5)]
 
 
 def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def interpolate_check(dl, st, directions, occ_left):
-    H, W = dl.shape
-    out = dl.copy()
-    for h in range(H):
-        for w in range(W):
-            if st[h, w] == 1:
-                nb = []
-                if directions == 16:
-                    for dx, dy in RAYS:
-                        xx, yy = float(w), float(h)
-                        while True:
-                            xx += dx
-                            yy += dy
-                            xi, yi = int(math.floor(xx + 0.5)), int(math.floor(yy + 0.5))
-                            if xi < 0 or xi >= W or yi < 0 or yi >= H:
-                                break
-                            if st[yi, xi] == 0:
-                                nb.append(dl[yi, xi])
-                                break
-                else:
-                    for rng_ in (range(w + 1, W), range(w - 1, -1, -1)):
-                        for x in rng_:
-                            if st[h, x] == 0:
-                                nb.append(dl[h, x])
-                                break
-                    for rng_ in (range(h + 1, H), range(h - 1, -1, -1)):
-                        for y in rng_:
-                            if st[y, w] == 0:
-                                nb.append(dl[y, w])
-                                break
-                if nb:
-                    out[h, w] = np.median(np.array(nb, dtype=np.float32))
-            elif st[h, w] == 2:
-                for x in (range(w - 1, -1, -1) if occ_left else range(w + 1, W)):
-                    if st[h, x] == 0:
-                        out[h, w] = dl[h, x]
-                        break
-    return out
 
 
 def test_paper_interpolation_rules():
@@ -86,45 +43,11 @@ def test_numpy1_promotion_subpixel():
     H, W, D = 30, 44, 12
     vol = rng.random((D, H, W), dtype=np.float32)
     d = rng.integers(0, D, size=(H, W)).astype(np.float32)
-    want = d.copy()
-    for h in range(H):
-        for w in range(W):
-            di = d[h, w]
-            if int(di - 1) < 0 or int(di + 1) >= D:
-                continue
-            cm, cp, c = vol[int(di - 1), h, w], vol[int(di + 1), h, w], vol[int(di), h, w]
-            num = np.float32(cp - cm)                               # float32 - float32 stays float32 under NumPy 1
-            den = 2.0 * (np.float64(cp) - 2.0 * np.float64(c) + np.float64(cm))
-            want[h, w] = np.float32(np.float64(di) - np.float64(num) / den)
+    want = numpy1_subpixel_check(d, vol)
     got = sd.subpixel(dev(d), dev(vol), numpy1_promotion=True).cpu().numpy()
     assert_bits(got, want, "NumPy-1 promotion")
     plain = sd.subpixel(dev(d), dev(vol)).cpu().numpy()
     assert np.abs(plain - got).max() <= 1e-3 and not np.array_equal(plain, got)
-
-
-def cbca_both_check(vol, arms_self, arms_other, side):
-    """arms: uint8 [H,W,4] = up, down, left, right."""
-    D, H, W = vol.shape
-    out = np.empty_like(vol)
-    for d in range(D):
-        sh = -d if side == 0 else d
-        for y in range(H):
-            for x in range(W):
-                def arms(qy):
-                    a = arms_self[qy, x].astype(int)
-                    xo = x + sh
-                    if 0 <= xo < W:
-                        a = np.minimum(a, arms_other[qy, xo].astype(int))
-                    return a
-                u, dn, _, _ = arms(y)
-                s, n = np.float32(0), 0
-                for qy in [y] + [y - k for k in range(1, u + 1)] + [y + k for k in range(1, dn + 1)]:
-                    _, _, l, r = arms(qy)
-                    for xx in [x] + [x - k for k in range(1, l + 1)] + [x + k for k in range(1, r + 1)]:
-                        s = np.float32(s + vol[d, qy, xx])
-                    n += l + r + 1
-                out[d, y, x] = np.float32(s / np.float32(n))
-    return out
 
 
 def test_both_view_support_regions():

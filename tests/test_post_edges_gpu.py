@@ -13,7 +13,10 @@ kernel -> test
   median_kernel, median5x5_kernel              test_median_matrix, test_filters_across_a_block_boundary
   bilateral_kernel, bilateral5x5_kernel        test_bilateral_matrix, test_filters_across_a_block_boundary
   cross_region_list_kernel                     test_region_list_every_slot
-(interpolate_paper_kernel and subpixel_kernel<true> are the opt-in extras of test_extras_gpu.py.)"""
+  interpolate_paper_kernel                     test_paper_rules_gpu.py::test_paper_interpolation
+  subpixel_kernel<true>, subpixel_hwd<true>    test_paper_rules_gpu.py::test_numpy1_subpixel
+(the two opt-in extras: their edges are in test_paper_rules_gpu.py, against tests/paper_rules_reference.py; a NaN
+neighbour in median_upto4, which no mccnn_lr_status map produces, is there too.)"""
 import numpy as np
 import pytest
 import torch
