@@ -45,7 +45,7 @@ extern "C" {
 
 typedef void *mccnn_stream_t; /* hipStream_t */
 
-#define MCCNN_ABI_VERSION 7 /* 2: window-mask plane, *_hwd entry points; 3: saturation flags; 4: program-driven CBCA; 5: skip programs; 6: one-volume launches; 7: refresh launches, SGM flag planes as a call of their own; still 7 with the mccnn_ingest_* and the mccnn_decision_* / mccnn_cost_volume_accurate* entry points and mccnn_sample_patches, and with mccnn_evaluate: purely additive, nothing that existed changed */
+#define MCCNN_ABI_VERSION 7 /* 2: window-mask plane, *_hwd entry points; 3: saturation flags; 4: program-driven CBCA; 5: skip programs; 6: one-volume launches; 7: refresh launches, SGM flag planes as a call of their own; still 7 with the mccnn_ingest_* and the mccnn_decision_* / mccnn_cost_volume_accurate* entry points and mccnn_sample_patches, and with mccnn_evaluate, and with the mccnn_kitti_* entry points and mccnn_evaluate_kitti: purely additive, nothing that existed changed */
 
 #define MCCNN_E_INVALID (-1)     /* bad argument (null pointer, non-positive size, unsupported shape) */
 #define MCCNN_E_UNSUPPORTED (-2) /* shape outside what the kernels were built for (e.g. D > 1024 for SGM) */
@@ -483,6 +483,50 @@ size_t mccnn_evaluate_scratch_bytes(int H, int W); /* 0 for non-positive sizes *
 int mccnn_evaluate(const float *disp, const float *gt, const uint8_t *mask /* may be NULL */, int H, int W,
                    const float *thresholds /* HOST, n_thr values */, int n_thr, int accumulate,
                    mccnn_eval_t *result /* device */, void *scratch, size_t scratch_bytes, mccnn_stream_t stream);
+
+/* ---- KITTI 2012 / 2015: the development kit's file code, background interpolation and error rule, on the device ------
+ * Written down from memory of the kit; THIS text is the binding definition.  Throughout, a disparity is
+ * VALID when it is finite and >= 0: -0.0f is valid; -1, NaN and +-inf are not (the rule of mccnn_evaluate).  Device
+ * pointers, sizes and a stream; no allocation, no synchronisation, no atomics: capturable.  Arguments are validated
+ * before any HIP call: null pointers, non-positive sizes, misaligned pointers (float32 4, uint16 2, scratch and result 8
+ * bytes) are MCCNN_E_INVALID, a scratch too small is MCCNN_E_SCRATCH, H*W beyond the grid's reach MCCNN_E_UNSUPPORTED.
+ *
+ * (a) mccnn_kitti_encode_u16: the float32 map [H][W] as the kit's 16-bit code [H][W].  An invalid disparity -> 0 ("no
+ *   value").  Otherwise v = rintf(disp * 256.0f) - one float32 multiply, round half to even - clamped to 1 .. 65535; the
+ *   lower clamp keeps a valid zero disparity from reading back as "no value".  (The kit truncates; rounding halves the
+ *   quantisation error and is this project's choice.)  One launch.
+ *   mccnn_kitti_decode_u16 is the way back, what a reader of the file sees: code / 256.0f (exact in float32), 0 -> +inf -
+ *   Middlebury's "unknown" as a ground truth, an invalid disparity as an estimate.  One launch.
+ *
+ * (b) mccnn_kitti_interpolate_background (out != disp): the kit's interpolateBackground, stated without its sequential
+ *   walk.  Row pass, on disp, for every invalid pixel: L is the nearest valid pixel to its left in its row, R the nearest
+ *   valid pixel to its right; with both the value is R < L ? R : L (float32 compare: L on a tie, and for -0.0f against
+ *   +0.0f); with one, that one; with neither the pixel keeps its bits.  After the row pass a pixel is invalid only if its
+ *   whole row was.  Column pass, on the row pass's result: an invalid pixel above the first valid pixel of its column takes
+ *   that pixel's value, one below the last valid pixel takes that one's; an invalid pixel between two valid pixels of its
+ *   column (a whole invalid row inside the image) stays as it is, as in the kit, and so does a column without a valid pixel.
+ *   Valid pixels are copied bit for bit.  Two launches (one workgroup per row; one thread per column).
+ *
+ * (c) mccnn_evaluate_kitti writes the mccnn_eval_t of mccnn_evaluate from 16-bit ground truth [H][W].  Region `all`: the
+ *   pixels with gt_occ != 0, truth g = gt_occ / 256.0f (exact in float32).  Region `nonocc`: the pixels with gt_noc != 0,
+ *   truth from gt_noc; with gt_noc == NULL it equals `all`.  Per pixel of a region: n_valid += 1; an invalid estimate adds
+ *   n_invalid += 1 and nothing else; otherwise err = fabsf(d - g), n_bad[k] += 1 when err > abs_thr[k] && err > rel_thr[k]
+ *   * g - the product a float32 multiply rounded on its own (no FMA contraction), both compares strict; KITTI 2015's D1 is
+ *   (3, 0.05), KITTI 2012's Out-Noc / Out-All at t pixels are (t, 0) - and the pixel's terms a = (double)err, q = a * a go
+ *   into sum_abs and sum_sq.  The sums are defined to the bit by the tree of mccnn_evaluate (chunks of 1024 pixel indices,
+ *   stride-halving tree, chunk partials added in ascending order from +0.0), and `accumulate` means what it means there.
+ *   interpolate != 0: the map scored is (b) applied to disp, held in scratch (two more launches); disp is never written.
+ *   abs_thr, rel_thr: HOST arrays of n_thr values each, read at call time.  scratch: mccnn_evaluate_kitti_scratch_bytes(H,
+ *   W, interpolate) bytes, 8-byte aligned like result, private to one call in flight.
+ *   Refused as well: n_thr outside 1 .. MCCNN_EVAL_MAX_THRESHOLDS, a NaN or negative threshold (MCCNN_E_INVALID). */
+int mccnn_kitti_encode_u16(const float *disp, int H, int W, uint16_t *out_u16, mccnn_stream_t stream);
+int mccnn_kitti_decode_u16(const uint16_t *code_u16, int H, int W, float *out, mccnn_stream_t stream);
+int mccnn_kitti_interpolate_background(const float *disp, int H, int W, float *out, mccnn_stream_t stream);
+size_t mccnn_evaluate_kitti_scratch_bytes(int H, int W, int interpolate); /* 0 for non-positive sizes */
+int mccnn_evaluate_kitti(const float *disp, const uint16_t *gt_occ_u16, const uint16_t *gt_noc_u16 /* may be NULL */,
+                         int H, int W, const float *abs_thr /* HOST */, const float *rel_thr /* HOST */, int n_thr,
+                         int interpolate, int accumulate, mccnn_eval_t *result /* device */, void *scratch,
+                         size_t scratch_bytes, mccnn_stream_t stream);
 
 /* ---- a1 epilogues of the conv stack (model.py:51-64, 111-125) ------------------------------------------------
  * mccnn_bias_act: x[n][c][i] = act(x[n][c][i] + bias[c]) in place on an NCHW tensor (plane = H*W elements) -

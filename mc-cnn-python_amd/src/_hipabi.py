@@ -104,6 +104,12 @@ SIGNATURES = {
     "mccnn_sample_patches": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "mccnn_evaluate_scratch_bytes": (_sz, [_i, _i]),
     "mccnn_evaluate": (_i, [_vp, _vp, _vp, _i, _i, ctypes.POINTER(_f), _i, _i, _vp, _vp, _sz, _vp]),
+    "mccnn_kitti_encode_u16": (_i, [_vp, _i, _i, _vp, _vp]),
+    "mccnn_kitti_decode_u16": (_i, [_vp, _i, _i, _vp, _vp]),
+    "mccnn_kitti_interpolate_background": (_i, [_vp, _i, _i, _vp, _vp]),
+    "mccnn_evaluate_kitti_scratch_bytes": (_sz, [_i, _i, _i]),
+    "mccnn_evaluate_kitti": (_i, [_vp, _vp, _vp, _i, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _i, _i, _i, _vp, _vp, _sz,
+                                  _vp]),
 }
 
 

@@ -92,7 +92,10 @@ class ImageDataGenerator(object):
 
     def __init__(self, left_image_list_file, shuffle=False, patch_size=(11, 11), in_left_suffix='im0.png',
                  in_right_suffix='im1.png', gt_suffix='disp0GT.pfm', dataset_neg_low=1.5, dataset_neg_high=6,
-                 dataset_pos=0.5, rng=None):
+                 dataset_pos=0.5, rng=None, layout=None):
+        # layout: a datasets.py layout whose path mapping and ground-truth reader replace the three suffixes (None: the
+        # reference's suffix replacement and PFM reader)
+        self.layout = layout
         self.shuffle = shuffle
         self.patch_size = patch_size
         self.in_left_suffix = in_left_suffix
@@ -112,8 +115,12 @@ class ImageDataGenerator(object):
         """Right-view and ground-truth paths follow from the left path by suffix replacement (:54-70)."""
         with open(image_list) as f:
             self.left_paths = [line.strip() for line in f if line.strip()]
-        self.right_paths = [p.replace(self.in_left_suffix, self.in_right_suffix) for p in self.left_paths]
-        self.gt_paths = [p.replace(self.in_left_suffix, self.gt_suffix) for p in self.left_paths]
+        if self.layout is not None:
+            self.right_paths = [self.layout.right(p) for p in self.left_paths]
+            self.gt_paths = [self.layout.truth_paths(p)[-1] for p in self.left_paths]
+        else:
+            self.right_paths = [p.replace(self.in_left_suffix, self.in_right_suffix) for p in self.left_paths]
+            self.gt_paths = [p.replace(self.in_left_suffix, self.gt_suffix) for p in self.left_paths]
         self.data_size = len(self.left_paths)
 
     @staticmethod
@@ -125,7 +132,10 @@ class ImageDataGenerator(object):
         """All pairs are kept in memory (:73-97): stereo training sets are a few dozen images."""
         self.left_images = [self._standardise(read_gray(p)) for p in self.left_paths]
         self.right_images = [self._standardise(read_gray(p)) for p in self.right_paths]
-        self.gt_images = [np.asarray(readPfm(p), dtype=np.float32) for p in self.gt_paths]
+        if self.layout is not None:      # float32, +inf where unknown, whatever the files hold (KITTI: kitti_gt_to_float)
+            self.gt_images = [np.asarray(self.layout.load_truth_float(p), dtype=np.float32) for p in self.left_paths]
+        else:
+            self.gt_images = [np.asarray(readPfm(p), dtype=np.float32) for p in self.gt_paths]
 
     def shuffle_data(self):
         order = self.rng.permutation(self.data_size)
@@ -244,7 +254,7 @@ class DevicePatchSampler(ImageDataGenerator):
     def __init__(self, left_image_list_file, shuffle=False, patch_size=(11, 11), in_left_suffix='im0.png',
                  in_right_suffix='im1.png', gt_suffix='disp0GT.pfm', dataset_neg_low=1.5, dataset_neg_high=6,
                  dataset_pos=0.5, rng=None, device="cuda", sampling="pair", truncate=True, augment=None, batch_size=128,
-                 world_size=1):
+                 world_size=1, layout=None):
         if sampling not in ("pair", "pool"):
             raise ValueError("sampling must be 'pair' or 'pool', not %r" % (sampling,))
         if patch_size[0] != patch_size[1] or patch_size[0] < 1 or patch_size[0] % 2 == 0 or patch_size[0] > 31:
@@ -266,7 +276,7 @@ class DevicePatchSampler(ImageDataGenerator):
         ImageDataGenerator.__init__(self, left_image_list_file, shuffle=shuffle and sampling == "pair",
                                     patch_size=patch_size, in_left_suffix=in_left_suffix,
                                     in_right_suffix=in_right_suffix, gt_suffix=gt_suffix, dataset_neg_low=dataset_neg_low,
-                                    dataset_neg_high=dataset_neg_high, dataset_pos=dataset_pos, rng=rng)
+                                    dataset_neg_high=dataset_neg_high, dataset_pos=dataset_pos, rng=rng, layout=layout)
         if sampling == "pool":
             self._build_valid_table()
             self._next_permutation()

@@ -1,4 +1,5 @@
-"""Scoring of disparity maps against Middlebury ground truth: the host side of mccnn_evaluate (csrc/evaluate.hip).
+"""Scoring of disparity maps against Middlebury ground truth: the host side of mccnn_evaluate (csrc/evaluate.hip), and
+against KITTI's through mccnn_evaluate_kitti (csrc/kitti.hip; KittiEvaluator, data set layouts: datasets.py).
 
 The counting and the sums happen on the device (stereo_device.evaluate: bad-pixel counts, invalid pixels and the float64
 error sums of the regions `all` and `nonocc`, defined to the bit in include/mccnn.h); this module turns the 192 bytes of a
@@ -35,6 +36,25 @@ def parse_thresholds(text):
     if not 1 <= len(values) <= 8 or any(math.isnan(v) for v in values):
         raise ValueError("expected 1 to 8 comma-separated thresholds, got %r" % (text,))
     return values
+
+
+def parse_kitti_thresholds(text):
+    """'3:0.05,2' -> ((3.0, 0.05), (2.0, 0.0)): 1 to 8 abs[:rel] items for mccnn_evaluate_kitti - a pixel is bad when its
+    error exceeds abs pixels and rel times the true disparity.  Neither part may be NaN or negative, and the abs parts
+    are distinct: they name the figures in the JSON files."""
+    pairs = []
+    for item in str(text).split(","):
+        if not item.strip():
+            continue
+        parts = item.split(":")
+        if len(parts) > 2:
+            raise ValueError("expected abs[:rel], got %r" % (item,))
+        pairs.append((float(parts[0]), float(parts[1]) if len(parts) == 2 else 0.0))
+    if not 1 <= len(pairs) <= 8 or any(math.isnan(v) or v < 0 for pair in pairs for v in pair):
+        raise ValueError("expected 1 to 8 comma-separated abs[:rel] thresholds, none NaN or negative, got %r" % (text,))
+    if len(set(a for a, _ in pairs)) != len(pairs):
+        raise ValueError("the abs parts name the figures and must differ, got %r" % (text,))
+    return tuple(pairs)
 
 
 def threshold_tag(t):
@@ -162,18 +182,28 @@ class Evaluator(object):
         self._total_scratch = []       # grown, never shrunk or freed: earlier commits may still be queued on other streams
         self._last_commit = None
 
+    # the three places that name the entry point (KittiEvaluator puts mccnn_evaluate_kitti there)
+    def _scratch_bytes(self, H, W):
+        return int(self.sd.hip.load().mccnn_evaluate_scratch_bytes(H, W))
+
+    def _new_scratch(self, H, W):
+        return self.sd.evaluate_scratch(H, W, self.device)
+
+    def _evaluate(self, disp, gt, mask, **kw):
+        self.sd.evaluate(disp, gt, mask, self.thresholds, **kw)
+
     def _scratch(self, have, H, W):
         """`have` if it serves an H x W map, else a new scratch."""
-        need = int(self.sd.hip.load().mccnn_evaluate_scratch_bytes(H, W))
+        need = self._scratch_bytes(H, W)
         if have is not None and have.numel() * have.element_size() >= need:
             return have
-        return self.sd.evaluate_scratch(H, W, self.device)
+        return self._new_scratch(H, W)
 
     def score(self, disp, gt, mask=None, slot=0):
         torch, sd = self.torch, self.sd
         st = self._slot[slot]
         st["scratch"] = self._scratch(st["scratch"], disp.shape[0], disp.shape[1])
-        sd.evaluate(disp, gt, mask, self.thresholds, out=st["result"], scratch=st["scratch"])
+        self._evaluate(disp, gt, mask, out=st["result"], scratch=st["scratch"])
         host = torch.empty((RESULT_BYTES // 8,), dtype=torch.int64, pin_memory=True)
         host.copy_(st["result"], non_blocking=True)
         done = torch.cuda.Event()
@@ -188,7 +218,7 @@ class Evaluator(object):
         scratch = self._scratch(self._total_scratch[-1] if self._total_scratch else None, disp.shape[0], disp.shape[1])
         if not self._total_scratch or scratch is not self._total_scratch[-1]:
             self._total_scratch.append(scratch)
-        sd.evaluate(disp, gt, mask, self.thresholds, out=self.total, accumulate=True, scratch=scratch)
+        self._evaluate(disp, gt, mask, out=self.total, accumulate=True, scratch=scratch)
         self._last_commit = torch.cuda.Event()
         self._last_commit.record(stream)
         self.pairs += 1
@@ -206,6 +236,30 @@ class Evaluator(object):
         return Metrics.from_result(self.total.cpu(), self.thresholds)
 
 
+class KittiEvaluator(Evaluator):
+    """The same bookkeeping on mccnn_evaluate_kitti: `gt` is the uint16 disp_occ plane and `mask` the uint16 disp_noc
+    plane (or None) as the kit stores them, thresholds are (abs, rel) pairs, interpolate fills the pixels without a
+    disparity as the kit does before they are scored.  Metrics names a figure by the abs part of its pair."""
+
+    def __init__(self, device=None, thresholds=((3.0, 0.05),), slots=1, interpolate=False):
+        self.pairs_thresholds = tuple((float(a), float(r)) for a, r in thresholds)
+        self.interpolate = bool(interpolate)
+        Evaluator.__init__(self, device, tuple(a for a, _ in self.pairs_thresholds), slots)
+
+    def _scratch_bytes(self, H, W):
+        return int(self.sd.hip.load().mccnn_evaluate_kitti_scratch_bytes(H, W, 1 if self.interpolate else 0))
+
+    def _new_scratch(self, H, W):
+        return self.sd.evaluate_kitti_scratch(H, W, self.device, self.interpolate)
+
+    def _evaluate(self, disp, gt, mask, **kw):
+        self.sd.evaluate_kitti(disp, gt, mask, self.pairs_thresholds, interpolate=self.interpolate, **kw)
+
+    def describe(self):
+        """What the JSON files say beside the figures."""
+        return dict(rel_thresholds=[r for _, r in self.pairs_thresholds], interpolate=self.interpolate)
+
+
 def write_json(path, obj):
     with open(path, "w") as f:
         json.dump(obj, f, indent=1, sort_keys=True)
@@ -218,13 +272,14 @@ class ListReport(object):
 
     def __init__(self, evaluator):
         self.evaluator = evaluator
+        self.extra = evaluator.describe() if hasattr(evaluator, "describe") else {}     # more keys in every file
         self.pairs = {}          # index -> (name, Metrics)
         self.skipped = {}        # index -> name
 
     def pair(self, index, name, metrics, path=None):
         self.pairs[index] = (name, metrics)
         if path is not None:
-            write_json(path, dict(metrics.to_dict(), pair=name, thresholds=list(metrics.thresholds)))
+            write_json(path, dict(metrics.to_dict(), pair=name, thresholds=list(metrics.thresholds), **self.extra))
 
     def skip(self, index, name):
         self.skipped[index] = name
@@ -235,4 +290,4 @@ class ListReport(object):
         write_json(path, dict(thresholds=list(self.evaluator.thresholds),
                               pairs=[dict(self.pairs[i][1].to_dict(), pair=self.pairs[i][0], index=i) for i in order],
                               pooled=self.evaluator.report().to_dict(), mean=mean_of(metrics),
-                              skipped=[self.skipped[i] for i in sorted(self.skipped)]))
+                              skipped=[self.skipped[i] for i in sorted(self.skipped)], **self.extra))

@@ -204,24 +204,33 @@ def pinned(a):
     return torch.from_numpy(np.ascontiguousarray(a)).pin_memory()
 
 
-def make_reader(paths, check_shape, to_host_buffer=pinned_u8, truth=None):
+def make_reader(paths, check_shape, to_host_buffer=pinned_u8, truth=None, shape=None):
     """read(index) for ListPipeline on top of match.py's file layout.  `paths(index)` -> dict(left, right, calib, out,
-    out_time, out_img, res_dir, img_dir); `check_shape(H, W, ndisp)` raises for a pair outside the envelope - before
-    anything of that pair is decoded, let alone reaches the GPU.  `truth(left_path)` (match.py --evaluate:
-    evaluation.load_ground_truth) -> (ground truth, mask or None) or None: read here as well, into pinned memory beside
-    the images (job.gt, job.mask; job.gt None = a pair without ground truth)."""
+    out_time, out_img, res_dir, img_dir[, dirs: every directory the outputs need]); `check_shape(H, W, ndisp)` raises for
+    a pair outside the envelope - before anything of that pair reaches the GPU.  `shape`: None - the size and ndisp are
+    those of the pair's calib.txt, checked before anything is decoded - or shape(left_path, left_image) -> (H, W, ndisp)
+    for a data set whose size is the decoded left image's (datasets.py: the KITTI layouts).  `truth(left_path)` (match.py
+    --evaluate: the layout's load_truth) -> (ground truth, mask or None) or None: read here as well, into pinned memory
+    beside the images (job.gt, job.mask; job.gt None = a pair without ground truth)."""
     def read(index):
         p = paths(index)
-        height, width, ndisp = util.parseCalib(p["calib"])
-        check_shape(height, width, ndisp)
-        util.recurMk(os.path.abspath(p["res_dir"]))
-        util.recurMk(os.path.abspath(p["img_dir"]))
-        left, right = decode_u8(p["left"]), decode_u8(p["right"])
+        if shape is None:
+            height, width, ndisp = util.parseCalib(p["calib"])
+            check_shape(height, width, ndisp)
+        for d in p.get("dirs", (p["res_dir"], p["img_dir"])):
+            util.recurMk(os.path.abspath(d))
+        left = decode_u8(p["left"])
+        if shape is not None:
+            height, width, ndisp = shape(p["left"], left)
+            check_shape(height, width, ndisp)
+        right = decode_u8(p["right"])
         if left.shape[2:] != right.shape[2:]:
             left, right = _three_channels(left), _three_channels(right)
         for a, which in ((left, p["left"]), (right, p["right"])):
             if a.shape[:2] != (height, width):
-                raise ValueError("%s is %dx%d, its calib.txt says %dx%d" % (which, a.shape[1], a.shape[0], width, height))
+                raise ValueError("%s is %dx%d, %s says %dx%d" % (which, a.shape[1], a.shape[0],
+                                                                 "its calib.txt" if shape is None else "the left view",
+                                                                 width, height))
         channels = 1 if left.ndim == 2 else left.shape[2]
         gt = mask = None
         found = truth(p["left"]) if truth is not None else None
@@ -235,20 +244,25 @@ def make_reader(paths, check_shape, to_host_buffer=pinned_u8, truth=None):
     return read
 
 
-def make_writer(rank=0, log=print, report=None, eval_file="evalMCCNN.json"):
+def _save_middlebury(disparity, p):
+    util.saveDisparity(disparity, p["out_img"])
+    util.writePfm(disparity, p["out"])
+
+
+def make_writer(rank=0, log=print, report=None, eval_file="evalMCCNN.json", save=_save_middlebury):
     """write(job, map, seconds) for ListPipeline: the three files of match.py, with the existing util functions; with a
-    `report` (evaluation.ListReport) also the pair's evaluation, once its 192 bytes are on the host."""
+    `report` (evaluation.ListReport) also the pair's evaluation, once its 192 bytes are on the host.  `save(result,
+    paths)` writes the map and its preview (datasets.py: a KITTI layout's result is the 16-bit plane)."""
     from datetime import datetime
 
     def write(job, disparity, seconds):
         p = job.paths
-        util.saveDisparity(disparity, p["out_img"])
-        util.writePfm(disparity, p["out"])
+        save(disparity, p)
         util.saveTimeFile(seconds, p["out_time"])
         log("[{}] {}: {:.3f} s -> {}".format(rank, datetime.now(), seconds, p["out"]))
         score = getattr(job, "score", None)       # of the map these files hold, or of the repeat that replaces it
         if report is not None and score is not None:
-            report.pair(job.index, job.name, score.metrics(), os.path.join(p["res_dir"], eval_file))
+            report.pair(job.index, job.name, score.metrics(), p.get("out_eval") or os.path.join(p["res_dir"], eval_file))
     return write
 
 
@@ -261,7 +275,7 @@ class Ticket(object):
 class MatcherBackend(object):
     """ListPipeline's backend on StereoMatchers: one matcher and one stream per slot, as match.py --pairs_in_flight."""
 
-    def __init__(self, matchers, streams, make_library_matcher, rank=0, log=print, report=None):
+    def __init__(self, matchers, streams, make_library_matcher, rank=0, log=print, report=None, device_output=None):
         import torch
         self.torch = torch
         self.matchers, self.streams = matchers, streams
@@ -275,6 +289,10 @@ class MatcherBackend(object):
         # pair only in retire(), once it is known which map is kept (the saturation redo) - in list order.
         self.report = report
         self.evaluator = report.evaluator if report is not None else None
+        # what crosses to the host for a map and what is scored: the map itself, or the pair device_output(map, scored)
+        # returns, enqueued behind the map on the slot's stream - like the evaluation NOT inside the captured graph (a
+        # KITTI layout: the 16-bit code, half the bytes, and what the file holds)
+        self.device_output = device_output
 
     def thread_init(self):
         self.torch.cuda.set_device(self.device)      # the current device is a per-thread setting
@@ -286,11 +304,14 @@ class MatcherBackend(object):
 
     def _to_host(self, disparity):
         torch = self.torch
-        host = torch.empty(tuple(disparity.shape), dtype=torch.float32, pin_memory=True)
-        host.copy_(disparity, non_blocking=True)
+        crossing, scored = disparity, disparity
+        if self.device_output is not None:
+            crossing, scored = self.device_output(disparity, self.evaluator is not None)
+        host = torch.empty(tuple(crossing.shape), dtype=crossing.dtype, pin_memory=True)
+        host.copy_(crossing, non_blocking=True)
         done = torch.cuda.Event()
         done.record()
-        return Ticket(host, done, disparity)
+        return Ticket(host, done, scored)
 
     def _score(self, slot, job, ticket, truth):
         """The evaluation of ticket.device_map behind it on the current stream; the writer finds it as job.score."""

@@ -26,6 +26,7 @@ from datetime import datetime
 
 import numpy as np
 
+import datasets
 import util
 
 # Flag names, types and defaults are the reference's command line (match.py:15-43) - that is the drop-in contract;
@@ -122,20 +123,37 @@ parser.add_argument("--evaluate", action="store_true",
                          "ground truth and over the non-occluded ones.  Writes evalMCCNN.json beside each disp0MCCNN.pfm and "
                          "submit_<tag>/eval.json (eval_rank<r>.json under torchrun) with the pooled totals; a pair without "
                          "ground truth is matched as usual and listed as skipped.  Every other output stays byte-identical")
-parser.add_argument("--eval_thresholds", type=str, default="0.5,1,2,4",
-                    help="with --evaluate: the bad-pixel thresholds in pixels, 1 to 8 comma-separated values")
+parser.add_argument("--eval_thresholds", type=str, default=None,
+                    help="with --evaluate: the bad-pixel thresholds in pixels, 1 to 8 comma-separated values (default: "
+                         "0.5,1,2,4).  With a KITTI --dataset every item is abs[:rel] - a pixel is bad when its error "
+                         "exceeds abs pixels and rel times the true disparity - and the default is the data set's own: "
+                         "3:0.05 (D1) for kitti2015, 2,3,4,5 for kitti2012")
+parser.add_argument("--dataset", choices=datasets.NAMES, default="middlebury",
+                    help="the layout of the input tree and the format of the results (src/datasets.py).  'middlebury': "
+                         "im0.png / im1.png / calib.txt per directory, PFM out.  'kitti2015': the list names "
+                         ".../image_2/NNNNNN_10.png, the right view is under image_3, the ground truth under disp_occ_0 and "
+                         "disp_noc_0 (16-bit PNG); the map is written as the development kit's 16-bit PNG to "
+                         "submit_<tag>/disp_0/, the time to submit_<tag>/time/, the evaluation to submit_<tag>/eval/.  "
+                         "'kitti2012': colored_0 / colored_1 or image_0 / image_1, disp_occ / disp_noc, maps in submit_<tag>/")
+parser.add_argument("--ndisp", type=int, default=None,
+                    help="with a KITTI --dataset: the number of disparities searched (default %d, the paper's; a "
+                         "Middlebury pair's comes from its calib.txt)" % datasets.KITTI_NDISP)
+parser.add_argument("--eval_interpolate", action="store_true",
+                    help="with --evaluate and a KITTI --dataset: fill the pixels without a disparity from their "
+                         "neighbours as the development kit does before scoring (on the device).  Without it they count "
+                         "as bad, as they do for Middlebury")
 
-# different file names
-left_image_suffix = "im0.png"
-left_gt_suffix = "disp0GT.pfm"
-right_image_suffix = "im1.png"
+# different file names (the Middlebury layout's: src/datasets.py)
+left_image_suffix = datasets.Middlebury.left_suffix
+left_gt_suffix = datasets.Middlebury.gt_suffix
+right_image_suffix = datasets.Middlebury.right_suffix
 right_gt_suffix = "disp1GT.pfm"
-calib_suffix = "calib.txt"
+calib_suffix = datasets.Middlebury.calib_suffix
 
-out_file = "disp0MCCNN.pfm"
-out_img_file = "disp0MCCNN.pgm"
-out_time_file = "timeMCCNN.txt"
-out_eval_file = "evalMCCNN.json"
+out_file = datasets.Middlebury.out_file
+out_img_file = datasets.Middlebury.out_img_file
+out_time_file = datasets.Middlebury.out_time_file
+out_eval_file = datasets.Middlebury.out_eval_file
 
 
 def hyper_parameters(args):
@@ -151,10 +169,15 @@ def main(argv=None):
     if args.fast and args.exact:
         parser.error("--fast and --exact exclude each other")
     import evaluation as ev
+    layout = datasets.get(args.dataset)
     try:
-        eval_thresholds = ev.parse_thresholds(args.eval_thresholds)
+        eval_thresholds = layout.parse_thresholds(args.eval_thresholds if args.eval_thresholds is not None
+                                                  else layout.default_thresholds)
     except ValueError as e:
         parser.error("--eval_thresholds: %s" % e)
+    ndisp_flag = datasets.resolve_ndisp(layout, args.ndisp, parser.error)
+    if args.eval_interpolate and not layout.kitti:
+        parser.error("--eval_interpolate goes with a KITTI --dataset")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -167,6 +190,14 @@ def main(argv=None):
     from distributed import shard_indices
     from model import ACCURATE_NET, NET
 
+    with open(args.list_file, "r") as f:
+        left_paths = [line.strip() for line in f.readlines()]
+    if layout.kitti:
+        # one --ndisp serves the whole list: a frame it does not fit (ndisp > W - 2) is refused here, from the image
+        # headers, before the GPU is touched
+        for index in shard_indices(args.start, args.end, len(left_paths), rank, world):
+            sd.check_envelope(*layout.shape(left_paths[index], ndisp_flag))
+
     hip.require_device()
     # one rank per GPU under torchrun; MCCNN_SHARED_GPU=1 (tests) lets several ranks share the visible GPUs
     shared = os.environ.get("MCCNN_SHARED_GPU") == "1"
@@ -176,9 +207,6 @@ def main(argv=None):
     image_root = os.path.join(args.save_dir, "submit_{}_imgs".format(args.tag))
     util.recurMk(os.path.abspath(result_root))
     util.recurMk(os.path.abspath(image_root))
-
-    with open(args.list_file, "r") as f:
-        left_paths = [line.strip() for line in f.readlines()]
 
     accurate = args.arch == "accurate"
     if accurate:
@@ -207,7 +235,8 @@ def main(argv=None):
                         fc_units=net.num_fc_units if accurate else sd.DECISION_UNITS)
     streams = [torch.cuda.Stream() for _ in range(in_flight)] if in_flight > 1 else [None]
     # --evaluate: one result buffer and scratch per slot, the list's running total on the device (src/evaluation.py)
-    report = ev.ListReport(ev.Evaluator(thresholds=eval_thresholds, slots=in_flight)) if args.evaluate else None
+    report = ev.ListReport(layout.evaluator(eval_thresholds, slots=in_flight,
+                                            interpolate=args.eval_interpolate)) if args.evaluate else None
     evaluator = report.evaluator if report is not None else None
     eval_path = os.path.join(result_root, "eval.json" if world == 1 else "eval_rank{}.json".format(rank))
     if args.pipeline:
@@ -215,22 +244,20 @@ def main(argv=None):
 
         def paths(index):
             left_path = left_paths[index]
-            pair_dir = os.path.dirname(left_path)
-            res_dir = pair_dir.replace(args.data_dir, result_root)
-            img_dir = pair_dir.replace(args.data_dir, image_root)
-            return dict(left=left_path, right=left_path.replace(left_image_suffix, right_image_suffix),
-                        calib=left_path.replace(left_image_suffix, calib_suffix), res_dir=res_dir, img_dir=img_dir,
-                        out=os.path.join(res_dir, out_file), out_time=os.path.join(res_dir, out_time_file),
-                        out_img=os.path.join(img_dir, out_img_file))
+            return dict(layout.outputs(left_path, args.data_dir, result_root, image_root), left=left_path,
+                        right=layout.right(left_path), calib=None if layout.kitti else layout.calib(left_path))
 
         def check_shape(height, width, ndisp):      # the flagless loop's refusal, with its message
             sd.workspace_bytes(height, width, ndisp, matchers[0].pixel_major(),
                                matchers[0].workspace_cbca_kernel(height, width, ndisp), **footprint_kw)
 
         backend = lm.MatcherBackend(matchers, streams, lambda: make_matcher("miopen", "library"), rank=rank,
-                                    report=report)
-        reader = lm.make_reader(paths, check_shape, truth=ev.load_ground_truth if args.evaluate else None)
-        pipeline = lm.ListPipeline(reader, backend, lm.make_writer(rank, report=report, eval_file=out_eval_file),
+                                    report=report, device_output=layout.device_output if layout.kitti else None)
+        # a KITTI frame's size is its decoded left image's: the capture policy sees every change through the job's key
+        reader = lm.make_reader(paths, check_shape, truth=layout.load_truth if args.evaluate else None,
+                                shape=(lambda left, image: layout.shape(left, ndisp_flag, image)) if layout.kitti else None)
+        pipeline = lm.ListPipeline(reader, backend,
+                                   lm.make_writer(rank, report=report, eval_file=out_eval_file, save=layout.save),
                                    slots=in_flight, readers=args.readers)
         try:
             pipeline.run(shard_indices(args.start, args.end, len(left_paths), rank, world))
@@ -247,7 +274,8 @@ def main(argv=None):
     redo = {"left": 0, "matcher": None}
 
     def finish(entry):
-        disparity, done, stTime, out_path, out_time_path, out_img_path, images, scored = entry
+        disparity, crossing, kept, done, stTime, out, images, scored = entry
+        out_path, out_time_path = out["out"], out["out_time"]
         done.synchronize()
         redone = False
         # the hand-written feature kernels report an activation beyond the range of their stored records (never seen
@@ -261,6 +289,7 @@ def main(argv=None):
                 redo["matcher"] = make_matcher("miopen", "library")
             print("[{}] ".format(rank) + matchers[0].saturation_notice().format(out_path))
             disparity = redo["matcher"].match(images[0], images[1], images[2])
+            crossing, kept = layout.device_output(disparity, scored is not None)
             torch.cuda.synchronize()
             redone = True
         if scored is not None:
@@ -268,14 +297,13 @@ def main(argv=None):
             index, name, score, gt, mask, slot, json_path = scored
             with torch.cuda.stream(streams[slot]) if in_flight > 1 else contextlib.nullcontext():
                 if redone:
-                    score = evaluator.score(disparity, gt, mask, slot)
-                evaluator.commit(disparity, gt, mask)
+                    score = evaluator.score(kept, gt, mask, slot)
+                evaluator.commit(kept, gt, mask)
             if redone:
                 torch.cuda.synchronize()     # the library matcher's output is overwritten by the next repeat
-        left_disparity_map = disparity.cpu().numpy()
+        left_disparity_map = crossing.cpu().numpy()     # the float32 map, or a KITTI layout's 16-bit plane
         endTime = time.time()
-        util.saveDisparity(left_disparity_map, out_img_path)
-        util.writePfm(left_disparity_map, out_path)
+        layout.save(left_disparity_map, out)
         util.saveTimeFile(endTime - stTime, out_time_path)
         print("[{}] {}: {:.3f} s -> {}".format(rank, datetime.now(), endTime - stTime, out_path))
         if scored is not None:
@@ -283,19 +311,15 @@ def main(argv=None):
 
     for index in shard_indices(args.start, args.end, len(left_paths), rank, world):
         left_path = left_paths[index]
-        right_path = left_path.replace(left_image_suffix, right_image_suffix)
-        calib_path = left_path.replace(left_image_suffix, calib_suffix)
-        # outputs mirror the input tree under the two roots (match.py:99-110): <root>/<dir of im0.png relative to data_dir>
-        pair_dir = os.path.dirname(left_path)
-        res_dir = pair_dir.replace(args.data_dir, result_root)
-        img_dir = pair_dir.replace(args.data_dir, image_root)
-        util.recurMk(os.path.abspath(res_dir))
-        util.recurMk(os.path.abspath(img_dir))
-        out_path = os.path.join(res_dir, out_file)
-        out_time_path = os.path.join(res_dir, out_time_file)
-        out_img_path = os.path.join(img_dir, out_img_file)
+        right_path = layout.right(left_path)
+        # Middlebury: outputs mirror the input tree under the two roots (match.py:99-110): <root>/<dir of im0.png relative
+        # to data_dir>; a KITTI layout: the development kit's submission tree (src/datasets.py)
+        out = layout.outputs(left_path, args.data_dir, result_root, image_root)
+        for d in out["dirs"]:
+            util.recurMk(os.path.abspath(d))
 
-        height, width, ndisp = util.parseCalib(calib_path)
+        # Middlebury: calib.txt; a KITTI layout: the left image's header and --ndisp
+        height, width, ndisp = layout.shape(left_path, ndisp_flag)
         print("[{}] pair {}: {} | {}  ({}x{}, ndisp {})".format(rank, index, left_path, right_path, width, height, ndisp))
         # refuses a shape outside what the kernels serve (ValueError naming the limit); each matcher checks its own
         # workspace against the free device memory before it allocates it
@@ -305,7 +329,7 @@ def main(argv=None):
             print("[{}] workspace {:.2f} GB ({} pair(s) in flight)".format(rank, footprint / 1e9, in_flight))
             last_shape = (height, width, ndisp)
 
-        truth = ev.load_ground_truth(left_path) if args.evaluate else None
+        truth = layout.load_truth(left_path) if args.evaluate else None
         if truth is not None:
             ev.check_shape(truth[0], (height, width), left_path)
         elif args.evaluate:
@@ -318,6 +342,9 @@ def main(argv=None):
             g = (g - np.mean(g, axis=(0, 1))) / np.std(g, axis=(0, 1))
             views.append(np.expand_dims(g, axis=2))
         left_image, right_image = views
+        if layout.kitti and right_image.shape != left_image.shape:
+            raise ValueError("%s is %dx%d, the left view %dx%d" % (right_path, right_image.shape[1], right_image.shape[0],
+                                                                   width, height))
         assert left_image.shape == (height, width, 1)
         assert right_image.shape == (height, width, 1)
 
@@ -334,14 +361,16 @@ def main(argv=None):
             dev_r = torch.from_numpy(right_image).cuda()
             disparity = matchers[slot].match(dev_l, dev_r, ndisp)
             scored = None
+            # what crosses to the host and what is scored: the map, or a KITTI layout's 16-bit code and what it holds,
+            # behind the map on this stream
+            crossing, kept = layout.device_output(disparity, truth is not None)
             if truth is not None:        # behind the map, on the pair's stream
                 gt = torch.from_numpy(truth[0]).cuda()
                 mask = torch.from_numpy(truth[1]).cuda() if truth[1] is not None else None
-                scored = (index, left_path, evaluator.score(disparity, gt, mask, slot), gt, mask, slot,
-                          os.path.join(res_dir, out_eval_file))
+                scored = (index, left_path, evaluator.score(kept, gt, mask, slot), gt, mask, slot, out["out_eval"])
             done = torch.cuda.Event()
             done.record()
-        pending.append((disparity, done, stTime, out_path, out_time_path, out_img_path, (dev_l, dev_r, ndisp), scored))
+        pending.append((disparity, crossing, kept, done, stTime, out, (dev_l, dev_r, ndisp), scored))
         if in_flight == 1:
             finish(pending.pop(0))
     while pending:

@@ -380,6 +380,95 @@ def evaluate(disp, gt, mask=None, thresholds=EVAL_THRESHOLDS, out=None, accumula
     return out
 
 
+# ---- KITTI: the kit's 16-bit code, background interpolation and error rule (csrc/kitti.hip) ---------------------------
+def _kitti_map(disp, who):
+    if disp.dim() != 2 or disp.dtype != torch.float32:
+        raise ValueError("%s: expected a float32 map [H,W], got %s %s" % (who, disp.dtype, tuple(disp.shape)))
+    return int(disp.shape[0]), int(disp.shape[1])
+
+
+def kitti_encode_u16(disp, out=None):
+    """disp: float32 device map [H,W] -> uint16 [H,W], the development kit's code: 0 for a pixel without a disparity (not
+    finite or < 0), else rint(disp * 256) clamped to 1 .. 65535 (include/mccnn.h).  One launch, no synchronisation."""
+    H, W = _kitti_map(disp, "kitti_encode_u16")
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.uint16, device=disp.device)
+    elif out.dtype != torch.uint16 or tuple(out.shape) != (H, W) or out.device != disp.device:
+        raise ValueError("kitti_encode_u16: `out` must be a uint16 %s on the map's device" % ((H, W),))
+    hip.check(hip.load().mccnn_kitti_encode_u16(hip.ptr(disp), H, W, hip.ptr(out), hip.stream()), "mccnn_kitti_encode_u16")
+    return out
+
+
+def kitti_decode_u16(code, out=None):
+    """code: uint16 device plane [H,W] -> float32 [H,W], what a reader of the 16-bit file sees: code / 256, 0 -> +inf
+    ("unknown" as a ground truth, no disparity as an estimate).  One launch, no synchronisation."""
+    if code.dim() != 2 or code.dtype != torch.uint16:
+        raise ValueError("kitti_decode_u16: expected a uint16 plane [H,W], got %s %s" % (code.dtype, tuple(code.shape)))
+    H, W = int(code.shape[0]), int(code.shape[1])
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.float32, device=code.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (H, W) or out.device != code.device:
+        raise ValueError("kitti_decode_u16: `out` must be a float32 %s on the plane's device" % ((H, W),))
+    hip.check(hip.load().mccnn_kitti_decode_u16(hip.ptr(code), H, W, hip.ptr(out), hip.stream()), "mccnn_kitti_decode_u16")
+    return out
+
+
+def kitti_interpolate_background(disp, out=None):
+    """The kit's interpolateBackground (include/mccnn.h): every pixel without a disparity filled from its row - the smaller
+    of the nearest valid neighbours - then from its column above the first and below the last valid row.  `out` must not
+    be `disp`.  Two launches, no synchronisation."""
+    H, W = _kitti_map(disp, "kitti_interpolate_background")
+    if out is None:
+        out = torch.empty_like(disp)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (H, W) or out.device != disp.device:
+        raise ValueError("kitti_interpolate_background: `out` must be a float32 %s on the map's device" % ((H, W),))
+    hip.check(hip.load().mccnn_kitti_interpolate_background(hip.ptr(disp), H, W, hip.ptr(out), hip.stream()),
+              "mccnn_kitti_interpolate_background")
+    return out
+
+
+def evaluate_kitti_scratch(H, W, device, interpolate=False):
+    """Scratch of one evaluate_kitti() in flight: mccnn_evaluate_kitti_scratch_bytes(H, W, interpolate) bytes."""
+    nbytes = int(hip.load().mccnn_evaluate_kitti_scratch_bytes(H, W, 1 if interpolate else 0))
+    return torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=device)
+
+
+KITTI_D1 = ((3.0, 0.05),)    # KITTI 2015: off by more than 3 px and by more than 5 % of the true disparity
+
+
+def evaluate_kitti(disp, gt_occ, gt_noc=None, thresholds=KITTI_D1, interpolate=False, out=None, accumulate=False,
+                   scratch=None):
+    """disp: float32 device map [H,W]; gt_occ, gt_noc (or None): uint16 [H,W] as the kit stores them (0 = no ground truth,
+    else disparity * 256) -> the 192-byte device tensor of evaluate(): region `all` from gt_occ, `nonocc` from gt_noc.
+    thresholds: 1 to 8 (abs, rel) pairs: a pixel is bad when its error exceeds abs pixels and rel times the true disparity.
+    interpolate: score kitti_interpolate_background(disp), held in `scratch` (an evaluate_kitti_scratch with the same
+    flag).  Everything else as evaluate()."""
+    H, W = _kitti_map(disp, "evaluate_kitti")
+    for name, t in (("gt_occ", gt_occ), ("gt_noc", gt_noc)):
+        if t is not None and (t.dtype != torch.uint16 or tuple(t.shape) != (H, W)):
+            raise ValueError("evaluate_kitti: expected a uint16 %s %s, got %s %s" % (name, (H, W), t.dtype, tuple(t.shape)))
+    for t in (gt_occ, gt_noc, out, scratch):
+        if t is not None and t.device != disp.device:
+            raise ValueError("evaluate_kitti: every tensor must live on the map's device")
+    pairs = [(float(a), float(r)) for a, r in thresholds]
+    if not 1 <= len(pairs) <= hip.MCCNN_EVAL_MAX_THRESHOLDS:
+        raise ValueError("evaluate_kitti: %d thresholds, expected 1..%d" % (len(pairs), hip.MCCNN_EVAL_MAX_THRESHOLDS))
+    if out is None:
+        if accumulate:
+            raise ValueError("evaluate_kitti: accumulate needs the `out` to accumulate into")
+        out = torch.empty((EVAL_BYTES // 8,), dtype=torch.int64, device=disp.device)
+    elif out.numel() * out.element_size() != EVAL_BYTES:
+        raise ValueError("evaluate_kitti: `out` must hold %d bytes" % EVAL_BYTES)
+    scratch = scratch if scratch is not None else evaluate_kitti_scratch(H, W, disp.device, interpolate)
+    floats = ctypes.c_float * len(pairs)
+    hip.check(hip.load().mccnn_evaluate_kitti(hip.ptr(disp), hip.ptr(gt_occ), hip.ptr(gt_noc) if gt_noc is not None else None,
+                                              H, W, floats(*[a for a, _ in pairs]), floats(*[r for _, r in pairs]),
+                                              len(pairs), 1 if interpolate else 0, 1 if accumulate else 0, hip.ptr(out),
+                                              hip.ptr(scratch), scratch.numel() * scratch.element_size(), hip.stream()),
+              "mccnn_evaluate_kitti")
+    return out
+
+
 # ---- a3 ----------------------------------------------------------------------------------------------------------
 def support_buffer(H, W, device):
     """An empty support plane (see cross_arms): the [H,W] view of a mccnn_support_bytes(H, W) allocation."""

@@ -31,6 +31,11 @@ with the current weights (stereo_device.StereoMatcher, default hyper-parameters,
 and scores the maps against disp0GT.pfm / mask0nocc.png on the device (evaluation.py), every --val_error_freq epochs on
 rank 0; the pooled val_bad1.0_nonocc, val_bad2.0_nonocc, val_bad2.0_all and val_avgerr_all go to scalars.jsonl, and
 --save_best keeps the checkpoint with the lowest val_bad2.0_nonocc as model_best.ckpt.npz.  Needs a GPU.
+Other data sets (not in the reference): --dataset kitti2012|kitti2015 maps a listed left image to its right view and its
+ground truth as the development kits lay them out (src/datasets.py) and reads the 16-bit disp_noc plane as float32 with
++inf where it holds no value, so every sampler works on the sparse truth as it does on Middlebury's.  --val_error then
+matches with --ndisp, scores with mccnn_evaluate_kitti and logs val_d1_all, val_d1_nonocc (off by more than 3 px and 5 %
+of the true disparity) and val_avgerr_all; --save_best keeps the lowest val_d1_all.
 """
 import argparse
 import json
@@ -39,6 +44,7 @@ from datetime import datetime
 
 import numpy as np
 
+import datasets
 import util
 from datagenerator import AUGMENT_KEYS      # NumPy only: torch is imported in main(), after the GPU is pinned
 
@@ -92,7 +98,16 @@ parser.add_argument("--val_error", action="store_true",
                          "weights and score it against its ground truth on the device (needs a GPU; rank 0)")
 parser.add_argument("--val_error_freq", type=int, default=1, help="with --val_error: every this many epochs")
 parser.add_argument("--save_best", action="store_true",
-                    help="with --val_error: copy the checkpoint with the lowest val_bad2.0_nonocc to model_best.ckpt.npz")
+                    help="with --val_error: copy the checkpoint with the lowest val_bad2.0_nonocc (a KITTI --dataset: "
+                         "val_d1_all) to model_best.ckpt.npz")
+parser.add_argument("--dataset", choices=datasets.NAMES, default="middlebury",
+                    help="the layout of the trees train.txt and val.txt name (src/datasets.py): where the right view and "
+                         "the ground truth of a left image are, and how the ground truth is read.  A KITTI layout trains "
+                         "on disp_noc (16-bit PNG, 0 = unknown) and --val_error then scores with the development kit's "
+                         "rule: val_d1_all, val_d1_nonocc (off by more than 3 px and 5 %%), val_avgerr_all")
+parser.add_argument("--ndisp", type=int, default=None,
+                    help="with a KITTI --dataset and --val_error: the number of disparities searched (default %d, the "
+                         "paper's)" % datasets.KITTI_NDISP)
 
 
 def parse_args(argv=None):
@@ -111,6 +126,7 @@ def parse_args(argv=None):
         parser.error("--save_best requires --val_error")
     if args.val_error_freq < 1:
         parser.error("--val_error_freq must be positive")
+    args.ndisp = datasets.resolve_ndisp(datasets.get(args.dataset), args.ndisp, parser.error)
     args.augment_overrides = overrides
     return args
 
@@ -247,6 +263,7 @@ class Trainer(object):
 
 
 VAL_ERROR_TAGS = ("val_bad1.0_nonocc", "val_bad2.0_nonocc", "val_bad2.0_all", "val_avgerr_all")
+KITTI_VAL_ERROR_TAGS = ("val_d1_all", "val_d1_nonocc", "val_avgerr_all")     # D1 = (3 px, 5 %), whichever KITTI year
 
 
 class PipelineValidator(object):
@@ -254,10 +271,14 @@ class PipelineValidator(object):
     serves every epoch: it reads the net's own tensors, and the nets' packed-weight caches are keyed by the tensors'
     _version, which every optimiser step advances."""
 
-    def __init__(self, net, list_file):
+    def __init__(self, net, list_file, layout=None, ndisp=None):
         import evaluation
         import stereo_device as sd
         self.ev = evaluation
+        self.layout = layout if layout is not None else datasets.get("middlebury")
+        self.ndisp = ndisp
+        self.tags = KITTI_VAL_ERROR_TAGS if self.layout.kitti else VAL_ERROR_TAGS
+        self.best_tag = self.tags[0] if self.layout.kitti else "val_bad2.0_nonocc"
         self.matcher = sd.StereoMatcher(net)
         with open(list_file, "r") as f:
             self.left_paths = [line.strip() for line in f if line.strip()]
@@ -265,23 +286,27 @@ class PipelineValidator(object):
     def run(self):
         """-> {tag: pooled value or None} over the pairs that have ground truth."""
         import torch
-        ev = self.ev
-        evaluator = ev.Evaluator(self.matcher.device, ev.DEFAULT_THRESHOLDS)
+        ev, layout = self.ev, self.layout
+        d1 = ((3.0, 0.05),)
+        evaluator = layout.evaluator(d1 if layout.kitti else ev.DEFAULT_THRESHOLDS, device=self.matcher.device)
         with torch.no_grad():
             for left_path in self.left_paths:
-                truth = ev.load_ground_truth(left_path)
+                truth = layout.load_truth(left_path)
                 if truth is None:
                     continue
-                height, width, ndisp = util.parseCalib(left_path.replace("im0.png", "calib.txt"))
+                height, width, ndisp = layout.shape(left_path, self.ndisp)
                 ev.check_shape(truth[0], (height, width), left_path)
                 views = []
-                for path in (left_path, left_path.replace("im0.png", "im1.png")):       # as match.py standardises
+                for path in (left_path, layout.right(left_path)):       # as match.py standardises
                     g = util.read_gray(path).astype(np.float32)
                     views.append(torch.from_numpy((g - np.mean(g, axis=(0, 1))) / np.std(g, axis=(0, 1))).cuda())
                 disparity = self.matcher.match(views[0], views[1], ndisp)
                 evaluator.pair(disparity, torch.from_numpy(truth[0]).cuda(),
                                torch.from_numpy(truth[1]).cuda() if truth[1] is not None else None)
         pooled = evaluator.report()
+        if layout.kitti:
+            return {"val_d1_all": pooled.bad(3.0, "all"), "val_d1_nonocc": pooled.bad(3.0, "nonocc"),
+                    "val_avgerr_all": pooled.figures["all"]["avgerr"]}
         return {"val_bad1.0_nonocc": pooled.bad(1.0, "nonocc"), "val_bad2.0_nonocc": pooled.bad(2.0, "nonocc"),
                 "val_bad2.0_all": pooled.bad(2.0, "all"), "val_avgerr_all": pooled.figures["all"]["avgerr"]}
 
@@ -311,6 +336,8 @@ def main(argv=None):
     os.makedirs(args.tensorboard_dir, exist_ok=True)
     os.makedirs(args.checkpoint_dir, exist_ok=True)
     ps = (args.patch_size, args.patch_size)
+    # None keeps the generators on the reference's suffix replacement; a KITTI layout maps the paths and reads the truth
+    layout = datasets.get(args.dataset) if args.dataset != "middlebury" else None
     if args.sampler == "device":
         import _hipabi
         _hipabi.require_device()                  # the cut is a HIP kernel; there is no CPU fallback
@@ -321,18 +348,19 @@ def main(argv=None):
         train_generator = datagenerator.DevicePatchSampler(
             os.path.join(args.list_dir, "train.txt"), shuffle=True, patch_size=ps,
             rng=np.random.default_rng(args.seed + 1000 * rank), device=device, sampling=args.sampling,
-            truncate=not args.subpixel_centres, augment=augment, batch_size=args.batch_size, world_size=world)
+            truncate=not args.subpixel_centres, augment=augment, batch_size=args.batch_size, world_size=world,
+            layout=layout)
         val_generator = datagenerator.DevicePatchSampler(
             os.path.join(args.list_dir, "val.txt"), shuffle=False, patch_size=ps,
-            rng=np.random.default_rng(args.seed + 7), device=device)
+            rng=np.random.default_rng(args.seed + 7), device=device, layout=layout)
         train_batches_per_epoch = train_generator.steps_per_epoch
         train_step = lambda: trainer.step_stacked(train_generator.next_batch(args.batch_size), args.batch_size)
         val_loss = lambda: trainer.loss_stacked(val_generator.next_batch(args.batch_size), args.batch_size)
     else:
         train_generator = ImageDataGenerator(os.path.join(args.list_dir, "train.txt"), shuffle=True, patch_size=ps,
-                                             rng=np.random.default_rng(args.seed + 1000 * rank))
+                                             rng=np.random.default_rng(args.seed + 1000 * rank), layout=layout)
         val_generator = ImageDataGenerator(os.path.join(args.list_dir, "val.txt"), shuffle=False, patch_size=ps,
-                                           rng=np.random.default_rng(args.seed + 7))
+                                           rng=np.random.default_rng(args.seed + 7), layout=layout)
         train_batches_per_epoch = train_generator.data_size
         train_step = lambda: trainer.step(*train_generator.next_batch(args.batch_size))
         val_loss = lambda: trainer.loss(*val_generator.next_batch(args.batch_size))
@@ -349,8 +377,9 @@ def main(argv=None):
     if args.resume is not None:
         trainer.load_state(args.resume)
     log = open(os.path.join(args.tensorboard_dir, "scalars.jsonl"), "a") if rank == 0 else None
-    validator = PipelineValidator(net, os.path.join(args.list_dir, "val.txt")) if args.val_error and rank == 0 else None
-    best = None          # the lowest val_bad2.0_nonocc so far
+    validator = PipelineValidator(net, os.path.join(args.list_dir, "val.txt"), layout,
+                                  args.ndisp) if args.val_error and rank == 0 else None
+    best = None          # the lowest val_bad2.0_nonocc (a KITTI layout: val_d1_all) so far
 
     def scalar(tag, value, step):
         if log is not None:
@@ -379,16 +408,16 @@ def main(argv=None):
         if validator is not None and (epoch + 1) % args.val_error_freq == 0:
             errors = validator.run()
             print("[{}] {}: epoch {} validation error: {}".format(rank, datetime.now(), epoch + 1, errors))
-            for tag in VAL_ERROR_TAGS:
+            for tag in validator.tags:
                 if errors[tag] is not None:
                     scalar(tag, errors[tag], train_batches_per_epoch * (epoch + 1))
-            key = errors["val_bad2.0_nonocc"]
+            key = errors[validator.best_tag]
             if args.save_best and key is not None and (best is None or key < best):
                 best = key
                 name = os.path.join(args.checkpoint_dir, "model_best.ckpt.npz")
                 np.savez(name, **trainer.state())
-                print("[{}] {}: epoch {} is the best so far (val_bad2.0_nonocc {}), saved to {}".format(
-                    rank, datetime.now(), epoch + 1, key, name))
+                print("[{}] {}: epoch {} is the best so far ({} {}), saved to {}".format(
+                    rank, datetime.now(), epoch + 1, validator.best_tag, key, name))
         if (epoch + 1) % args.val_freq == 0:
             with torch.no_grad():
                 val_ls = sum(float(val_loss())

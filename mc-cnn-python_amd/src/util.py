@@ -134,3 +134,21 @@ def pin_gpu(args, world):
     if world == 1 and (getattr(args, "gpu_explicit", False) or "HIP_VISIBLE_DEVICES" not in os.environ):
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu
         os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu
+
+
+def read_u16(path):
+    """A 16-bit greyscale PNG (PIL mode I;16) as uint16 [H,W]: KITTI's disparity files (0 = no value, else disparity
+    * 256).  Any other mode is refused: an 8-bit file here is a mistake, not a disparity map."""
+    from PIL import Image
+    im = Image.open(path)
+    if im.mode not in ("I;16", "I;16L", "I;16B"):
+        raise ValueError("%s: expected a 16-bit greyscale PNG, its mode is %s" % (path, im.mode))
+    return np.ascontiguousarray(np.asarray(im), dtype=np.uint16)
+
+
+def write_png_u16(code, filename):
+    """uint16 [H,W] -> a 16-bit greyscale PNG, at PIL's default compression."""
+    from PIL import Image
+    code = np.ascontiguousarray(code)
+    assert code.ndim == 2 and code.dtype == np.uint16
+    Image.frombytes("I;16", (code.shape[1], code.shape[0]), code.astype("<u2").tobytes()).save(filename, format="PNG")
