@@ -87,8 +87,12 @@ int mccnn_cost_volume_hwd(const float *fl, const float *fr, int H, int W, int C,
  *   w_final [units], b_final: the last layer.  mccnn_decision_pack_bytes: size of `packed` (0: outside the envelope).
  * mode MCCNN_CV_EXACT: every float32 operand as two f16 numbers, three v_mfma_f32_32x32x16_f16 products per multiply,
  *   float32 accumulation - float32-accurate scores; MCCNN_CV_MFMA: one f16 product per multiply.
- * saturation_flag (device int, may be NULL): set to 1 when an activation of a stored voxel exceeds the f16 range of
- *   the operands (|x| * 256 > 65504; clamped) - the contract of mccnn_conv3x3_split.
+ * saturation_flag (device int, may be NULL): set to 1 when an activation of a stored voxel (w >= d, d < D, w < W)
+ *   exceeds the f16 range of the operands (x * 256 > 65504, +inf included; clamped) or is NaN of either sign - in
+ *   aL + aR or in a hidden layer's pre-activation; behind the last hidden layer, which feeds the float32 final
+ *   product, NaN alone.  -inf is what relu makes of it, 0, and raises nothing: the library route agrees.  The contract
+ *   of mccnn_conv3x3_split; what a flagged call stores in such a voxel is unspecified (finite where the kernel
+ *   clamped, never the network's NaN): the flag means "repeat on the library route".  Never cleared by the call.
  * Envelope (MCCNN_E_UNSUPPORTED outside): C (feature maps behind aL / aR) 64 or 112, units = 384, n_fc 3 or 4,
  *   2 <= D <= 1024, D <= W - 2, H <= 65535; _hwd: one volume row below 2 GiB. */
 size_t mccnn_decision_pack_bytes(int n_fc, int units, int mode);

@@ -25,7 +25,9 @@
 // Precisions (one template): SPLIT carries every float32 operand as two f16 numbers (x * scale = hi + lo, 22
 // significand bits) and every multiply as three products hi*hi + hi*lo + lo*hi, float32 accumulation; the other form
 // is one f16 product per multiply.  Activations carry the factor 256 and saturate at |x| * 256 = 65504, the contract
-// of conv_mfma.hip: a clamped activation of a stored voxel raises the saturation flag.
+// of conv_mfma.hip: a clamped activation of a stored voxel raises the saturation flag.  So does a NaN in aL + aR or in
+// a hidden layer's pre-activation (the tests are made before the ReLU, which would turn NaN into 0); -inf is what relu
+// makes of it, 0, and raises nothing.
 #include "common.h"
 
 namespace mccnn {
@@ -101,9 +103,9 @@ __global__ __launch_bounds__(256) void decision_kernel(const float *__restrict__
             const float x[4] = {a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float y = fmaxf(x[i], 0.f);
-                over |= !(y * DK_ACT_SCALE <= 65504.f);
-                act[t][4 * g + i] = y;
+                // the range test on the pre-ReLU value: NaN fails it (fmaxf(NaN, 0) is 0), negative values pass
+                over |= !(x[i] * DK_ACT_SCALE <= 65504.f);
+                act[t][4 * g + i] = fmaxf(x[i], 0.f);
             }
         }
 
@@ -170,7 +172,9 @@ __global__ __launch_bounds__(256) void decision_kernel(const float *__restrict__
         }
         // bias + ReLU: the accumulators become the next layer's input (or the final product's)
         const float *pb = bias + (size_t)layer * DK_UNITS + 4 * hh;
-        const bool feeds_f16 = layer + 1 < n_layers;
+        // the range test is made before the ReLU, as above.  The last hidden layer feeds the float32 product and has
+        // no range: against +inf the test is x != x, NaN alone.  (x <= 255.875 is x * 256 <= 65504: a power of two.)
+        const float limit = layer + 1 < n_layers ? 65504.f / DK_ACT_SCALE : __builtin_inff();
 #pragma unroll
         for (int t = 0; t < DK_TILES; ++t)
 #pragma unroll
@@ -179,9 +183,9 @@ __global__ __launch_bounds__(256) void decision_kernel(const float *__restrict__
                 const float bb[4] = {b.x, b.y, b.z, b.w};
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float y = fmaxf(acc[t][4 * g + i] * inv_scale + bb[i], 0.f);
-                    over |= feeds_f16 && !(y * DK_ACT_SCALE <= 65504.f);
-                    act[t][4 * g + i] = y;
+                    const float x = acc[t][4 * g + i] * inv_scale + bb[i];
+                    over |= !(x <= limit);
+                    act[t][4 * g + i] = fmaxf(x, 0.f);
                 }
             }
     }
@@ -214,7 +218,7 @@ __global__ __launch_bounds__(256) void decision_kernel(const float *__restrict__
         else
             rcv[(rowbase + (w - d)) * sp + (size_t)d * sd] = out;
     }
-    // a stored voxel's activation left the f16 range (|x| * 256 > 65504): clamped, the score is not float32-accurate
+    // a stored voxel's activation left the f16 range (x * 256 > 65504: clamped) or was NaN: the score is not the network's
     if (sat_flag && __builtin_amdgcn_ballot_w64(over && valid) != 0 && lane == 0) atomicOr(sat_flag, 1);
 }
 

@@ -1405,9 +1405,10 @@ class StereoMatcher(object):
         return aggregation_route(self.hp["cbca_distance"], 1, 1, self.cbca_order, self.extras, self.layout,
                                  "hwd") != "plane_major"
 
-    def _saturated_pair(self, left_image, right_image, ndisp, out):
+    def _saturated_pair(self, left_image, right_image, ndisp, out, keep=None):
         """on_saturation for the pair that has just been launched: None when its features were fine (or nobody is to
-        look), else the map of the same pair behind the float32 library convolutions (written to `out` if given)."""
+        look), else the map of the same pair behind the float32 library convolutions (written to `out` if given).
+        keep: the dict the pair's stages were handed out in; the repeated pair's stages replace them."""
         if not self.saturation_checked() or self.on_saturation == "ignore" or torch.cuda.is_current_stream_capturing():
             return None
         if not self.features_saturated():
@@ -1421,14 +1422,17 @@ class StereoMatcher(object):
             self._library_twin = StereoMatcher(self.net, hp=self.hp, cv_mode=self.cv_mode, cbca_order=self.cbca_order,
                                                extras=self.extras, features="miopen", layout=self.layout,
                                                cbca_kernel=self.cbca_kernel, on_saturation="ignore", decision="library")
-        return self._library_twin.match(left_image, right_image, ndisp, out=out)
+        if keep is not None:
+            keep.clear()
+        return self._library_twin.match(left_image, right_image, ndisp, out=out, keep=keep)
 
     def match(self, left_image, right_image, ndisp, timer=_NO_TIMER, keep=None, _static_out=False, out=None):
         """_match() + the on_saturation policy (class docstring): a pair whose hand-written features were clamped is
-        matched again with the library convolutions unless the caller asked to be left alone."""
+        matched again with the library convolutions unless the caller asked to be left alone.  With `keep` the stages
+        handed out are those of the map that is returned: the repeated pair's where the pair was repeated."""
         res = self._match(left_image, right_image, ndisp, timer=timer, keep=keep, _static_out=_static_out, out=out)
-        if keep is None and not _static_out:
-            redo = self._saturated_pair(left_image, right_image, ndisp, out)
+        if not _static_out:
+            redo = self._saturated_pair(left_image, right_image, ndisp, out, keep)
             if redo is not None:
                 return redo
         return res
