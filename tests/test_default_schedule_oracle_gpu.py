@@ -44,8 +44,9 @@ def _case(env, L, R, D, hp=None):
     return Case(L, R, D, hp, l, r, fl, fr, want)
 
 
-def _matcher(env, hp=None):
-    m = env["sd"].StereoMatcher(env["net"], hp=hp) if hp else env["sd"].StereoMatcher(env["net"])
+def _matcher(env, hp=None, **kw):
+    """The default matcher; kw: what does not touch the schedule (on_saturation)."""
+    m = env["sd"].StereoMatcher(env["net"], hp=hp, **kw) if hp else env["sd"].StereoMatcher(env["net"], **kw)
     assert m.features == "split_f16" and m.pixel_major()
     assert m.free_chains and m.two_chains and m.sgm_flags_once and m.skip_unit_regions and m.refresh_first
     return m
