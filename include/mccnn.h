@@ -45,7 +45,7 @@ extern "C" {
 
 typedef void *mccnn_stream_t; /* hipStream_t */
 
-#define MCCNN_ABI_VERSION 7 /* 2: window-mask plane, *_hwd entry points; 3: saturation flags; 4: program-driven CBCA; 5: skip programs; 6: one-volume launches; 7: refresh launches, SGM flag planes as a call of their own; still 7 with the mccnn_ingest_* and the mccnn_decision_* / mccnn_cost_volume_accurate* entry points and mccnn_sample_patches, and with mccnn_evaluate, and with the mccnn_kitti_* entry points and mccnn_evaluate_kitti: purely additive, nothing that existed changed */
+#define MCCNN_ABI_VERSION 7 /* 2: window-mask plane, *_hwd entry points; 3: saturation flags; 4: program-driven CBCA; 5: skip programs; 6: one-volume launches; 7: refresh launches, SGM flag planes as a call of their own; still 7 with the mccnn_ingest_* and the mccnn_decision_* / mccnn_cost_volume_accurate* entry points and mccnn_sample_patches, and with mccnn_evaluate, and with the mccnn_kitti_* entry points and mccnn_evaluate_kitti, and with mccnn_confidence / mccnn_confidence_hwd: purely additive, nothing that existed changed */
 
 #define MCCNN_E_INVALID (-1)     /* bad argument (null pointer, non-positive size, unsupported shape) */
 #define MCCNN_E_UNSUPPORTED (-2) /* shape outside what the kernels were built for (e.g. D > 1024 for SGM) */
@@ -402,6 +402,43 @@ int mccnn_subpixel_ex(const float *disp, const float *vol_dhw, int D, int H, int
 /* mccnn_subpixel_ex on a pixel-major volume [H][W][Dp]: the same arithmetic, three neighbouring floats per pixel. */
 int mccnn_subpixel_hwd(const float *disp, const float *vol_hwd, int D, int H, int W, int numpy1_promotion, float *out,
                        mccnn_stream_t stream);
+
+/* ---- confidence measures of the left disparity: how far each pixel of the map can be trusted -------------------------
+ * One more streaming read of the final aggregated left volume (4 B/voxel, whichever measures are asked for); MSM, MMN
+ * and CUR need that volume alone, LRC the right winner-take-all map besides.  Larger always means more confident.
+ * Definitions (binding).  For one pixel (h, w) let c[d], 0 <= d < D, be its float32 costs in the final left volume; in
+ * the pixel-major layout the pad lanes D <= d < Dp are never read.
+ *   d1, c1: best = +inf, d1 = -1; for d ascending: if c[d] < best then best = c[d], d1 = d.  This is exactly mccnn_wta:
+ *     NaN and +inf never win.  c1 = c[d1].
+ *   No winner: if d1 == -1, every requested plane gets -inf (bits 0xFF800000).
+ *   c2: the same scan from +inf over d != d1, value only: an equal cost at a later index gives c2 == c1; +inf if nothing
+ *     else is below +inf.
+ *   MCCNN_CONF_MSM = 1: -c1 (a sign flip).
+ *   MCCNN_CONF_MMN = 2: c2 - c1, one float32 subtraction.
+ *   MCCNN_CONF_CUR = 4: cm = d1 >= 1 ? c[d1-1] : c[d1+1];  cp = d1 <= D-2 ? c[d1+1] : c[d1-1];
+ *     t = 2.0f * c1;  u = cp - t;  cur = u + cm: three float32 operations in the order of subpixel_hwd_kernel's
+ *     denominator; there is no contraction (the library is built with -ffp-contract=off).
+ *   MCCNN_CONF_LRC = 8: x = w - d1; if x < 0 the value is -inf.  Otherwise r = disp_right[h*W + x]; if !(r >= 0.0f) ||
+ *     r == +inf the value is -inf (that covers NaN, -1 and every negative value; -0.0 passes).  Otherwise the value is
+ *     -fabsf((float)d1 - r).
+ *   Whatever IEEE arithmetic yields for +-inf costs is the definition (c1 = c2 = -inf gives NaN for MMN).
+ * Planes are written in ascending bit order into out[K][H][W], K = popcount(measures); unrequested planes do not exist.
+ * One launch, no scratch, no atomics, no synchronisation: capturable.
+ * Refused before any HIP call (MCCNN_E_INVALID): null vol / out, D < 2, non-positive H or W, measures == 0 or bits above
+ *   15, MCCNN_CONF_LRC with a null disp_right, out overlapping disp_right; for the pixel-major entry D > 1024
+ *   (MCCNN_E_UNSUPPORTED, the envelope's limit).
+ * Out of scope: measures that need the right volume (the left-right difference: the fused winner-take-all launch leaves
+ *   that volume unwritten); measures that need exp (likelihood, entropy: not definable to the bit); the ratio measures
+ *   (these costs are negative); the local-minimum margin (after SGM and 16 aggregation iterations the curves are
+ *   unimodal: +inf for half the pixels of the reference's own volumes). */
+#define MCCNN_CONF_MSM 1u
+#define MCCNN_CONF_MMN 2u
+#define MCCNN_CONF_CUR 4u
+#define MCCNN_CONF_LRC 8u
+int mccnn_confidence_hwd(const float *vol_hwd /* [H][W][Dp] */, const float *disp_right /* NULL unless LRC */, int D,
+                         int H, int W, unsigned measures, float *out, mccnn_stream_t stream);
+int mccnn_confidence(const float *vol_dhw /* [D][H][W] */, const float *disp_right /* NULL unless LRC */, int D, int H,
+                     int W, unsigned measures, float *out, mccnn_stream_t stream);
 
 /* ---- a10 median_filter (pf:403-421): clipped fh x fw window (odd sizes, fh*fw <= 49), np.median -------------
  * np.median to the bit: NaN in the window gives NaN, and a median of -0.0 is +0.0 (np.mean's sum starts from +0).

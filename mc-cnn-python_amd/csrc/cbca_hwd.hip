@@ -30,6 +30,7 @@
 // the workgroups sweep column by column (4 rows x G columns per workgroup), so that the ~400 waves an XCD has
 // resident cover a compact window of the image whose rows stay in that XCD's 4 MiB L2 while they are being reused.
 #include "support.h"
+#include "wave_reduce.h"   // wave_min_f / wave_min_i: the WTA's reductions (also in the fused last iteration)
 
 namespace mccnn {
 namespace hw {
@@ -209,35 +210,6 @@ __device__ __forceinline__ void load_window(typename Vec<VPL>::T (&win)[NW], wm_
         }
         load_window<VPL, N + 1>(win, u, rs, voff, rowoff, pix);
     }
-}
-
-// wave-wide reductions of the WTA (also used by the fused last iteration below)
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ int dpp_i(int old, int src)
-{
-    return __builtin_amdgcn_update_dpp(old, src, CTRL, ROW_MASK, 0xf, false);
-}
-__device__ __forceinline__ float wave_min_f(float x)
-{
-    // lanes without a source keep their own value (old = x)
-    auto step = [](float v, int o) { return fminf(v, __int_as_float(o)); };
-    x = step(x, dpp_i<0xB1>(__float_as_int(x), __float_as_int(x)));         // quad_perm [1,0,3,2]
-    x = step(x, dpp_i<0x4E>(__float_as_int(x), __float_as_int(x)));         // quad_perm [2,3,0,1]
-    x = step(x, dpp_i<0x141>(__float_as_int(x), __float_as_int(x)));        // row_half_mirror
-    x = step(x, dpp_i<0x140>(__float_as_int(x), __float_as_int(x)));        // row_mirror
-    x = step(x, dpp_i<0x142, 0xA>(__float_as_int(x), __float_as_int(x)));   // row_bcast:15
-    x = step(x, dpp_i<0x143, 0xC>(__float_as_int(x), __float_as_int(x)));   // row_bcast:31
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
-}
-__device__ __forceinline__ int wave_min_i(int x)
-{
-    x = min(x, dpp_i<0xB1>(x, x));
-    x = min(x, dpp_i<0x4E>(x, x));
-    x = min(x, dpp_i<0x141>(x, x));
-    x = min(x, dpp_i<0x140>(x, x));
-    x = min(x, dpp_i<0x142, 0xA>(x, x));
-    x = min(x, dpp_i<0x143, 0xC>(x, x));
-    return __builtin_amdgcn_readlane(x, 63);
 }
 
 // One launch aggregates up to two volumes of the same shape (left and right view, each with its own support plane).

@@ -27,6 +27,10 @@ MCCNN_E_UNSUPPORTED = -2  # shape / parameter the kernels are not built for
 MCCNN_E_SCRATCH = -3      # scratch buffer too small
 
 MCCNN_EVAL_MAX_THRESHOLDS = 8
+MCCNN_CONF_MSM = 1        # mccnn_confidence / mccnn_confidence_hwd: -c1
+MCCNN_CONF_MMN = 2        # c2 - c1
+MCCNN_CONF_CUR = 4        # c[d1+1] - 2 c1 + c[d1-1]
+MCCNN_CONF_LRC = 8        # -|d1 - disp_right[h, w - d1]|
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -70,6 +74,8 @@ SIGNATURES = {
     "mccnn_cbca_iter_prog_pair_wta": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "mccnn_wta_hwd": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "mccnn_subpixel_hwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "mccnn_confidence_hwd": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_uint, _vp, _vp]),
+    "mccnn_confidence": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_uint, _vp, _vp]),
     "mccnn_hwd_pitch": (_i, [_i]),
     "mccnn_dhw_to_hwd": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "mccnn_hwd_to_dhw": (_i, [_vp, _vp, _i, _i, _i, _vp]),

@@ -80,6 +80,20 @@ class Middlebury(object):
         import evaluation
         return evaluation.parse_thresholds(text)
 
+    default_auc_threshold = "1.0"
+
+    def parse_auc_threshold(self, text):
+        """--eval_auc_threshold: one error in pixels; a pixel is bad when err > T."""
+        import evaluation
+        values = evaluation.parse_thresholds(text)
+        if len(values) != 1:
+            raise ValueError("expected one threshold, got %r" % (text,))
+        return values[0]
+
+    def confidence_path(self, paths, measure):
+        """match.py --confidence: the plane of `measure` beside disp0MCCNN.pfm."""
+        return os.path.join(paths["res_dir"], "conf0MCCNN_%s.pfm" % measure)
+
     def evaluator(self, thresholds, slots=1, interpolate=False, device=None):
         import evaluation
         return evaluation.Evaluator(device, thresholds, slots)
@@ -156,6 +170,23 @@ class Kitti(object):
     def parse_thresholds(self, text):
         import evaluation
         return evaluation.parse_kitti_thresholds(text)
+
+    default_auc_threshold = "3:0.05"
+
+    def parse_auc_threshold(self, text):
+        """--eval_auc_threshold: one abs[:rel] item; a pixel is bad when err > abs and err > rel * truth."""
+        import evaluation
+        pairs = evaluation.parse_kitti_thresholds(text)
+        if len(pairs) != 1:
+            raise ValueError("expected one abs[:rel] threshold, got %r" % (text,))
+        return pairs[0]
+
+    def confidence_path(self, paths, measure):
+        """match.py --confidence: submit_<tag>/conf_<measure>/NNNNNN_10.pfm (the submission tree's root is where its
+        time/ directory hangs)."""
+        root = os.path.dirname(os.path.dirname(paths["out_time"]))
+        stem = os.path.splitext(os.path.basename(paths["out"]))[0]
+        return os.path.join(root, "conf_%s" % measure, stem + ".pfm")
 
     def evaluator(self, thresholds, slots=1, interpolate=False, device=None):
         import evaluation

@@ -260,6 +260,130 @@ class KittiEvaluator(Evaluator):
         return dict(rel_thresholds=[r for _, r in self.pairs_thresholds], interpolate=self.interpolate)
 
 
+# ---- a score for confidence measures: the sparsification curve ---------------------------------------------------------
+# Take the n pixels of region `all`, ordered by confidence descending (a NaN confidence counts as -inf; ties by ascending
+# pixel index h*W + w: a stable sort, so that ties cannot move the curve).  B(k) = the bad pixels among the first k.
+#     auc         = (1/n) sum_{k=1..n} B(k) / k
+#     auc_optimal = (1/n) sum_{k=n-e+1..n} (k - (n-e)) / k,  e = B(n): the curve of the ordering that puts every bad pixel last
+# both float64.  A measure is the better the closer its auc is to auc_optimal; bad_rate = e / n is where every curve ends.
+def _f32(x):
+    """A Python scalar with the value float32 gives it: compared with (or multiplied into) a float32 tensor it behaves as
+    the float32 number, whichever precision the comparison runs in."""
+    return float(np.float32(x))
+
+
+def bad_and_region(disp, gt, threshold=1.0):
+    """Middlebury: (bad, region) bool [H,W] device tensors for a float32 map and ground truth.  region: gt finite (`all`
+    of mccnn_evaluate); bad: the estimate invalid (not finite, or < 0) or fabsf(disp - gt) > threshold in float32."""
+    import torch
+    region = torch.isfinite(gt)
+    invalid = ~torch.isfinite(disp) | (disp < 0)
+    err = (disp - gt).abs()
+    # (thresholds are Python scalars rounded to float32: a device tensor made from a host scalar is a blocking copy, which
+    # would make the calling thread wait for the pair just enqueued on this stream)
+    return (invalid | (err > _f32(threshold))) & region, region
+
+
+def bad_and_region_kitti(disp, gt_occ_u16, abs_thr=3.0, rel_thr=0.05):
+    """KITTI (gt_occ_u16: the kit's 16-bit codes, uint16 or a wider integer tensor): region: gt_occ != 0 (`all` of
+    mccnn_evaluate_kitti), truth g = code / 256; bad: the estimate invalid, or err > abs_thr and err > rel_thr * g,
+    float32 throughout."""
+    import torch
+    if gt_occ_u16.dtype == torch.uint16:
+        code = gt_occ_u16.view(torch.int16).to(torch.int32) & 0xFFFF
+    else:
+        code = gt_occ_u16.to(torch.int32)
+    region = code != 0
+    g = code.to(torch.float32) / 256.0
+    invalid = ~torch.isfinite(disp) | (disp < 0)
+    err = (disp - g).abs()
+    return (invalid | ((err > _f32(abs_thr)) & (err > g * _f32(rel_thr)))) & region, region
+
+
+def sparsification(confidence, bad, region):
+    """confidence: float32 [K,H,W] planes; bad, region: bool [H,W] -> float64 device tensor [3 + K]: n, e, auc_optimal and
+    the K values of auc.  torch on the current stream; no host synchronisation and no data-dependent shape: a pixel
+    outside the region gets key -inf and weight 0, ranks are the running count of the weights, n stays on the device
+    (n = 0 gives NaN for the three figures)."""
+    import torch
+    K = confidence.shape[0]
+    region = region.reshape(-1)
+    bad = (bad.reshape(-1) & region).to(torch.float64)
+    weight = region.to(torch.float64)
+    key = confidence.reshape(K, -1)
+    key = key.masked_fill(torch.isnan(key) | ~region[None, :], float("-inf")) + 0.0  # (+ 0.0: -0.0 ties with +0.0)
+    order = torch.sort(key, dim=1, descending=True, stable=True).indices
+    w = weight[order]
+    rank = torch.cumsum(w, dim=1)                                                    # k at every in-region pixel
+    run = torch.cumsum(bad[order], dim=1)                                            # B(k)
+    terms = torch.where(w > 0, run / rank.clamp(min=1.0), torch.zeros_like(run))
+    n, e = weight.sum(), bad.sum()
+    auc = terms.sum(dim=1) / n
+    k = torch.arange(1, region.numel() + 1, dtype=torch.float64, device=confidence.device)
+    first = n - e
+    optimal = torch.where((k > first) & (k <= n), (k - first) / k, torch.zeros_like(k)).sum() / n
+    return torch.cat([torch.stack([n, e, optimal]), auc])
+
+
+def sparsification_figures(values, names, threshold):
+    """The JSON entry of a pair from the host copy of sparsification()'s result."""
+    values = [float(v) for v in values]
+    n, e = int(values[0]), int(values[1])
+    return dict(threshold=threshold, n=n, bad_rate=(e / n if n > 0 else None), auc_optimal=values[2] if n > 0 else None,
+                auc={name: (values[3 + i] if n > 0 else None) for i, name in enumerate(names)})
+
+
+class SparsificationScore(object):
+    """A pair's sparsification figures on their way to the host, like PairScore: pinned float64 values + the event behind
+    the copy."""
+
+    def __init__(self, host, done, names, threshold):
+        self.host, self.done, self.names, self.threshold = host, done, names, threshold
+
+    def figures(self):
+        """Blocks until the values are on the host."""
+        self.done.synchronize()
+        return sparsification_figures(self.host.numpy(), self.names, self.threshold)
+
+
+class Sparsifier(object):
+    """match.py --evaluate --confidence: scores the confidence planes of a map against its ground truth.  threshold: a
+    float T (Middlebury: bad when err > T) or an (abs, rel) pair (KITTI: gt is the uint16 disp_occ plane)."""
+
+    def __init__(self, names, threshold):
+        self.names = tuple(names)
+        self.kitti = isinstance(threshold, (tuple, list))
+        self.threshold = [float(t) for t in threshold] if self.kitti else float(threshold)
+
+    def score(self, disp, planes, gt):
+        """Enqueued on the current stream behind the map and its planes, outside any captured graph; the 3 + K float64
+        values cross to pinned host memory where the pair's 192-byte result does.  Nothing blocks the host."""
+        import torch
+        if self.kitti:
+            bad, region = bad_and_region_kitti(disp, gt, *self.threshold)
+        else:
+            bad, region = bad_and_region(disp, gt, self.threshold)
+        values = sparsification(planes, bad, region)
+        host = torch.empty((3 + len(self.names),), dtype=torch.float64, pin_memory=True)
+        host.copy_(values, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        return SparsificationScore(host, done, self.names, self.threshold)
+
+
+def mean_sparsification(figures):
+    """Unweighted mean over the scored pairs of bad_rate, auc_optimal and every measure's auc; a pair whose figure is
+    None (an empty region) does not count."""
+    def mean(values):
+        values = [v for v in values if v is not None]
+        return sum(values) / len(values) if values else None
+
+    names = list(figures[0]["auc"]) if figures else []
+    return dict(threshold=figures[0]["threshold"] if figures else None, pairs=len(figures),
+                bad_rate=mean(f["bad_rate"] for f in figures), auc_optimal=mean(f["auc_optimal"] for f in figures),
+                auc={n: mean(f["auc"][n] for f in figures) for n in names})
+
+
 def write_json(path, obj):
     with open(path, "w") as f:
         json.dump(obj, f, indent=1, sort_keys=True)
@@ -275,11 +399,21 @@ class ListReport(object):
         self.extra = evaluator.describe() if hasattr(evaluator, "describe") else {}     # more keys in every file
         self.pairs = {}          # index -> (name, Metrics)
         self.skipped = {}        # index -> name
+        self.sparsification = {} # index -> the pair's sparsification figures (match.py --confidence only)
 
-    def pair(self, index, name, metrics, path=None):
+    def _pair_extra(self, index):
+        """The keys a pair's entry gains with --confidence; none without it, so that the files keep their bytes."""
+        return dict(sparsification=self.sparsification[index]) if index in self.sparsification else {}
+
+    def pair(self, index, name, metrics, path=None, sparsification=None):
         self.pairs[index] = (name, metrics)
+        if sparsification is not None:
+            self.sparsification[index] = sparsification
+        else:
+            self.sparsification.pop(index, None)
         if path is not None:
-            write_json(path, dict(metrics.to_dict(), pair=name, thresholds=list(metrics.thresholds), **self.extra))
+            write_json(path, dict(metrics.to_dict(), pair=name, thresholds=list(metrics.thresholds), **self.extra,
+                                  **self._pair_extra(index)))
 
     def skip(self, index, name):
         self.skipped[index] = name
@@ -287,7 +421,11 @@ class ListReport(object):
     def write(self, path):
         order = sorted(self.pairs)
         metrics = [self.pairs[i][1] for i in order]
+        mean = mean_of(metrics)
+        if self.sparsification:
+            mean["sparsification"] = mean_sparsification([self.sparsification[i] for i in order if i in self.sparsification])
         write_json(path, dict(thresholds=list(self.evaluator.thresholds),
-                              pairs=[dict(self.pairs[i][1].to_dict(), pair=self.pairs[i][0], index=i) for i in order],
-                              pooled=self.evaluator.report().to_dict(), mean=mean_of(metrics),
+                              pairs=[dict(self.pairs[i][1].to_dict(), pair=self.pairs[i][0], index=i, **self._pair_extra(i))
+                                     for i in order],
+                              pooled=self.evaluator.report().to_dict(), mean=mean,
                               skipped=[self.skipped[i] for i in sorted(self.skipped)], **self.extra))

@@ -249,33 +249,45 @@ def _save_middlebury(disparity, p):
     util.writePfm(disparity, p["out"])
 
 
-def make_writer(rank=0, log=print, report=None, eval_file="evalMCCNN.json", save=_save_middlebury):
+def make_writer(rank=0, log=print, report=None, eval_file="evalMCCNN.json", save=_save_middlebury, save_confidence=None):
     """write(job, map, seconds) for ListPipeline: the three files of match.py, with the existing util functions; with a
     `report` (evaluation.ListReport) also the pair's evaluation, once its 192 bytes are on the host.  `save(result,
-    paths)` writes the map and its preview (datasets.py: a KITTI layout's result is the 16-bit plane)."""
+    paths)` writes the map and its preview (datasets.py: a KITTI layout's result is the 16-bit plane);
+    with match.py --confidence the backend's result is the pair (map, planes) of one ticket - a repeated pair's files get
+    the repeated pair's planes - and `save_confidence(planes, paths)` writes the planes."""
     from datetime import datetime
 
     def write(job, disparity, seconds):
         p = job.paths
+        planes = None
+        if isinstance(disparity, tuple):
+            disparity, planes = disparity
         save(disparity, p)
+        if planes is not None:
+            save_confidence(planes, p)
         util.saveTimeFile(seconds, p["out_time"])
         log("[{}] {}: {:.3f} s -> {}".format(rank, datetime.now(), seconds, p["out"]))
         score = getattr(job, "score", None)       # of the map these files hold, or of the repeat that replaces it
         if report is not None and score is not None:
-            report.pair(job.index, job.name, score.metrics(), p.get("out_eval") or os.path.join(p["res_dir"], eval_file))
+            auc = getattr(job, "auc", None)
+            report.pair(job.index, job.name, score.metrics(), p.get("out_eval") or os.path.join(p["res_dir"], eval_file),
+                        **(dict(sparsification=auc.figures()) if auc is not None else {}))
     return write
 
 
 class Ticket(object):
-    def __init__(self, host, done, device_map=None):
+    def __init__(self, host, done, device_map=None, host_planes=None, device_planes=None):
         self.host, self.done, self.device_map = host, done, device_map
+        # with --confidence: the planes in a second pinned buffer, copied behind the map, and where they are on the device
+        self.host_planes, self.device_planes = host_planes, device_planes
         self.truth = None            # with --evaluate: the pair's (ground truth, mask) on the device
 
 
 class MatcherBackend(object):
     """ListPipeline's backend on StereoMatchers: one matcher and one stream per slot, as match.py --pairs_in_flight."""
 
-    def __init__(self, matchers, streams, make_library_matcher, rank=0, log=print, report=None, device_output=None):
+    def __init__(self, matchers, streams, make_library_matcher, rank=0, log=print, report=None, device_output=None,
+                 confidence=(), sparsifier=None):
         import torch
         self.torch = torch
         self.matchers, self.streams = matchers, streams
@@ -293,6 +305,13 @@ class MatcherBackend(object):
         # returns, enqueued behind the map on the slot's stream - like the evaluation NOT inside the captured graph (a
         # KITTI layout: the 16-bit code, half the bytes, and what the file holds)
         self.device_output = device_output
+        # match.py --confidence: the matchers return (map, planes); --evaluate besides: the planes are scored
+        # (evaluation.Sparsifier) behind the pair's evaluation, outside the graph like it
+        self.confidence = tuple(confidence)
+        self.sparsifier = sparsifier
+
+    def _map_and_planes(self, result):
+        return result if self.confidence else (result, None)
 
     def thread_init(self):
         self.torch.cuda.set_device(self.device)      # the current device is a per-thread setting
@@ -302,21 +321,27 @@ class MatcherBackend(object):
         s = self.streams[slot]
         return self.torch.cuda.stream(s) if s is not None else contextlib.nullcontext()
 
-    def _to_host(self, disparity):
+    def _to_host(self, disparity, planes=None):
         torch = self.torch
         crossing, scored = disparity, disparity
         if self.device_output is not None:
             crossing, scored = self.device_output(disparity, self.evaluator is not None)
         host = torch.empty(tuple(crossing.shape), dtype=crossing.dtype, pin_memory=True)
         host.copy_(crossing, non_blocking=True)
+        host_planes = None
+        if planes is not None:
+            host_planes = torch.empty(tuple(planes.shape), dtype=planes.dtype, pin_memory=True)
+            host_planes.copy_(planes, non_blocking=True)
         done = torch.cuda.Event()
         done.record()
-        return Ticket(host, done, scored)
+        return Ticket(host, done, scored, host_planes, planes)
 
     def _score(self, slot, job, ticket, truth):
         """The evaluation of ticket.device_map behind it on the current stream; the writer finds it as job.score."""
         ticket.truth = truth
         job.score = self.evaluator.score(ticket.device_map, truth[0], truth[1], slot)
+        if self.sparsifier is not None:
+            job.auc = self.sparsifier.score(ticket.device_map, ticket.device_planes, truth[0])
 
     def submit(self, slot, job, mode):
         self.log("[{}] pair {}: {}  ({}x{}, ndisp {}, {} byte(s) per pixel, {})".format(
@@ -324,10 +349,10 @@ class MatcherBackend(object):
         m = self.matchers[slot]
         with self._stream(slot):
             if mode == "eager":
-                disparity = m.match_u8(job.left, job.right, job.ndisp)
+                disparity, planes = self._map_and_planes(m.match_u8(job.left, job.right, job.ndisp))
             else:
-                disparity = m.match_graph_u8(job.left, job.right, job.ndisp)
-            ticket = self._to_host(disparity)
+                disparity, planes = self._map_and_planes(m.match_graph_u8(job.left, job.right, job.ndisp))
+            ticket = self._to_host(disparity, planes)
             if self.evaluator is not None:
                 if getattr(job, "gt", None) is None:
                     self.report.skip(job.index, job.name)
@@ -339,7 +364,9 @@ class MatcherBackend(object):
 
     def wait(self, ticket):
         ticket.done.synchronize()
-        return ticket.host.numpy()
+        if ticket.host_planes is None:
+            return ticket.host.numpy()
+        return ticket.host.numpy(), ticket.host_planes.numpy()
 
     def retire(self, slot, job, ticket):
         ticket.done.synchronize()
@@ -356,8 +383,8 @@ class MatcherBackend(object):
         if self._redo_matcher is None:
             self._redo_matcher = self.make_library_matcher()
         self.log("[{}] ".format(self.rank) + m0.saturation_notice().format(job.paths["out"]))
-        disparity = self._redo_matcher.match_u8(job.left, job.right, job.ndisp)
-        again = self._to_host(disparity)
+        disparity, planes = self._map_and_planes(self._redo_matcher.match_u8(job.left, job.right, job.ndisp))
+        again = self._to_host(disparity, planes)
         self.torch.cuda.synchronize()
         if ticket.truth is not None:
             with self._stream(slot):     # the slot's result buffer and scratch belong to the slot's stream

@@ -15,6 +15,8 @@ near-ties in the WTA can then resolve differently) and leaves every other stage 
 iteration), the fast variant of rounds 2-3, which the bit-exact aggregation has overtaken since.
 --pipeline streams the list (list_matcher.py): decoder threads, grey conversion + standardisation on the device, one
 hipGraph replay per pair where a shape repeats, a writer thread - the same files, byte for byte.
+--confidence msm,mmn,cur,lrc (any subset) writes the confidence planes of every map, conf0MCCNN_<measure>.pfm beside
+disp0MCCNN.pfm, in all three loops; with --evaluate their sparsification figures join evalMCCNN.json and eval.json.
 Multi-GPU: launch one process per GPU with different -g / -s / -e, as the reference intends (match.py:17, 26-28),
 or use `torchrun --nproc-per-node N match.py ...`: rank r then takes the pairs i = r (mod N) of the window.
 """
@@ -142,6 +144,30 @@ parser.add_argument("--eval_interpolate", action="store_true",
                     help="with --evaluate and a KITTI --dataset: fill the pixels without a disparity from their "
                          "neighbours as the development kit does before scoring (on the device).  Without it they count "
                          "as bad, as they do for Middlebury")
+parser.add_argument("--confidence", type=str, default=None,
+                    help="confidence measures of every map, a comma-separated subset of msm,mmn,cur,lrc (negated winning "
+                         "cost, margin to the runner-up, curvature at the winner, negated left-right difference; larger = "
+                         "more confident; include/mccnn.h defines them): one more launch per pair, and one float32 PFM per "
+                         "measure, conf0MCCNN_<measure>.pfm beside disp0MCCNN.pfm (a KITTI --dataset: "
+                         "submit_<tag>/conf_<measure>/NNNNNN_10.pfm).  With --evaluate the measures are scored by the area "
+                         "under their sparsification curves (\"sparsification\" in evalMCCNN.json and eval.json).  "
+                         "Every other output stays byte-identical")
+parser.add_argument("--eval_auc_threshold", type=str, default=None,
+                    help="with --evaluate --confidence: the error that makes a pixel bad on the sparsification curve, in "
+                         "pixels (default 1.0); with a KITTI --dataset abs[:rel] (default 3:0.05)")
+
+CONFIDENCE_MEASURES = ("msm", "mmn", "cur", "lrc")      # stereo_device.CONFIDENCE_MEASURES (not imported before the GPU is pinned)
+
+
+def parse_confidence(text):
+    """'mmn,lrc' -> ('mmn', 'lrc') in plane order; () for None."""
+    if text is None:
+        return ()
+    names = [t.strip() for t in str(text).split(",") if t.strip()]
+    if not names or len(set(names)) != len(names) or any(n not in CONFIDENCE_MEASURES for n in names):
+        raise ValueError("expected a comma-separated subset of %s without repeats, got %r" % (",".join(CONFIDENCE_MEASURES), text))
+    return tuple(n for n in CONFIDENCE_MEASURES if n in names)
+
 
 # different file names (the Middlebury layout's: src/datasets.py)
 left_image_suffix = datasets.Middlebury.left_suffix
@@ -176,6 +202,17 @@ def main(argv=None):
     except ValueError as e:
         parser.error("--eval_thresholds: %s" % e)
     ndisp_flag = datasets.resolve_ndisp(layout, args.ndisp, parser.error)
+    try:
+        conf_names = parse_confidence(args.confidence)
+    except ValueError as e:
+        parser.error("--confidence: %s" % e)
+    if args.eval_auc_threshold is not None and not (args.evaluate and conf_names):
+        parser.error("--eval_auc_threshold goes with --evaluate --confidence")
+    try:
+        auc_threshold = layout.parse_auc_threshold(args.eval_auc_threshold if args.eval_auc_threshold is not None
+                                                   else layout.default_auc_threshold)
+    except ValueError as e:
+        parser.error("--eval_auc_threshold: %s" % e)
     if args.eval_interpolate and not layout.kitti:
         parser.error("--eval_interpolate goes with a KITTI --dataset")
 
@@ -228,16 +265,30 @@ def main(argv=None):
             extras=dict(both_view_support=args.paper_support_regions,
                         interpolation_directions=16 if args.paper_interpolation else 4,
                         occlusion_from_left=args.paper_interpolation, numpy1_promotion=args.numpy1_promotion,
-                        sgm_independent_directions=args.paper_sgm))
+                        sgm_independent_directions=args.paper_sgm),
+            confidence=conf_names)
+
+    def map_and_planes(result):
+        """What a matcher returns, as (map, planes or None)."""
+        return result if conf_names else (result, None)
+
+    def save_confidence(planes, out):
+        """One PFM per measure from the host planes [K,H,W] (layout.confidence_path names the file)."""
+        for k, name in enumerate(conf_names):
+            path = layout.confidence_path(out, name)
+            util.recurMk(os.path.abspath(os.path.dirname(path)))
+            util.writePfm(planes[k], path)
 
     matchers = [make_matcher("miopen" if args.features == "library" else "auto") for _ in range(in_flight)]
     footprint_kw = dict(pairs_in_flight=in_flight, arch=args.arch,
-                        fc_units=net.num_fc_units if accurate else sd.DECISION_UNITS)
+                        fc_units=net.num_fc_units if accurate else sd.DECISION_UNITS, confidence=len(conf_names))
     streams = [torch.cuda.Stream() for _ in range(in_flight)] if in_flight > 1 else [None]
     # --evaluate: one result buffer and scratch per slot, the list's running total on the device (src/evaluation.py)
     report = ev.ListReport(layout.evaluator(eval_thresholds, slots=in_flight,
                                             interpolate=args.eval_interpolate)) if args.evaluate else None
     evaluator = report.evaluator if report is not None else None
+    # --evaluate --confidence: the sparsification figures of every scored pair, behind its evaluation on its stream
+    sparsifier = ev.Sparsifier(conf_names, auc_threshold) if (report is not None and conf_names) else None
     eval_path = os.path.join(result_root, "eval.json" if world == 1 else "eval_rank{}.json".format(rank))
     if args.pipeline:
         import list_matcher as lm
@@ -252,12 +303,14 @@ def main(argv=None):
                                matchers[0].workspace_cbca_kernel(height, width, ndisp), **footprint_kw)
 
         backend = lm.MatcherBackend(matchers, streams, lambda: make_matcher("miopen", "library"), rank=rank,
-                                    report=report, device_output=layout.device_output if layout.kitti else None)
+                                    report=report, device_output=layout.device_output if layout.kitti else None,
+                                    confidence=conf_names, sparsifier=sparsifier)
         # a KITTI frame's size is its decoded left image's: the capture policy sees every change through the job's key
         reader = lm.make_reader(paths, check_shape, truth=layout.load_truth if args.evaluate else None,
                                 shape=(lambda left, image: layout.shape(left, ndisp_flag, image)) if layout.kitti else None)
         pipeline = lm.ListPipeline(reader, backend,
-                                   lm.make_writer(rank, report=report, eval_file=out_eval_file, save=layout.save),
+                                   lm.make_writer(rank, report=report, eval_file=out_eval_file, save=layout.save,
+                                                  save_confidence=save_confidence if conf_names else None),
                                    slots=in_flight, readers=args.readers)
         try:
             pipeline.run(shard_indices(args.start, args.end, len(left_paths), rank, world))
@@ -274,7 +327,7 @@ def main(argv=None):
     redo = {"left": 0, "matcher": None}
 
     def finish(entry):
-        disparity, crossing, kept, done, stTime, out, images, scored = entry
+        disparity, planes, crossing, kept, done, stTime, out, images, scored = entry
         out_path, out_time_path = out["out"], out["out_time"]
         done.synchronize()
         redone = False
@@ -288,26 +341,32 @@ def main(argv=None):
             if redo["matcher"] is None:
                 redo["matcher"] = make_matcher("miopen", "library")
             print("[{}] ".format(rank) + matchers[0].saturation_notice().format(out_path))
-            disparity = redo["matcher"].match(images[0], images[1], images[2])
+            disparity, planes = map_and_planes(redo["matcher"].match(images[0], images[1], images[2]))
             crossing, kept = layout.device_output(disparity, scored is not None)
             torch.cuda.synchronize()
             redone = True
         if scored is not None:
             # the total takes the map that is kept, once, in list order; a repeated pair is scored again
-            index, name, score, gt, mask, slot, json_path = scored
+            index, name, score, auc, gt, mask, slot, json_path = scored
             with torch.cuda.stream(streams[slot]) if in_flight > 1 else contextlib.nullcontext():
                 if redone:
                     score = evaluator.score(kept, gt, mask, slot)
+                    if sparsifier is not None:
+                        auc = sparsifier.score(kept, planes, gt)
                 evaluator.commit(kept, gt, mask)
             if redone:
                 torch.cuda.synchronize()     # the library matcher's output is overwritten by the next repeat
         left_disparity_map = crossing.cpu().numpy()     # the float32 map, or a KITTI layout's 16-bit plane
+        host_planes = planes.cpu().numpy() if planes is not None else None
         endTime = time.time()
         layout.save(left_disparity_map, out)
+        if host_planes is not None:
+            save_confidence(host_planes, out)
         util.saveTimeFile(endTime - stTime, out_time_path)
         print("[{}] {}: {:.3f} s -> {}".format(rank, datetime.now(), endTime - stTime, out_path))
         if scored is not None:
-            report.pair(index, name, score.metrics(), json_path)
+            report.pair(index, name, score.metrics(), json_path,
+                        sparsification=auc.figures() if auc is not None else None)
 
     for index in shard_indices(args.start, args.end, len(left_paths), rank, world):
         left_path = left_paths[index]
@@ -359,7 +418,7 @@ def main(argv=None):
         with ctx:
             dev_l = torch.from_numpy(left_image).cuda()
             dev_r = torch.from_numpy(right_image).cuda()
-            disparity = matchers[slot].match(dev_l, dev_r, ndisp)
+            disparity, planes = map_and_planes(matchers[slot].match(dev_l, dev_r, ndisp))
             scored = None
             # what crosses to the host and what is scored: the map, or a KITTI layout's 16-bit code and what it holds,
             # behind the map on this stream
@@ -367,10 +426,12 @@ def main(argv=None):
             if truth is not None:        # behind the map, on the pair's stream
                 gt = torch.from_numpy(truth[0]).cuda()
                 mask = torch.from_numpy(truth[1]).cuda() if truth[1] is not None else None
-                scored = (index, left_path, evaluator.score(kept, gt, mask, slot), gt, mask, slot, out["out_eval"])
+                scored = (index, left_path, evaluator.score(kept, gt, mask, slot),
+                          sparsifier.score(kept, planes, gt) if sparsifier is not None else None, gt, mask, slot,
+                          out["out_eval"])
             done = torch.cuda.Event()
             done.record()
-        pending.append((disparity, crossing, kept, done, stTime, out, (dev_l, dev_r, ndisp), scored))
+        pending.append((disparity, planes, crossing, kept, done, stTime, out, (dev_l, dev_r, ndisp), scored))
         if in_flight == 1:
             finish(pending.pop(0))
     while pending:

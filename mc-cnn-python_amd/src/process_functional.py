@@ -56,7 +56,7 @@ _CBCA_ORDERS = {"separable": hip.MCCNN_CBCA_SEPARABLE, "reference": hip.MCCNN_CB
 
 __all__ = ["compute_features", "compute_cost_volume", "compute_cost_volume_accurate", "cost_volume_aggregation", "SGM_average",
            "disparity_prediction", "interpolation", "subpixel_enhance", "median_filter", "bilateral_filter",
-           "semi_global_matching", "compute_cross_region"]
+           "semi_global_matching", "compute_cross_region", "confidence_measures"]
 
 
 def _dev(x, dtype=torch.float32):
@@ -309,3 +309,17 @@ def bilateral_filter(left_image, left_disparity_map, filter_height, filter_width
     img, _ = _img(left_image)
     dl, was_np = _dev(left_disparity_map)
     return _ret(sd.bilateral(img, dl, int(filter_height), int(filter_width), mean, std_dev, blur_threshold), was_np)
+
+
+CONFIDENCE_MEASURES = sd.CONFIDENCE_MEASURES
+
+
+def confidence_measures(left_cost_volume, right_disparity_map=None, measures=CONFIDENCE_MEASURES):
+    """Not in the reference: how far each pixel of the left winner-take-all map can be trusted (include/mccnn.h has the
+    definitions; larger is more confident).  left_cost_volume: the final left volume [D,H,W] that disparity_prediction
+    reads; right_disparity_map: its right map, needed by "lrc" alone.  Returns {measure: [H,W] float32 map}."""
+    v, was_np = _dev(left_cost_volume)
+    dr = None if right_disparity_map is None else _dev(right_disparity_map)[0]
+    names = sd.confidence_names(measures)
+    planes = sd.confidence(v, dr, names)
+    return dict((n, _ret(planes[i].clone(), was_np)) for i, n in enumerate(names))

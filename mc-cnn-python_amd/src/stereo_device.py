@@ -1089,6 +1089,66 @@ def subpixel_hwd(dl, vol_hwd, D, out=None, numpy1_promotion=False):
     return out
 
 
+# ---- confidence measures of the left disparity (include/mccnn.h has the definitions) ------------------------------------
+CONFIDENCE_MEASURES = ("msm", "mmn", "cur", "lrc")        # in bit order: the order of the planes
+_CONFIDENCE_BITS = dict(msm=hip.MCCNN_CONF_MSM, mmn=hip.MCCNN_CONF_MMN, cur=hip.MCCNN_CONF_CUR, lrc=hip.MCCNN_CONF_LRC)
+
+
+def confidence_mask(names):
+    """The MCCNN_CONF_* mask of a sequence of measure names (a single name may be passed as a string).  Unknown and
+    repeated names and an empty selection are refused."""
+    names = (names,) if isinstance(names, str) else tuple(names)
+    mask = 0
+    for name in names:
+        bit = _CONFIDENCE_BITS.get(name)
+        if bit is None:
+            raise ValueError("unknown confidence measure %r: choose from %s" % (name, ", ".join(CONFIDENCE_MEASURES)))
+        if mask & bit:
+            raise ValueError("confidence measure %r named twice" % (name,))
+        mask |= bit
+    if not mask:
+        raise ValueError("no confidence measure named: choose from %s" % ", ".join(CONFIDENCE_MEASURES))
+    return mask
+
+
+def confidence_names(measures):
+    """The measures of a selection (names or a mask) in plane order."""
+    mask = measures if isinstance(measures, int) else confidence_mask(measures)
+    return tuple(n for n in CONFIDENCE_MEASURES if mask & _CONFIDENCE_BITS[n])
+
+
+def _confidence(entry, vol, D, H, W, disp_right, measures, out):
+    mask = confidence_mask(measures)
+    k = bin(mask).count("1")
+    if mask & hip.MCCNN_CONF_LRC and disp_right is None:
+        raise ValueError("%s: the lrc measure needs the right disparity map" % entry)
+    if disp_right is not None and (tuple(disp_right.shape) != (H, W) or disp_right.dtype != torch.float32):
+        raise ValueError("%s: disp_right must be a float32 [H,W] map" % entry)
+    if vol.dtype != torch.float32:
+        raise ValueError("%s: the volume must be float32" % entry)
+    if out is None:
+        out = torch.empty((k, H, W), dtype=torch.float32, device=vol.device)
+    elif tuple(out.shape) != (k, H, W) or out.dtype != torch.float32:
+        raise ValueError("%s: `out` must be a float32 [%d,%d,%d] tensor" % (entry, k, H, W))
+    hip.check(getattr(hip.load(), entry)(hip.ptr(vol), hip.ptr(disp_right) if disp_right is not None else None, int(D), H,
+                                         W, mask, hip.ptr(out), hip.stream()), entry)
+    return out
+
+
+def confidence_hwd(vol_hwd, D, disp_right=None, measures=CONFIDENCE_MEASURES, out=None):
+    """Confidence planes [K,H,W] of a pixel-major left volume [H,W,Dp], in the order of CONFIDENCE_MEASURES; disp_right:
+    the right winner-take-all map (needed by "lrc" only)."""
+    H, W, Dp = vol_hwd.shape
+    assert Dp == hwd_pitch(D)
+    return _confidence("mccnn_confidence_hwd", vol_hwd, D, H, W, disp_right, measures, out)
+
+
+def confidence(vol_dhw, disp_right=None, measures=CONFIDENCE_MEASURES, out=None):
+    """confidence_hwd() on a plane-major volume [D,H,W]: the same bits."""
+    D, H, W = vol_dhw.shape
+    return _confidence("mccnn_confidence", vol_dhw, D, H, W, disp_right, measures, out)
+
+
 def lr_status(dl, dr, ndisp, out=None):
     H, W = dl.shape
     st = out if out is not None else torch.empty((H, W), dtype=torch.int32, device=dl.device)
@@ -1193,13 +1253,15 @@ def check_envelope(H, W, D):
 
 
 def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flight=1, arch="fast",
-                    fc_units=DECISION_UNITS):
+                    fc_units=DECISION_UNITS, confidence=0):
     """Device bytes StereoMatcher.workspace(H, W, D) allocates, times `pairs_in_flight` (match.py --pairs_in_flight:
     one matcher per pair in flight): four volumes of H*W*Dp*4 bytes (Dp = hwd_pitch(D)), the SGM scratch and the flag
     planes of the four directions, both support planes, the status and map planes, and - on pixel-major volumes with
     cbca_kernel != "hwd" - the two aggregation program buffers where their programs encode the shape.  Not included:
     the feature maps (2 x H*W*64*4 bytes while the cost volume is built) and the conv activations.
-    arch="accurate": plus the two [H,W,fc_units] float32 halves of the first fully-connected layer."""
+    arch="accurate": plus the two [H,W,fc_units] float32 halves of the first fully-connected layer.
+    confidence: the number K of confidence planes the matcher was asked for (StereoMatcher(confidence=...)): plus one
+    [K,H,W] float32 buffer; 0 (default): none."""
     check_envelope(H, W, D)
     lib = hip.load()
     H, W, D = int(H), int(W), int(D)
@@ -1214,6 +1276,7 @@ def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flig
         raise ValueError("arch must be 'fast' or 'accurate'")
     if arch == "accurate":
         n += 2 * H * W * int(fc_units) * 4
+    n += int(confidence) * H * W * 4
     return n * max(1, int(pairs_in_flight))
 
 
@@ -1247,7 +1310,7 @@ class StereoMatcher(object):
     def __init__(self, net, hp=None, cv_mode=hip.MCCNN_CV_EXACT, cbca_order=hip.MCCNN_CBCA_REFERENCE_ORDER,
                  feature_tile_rows=None, extras=None, features="auto", layout="auto", cbca_kernel="auto",
                  on_saturation="fallback", skip_unit_regions=True, two_chains=True, free_chains=True, refresh_first=True,
-                 sgm_flags_once=True, decision="auto"):
+                 sgm_flags_once=True, decision="auto", confidence=()):
         self.device = hip.require_device()
         self.net = net
         self.hp = dict(DEFAULT_HP)
@@ -1322,6 +1385,10 @@ class StereoMatcher(object):
             if unknown:
                 raise ValueError("unknown extras: %s" % sorted(unknown))
             self.extras.update(extras)
+        # confidence measures of the returned map (CONFIDENCE_MEASURES; names in any order, planes in that order): one
+        # more launch per pair behind the post-processing, and every match entry returns (map, planes [K,H,W]).
+        # Empty (default): nothing changes - no launch, no buffer, the map alone is returned.
+        self.confidence = confidence_names(confidence) if confidence else ()
         self._ws = {}
         self._graphs = {}
         self._side = None
@@ -1359,7 +1426,8 @@ class StereoMatcher(object):
         if ws is None:
             need = workspace_bytes(H, W, D, self.pixel_major(), self.workspace_cbca_kernel(H, W, D),
                                    arch="accurate" if self.accurate else "fast",
-                                   fc_units=self.net.num_fc_units if self.accurate else DECISION_UNITS)
+                                   fc_units=self.net.num_fc_units if self.accurate else DECISION_UNITS,
+                                   confidence=len(self.confidence))
             self._ws, self._graphs = {}, {}          # one shape resident at a time: the previous one goes first
             _require_device_memory(need, "StereoMatcher: the workspace of a %dx%d pair with ndisp=%d" % (W, H, D))
             dp = hwd_pitch(D)
@@ -1376,6 +1444,8 @@ class StereoMatcher(object):
             if self.accurate:
                 ws["halves"] = tuple(torch.empty((H, W, self.net.num_fc_units), dtype=torch.float32, device=dev)
                                      for _ in range(2))
+            if self.confidence:
+                ws["confidence"] = torch.empty((len(self.confidence), H, W), dtype=torch.float32, device=dev)
             ws["progs"] = None
             # (distances above CBCA_HWD_MAX_DISTANCE: the aggregation programs do not encode such arms - the joined
             # two-volume path of mccnn_cbca_iter_hwd_long_pair runs, as for shapes the programs do not encode)
@@ -1405,9 +1475,10 @@ class StereoMatcher(object):
         return aggregation_route(self.hp["cbca_distance"], 1, 1, self.cbca_order, self.extras, self.layout,
                                  "hwd") != "plane_major"
 
-    def _saturated_pair(self, left_image, right_image, ndisp, out, keep=None):
+    def _saturated_pair(self, left_image, right_image, ndisp, out, keep=None, confidence_out=None):
         """on_saturation for the pair that has just been launched: None when its features were fine (or nobody is to
-        look), else the map of the same pair behind the float32 library convolutions (written to `out` if given).
+        look), else the map of the same pair behind the float32 library convolutions (written to `out` if given) - with
+        its confidence planes (written to `confidence_out` if given) where the matcher produces them.
         keep: the dict the pair's stages were handed out in; the repeated pair's stages replace them."""
         if not self.saturation_checked() or self.on_saturation == "ignore" or torch.cuda.is_current_stream_capturing():
             return None
@@ -1421,18 +1492,23 @@ class StereoMatcher(object):
         if self._library_twin is None:
             self._library_twin = StereoMatcher(self.net, hp=self.hp, cv_mode=self.cv_mode, cbca_order=self.cbca_order,
                                                extras=self.extras, features="miopen", layout=self.layout,
-                                               cbca_kernel=self.cbca_kernel, on_saturation="ignore", decision="library")
+                                               cbca_kernel=self.cbca_kernel, on_saturation="ignore", decision="library",
+                                               confidence=self.confidence)
         if keep is not None:
             keep.clear()
-        return self._library_twin.match(left_image, right_image, ndisp, out=out, keep=keep)
+        return self._library_twin.match(left_image, right_image, ndisp, out=out, keep=keep, confidence_out=confidence_out)
 
-    def match(self, left_image, right_image, ndisp, timer=_NO_TIMER, keep=None, _static_out=False, out=None):
+    def match(self, left_image, right_image, ndisp, timer=_NO_TIMER, keep=None, _static_out=False, out=None,
+              confidence_out=None):
         """_match() + the on_saturation policy (class docstring): a pair whose hand-written features were clamped is
         matched again with the library convolutions unless the caller asked to be left alone.  With `keep` the stages
-        handed out are those of the map that is returned: the repeated pair's where the pair was repeated."""
-        res = self._match(left_image, right_image, ndisp, timer=timer, keep=keep, _static_out=_static_out, out=out)
+        handed out are those of the map that is returned: the repeated pair's where the pair was repeated.
+        A matcher with confidence measures returns (map, planes [K,H,W]); the planes follow the map's rules - a copy,
+        or `confidence_out` (a contiguous float32 [K,H,W] device tensor) where one is given, next to `out`."""
+        res = self._match(left_image, right_image, ndisp, timer=timer, keep=keep, _static_out=_static_out, out=out,
+                          confidence_out=confidence_out)
         if not _static_out:
-            redo = self._saturated_pair(left_image, right_image, ndisp, out, keep)
+            redo = self._saturated_pair(left_image, right_image, ndisp, out, keep, confidence_out)
             if redo is not None:
                 return redo
         return res
@@ -1663,6 +1739,23 @@ class StereoMatcher(object):
         timer.stop()
         return dl, dr, lcv
 
+    def _confidence(self, ws, D, dr, left_volume, pixel_major, timer, keep, out, static_out):
+        """The confidence planes of the pair, from the left result volume and the right WTA map: one launch on the
+        current stream, into the workspace buffer (or `out`); handed out by _post's rules for the map."""
+        if out is not None and (out.device != dr.device or not out.is_contiguous()):
+            raise ValueError("match: `confidence_out` must be a contiguous float32 [K,H,W] tensor on the images' device")
+        dst = out if out is not None else (ws["confidence"] if keep is None else None)
+        timer.start("confidence")
+        if pixel_major:
+            planes = confidence_hwd(left_volume, D, dr, self.confidence, out=dst)
+        else:
+            planes = confidence(left_volume, dr, self.confidence, out=dst)
+        timer.stop()
+        if keep is not None:
+            keep["confidence"] = planes
+            return planes
+        return planes if (static_out or out is not None) else planes.clone()
+
     def _post(self, ws, L, D, dl, dr, left_volume, pixel_major, m, timer, keep, out, static_out):
         """a8 .. a11 on the WTA maps and the left result volume (in the layout `pixel_major` says).  Per-pair maps live
         in the workspace unless the caller keeps intermediates (tests): apart from the returned map (see `out`) a pair
@@ -1689,12 +1782,14 @@ class StereoMatcher(object):
         # or (match_graph) wants the static buffer
         return db if (static_out or out is not None) else db.clone()
 
-    def _match(self, left_image, right_image, ndisp, timer=_NO_TIMER, keep=None, _static_out=False, out=None):
+    def _match(self, left_image, right_image, ndisp, timer=_NO_TIMER, keep=None, _static_out=False, out=None,
+               confidence_out=None):
         """left/right: standardised float32 device tensors [H,W] (or [H,W,1]).  Returns the final left disparity
         map [H,W] on the device.  The matcher's workspace is reused by the next call, so the map is handed out as a
         copy - one [H,W] allocation + one copy per pair; pass `out` (a contiguous float32 [H,W] device tensor) and the
         last kernel writes there instead: nothing is allocated but the conv activations.  `keep`, if a dict, receives
-        intermediate device tensors in the reference's [D,H,W] layout (tests)."""
+        intermediate device tensors in the reference's [D,H,W] layout (tests).  A matcher with confidence measures
+        returns (map, planes) - see match()."""
         L = left_image.reshape(left_image.shape[0], left_image.shape[1]).contiguous()
         R = right_image.reshape(right_image.shape[0], right_image.shape[1]).contiguous()
         H, W = L.shape
@@ -1747,7 +1842,10 @@ class StereoMatcher(object):
                                                                timer, keep)
         else:
             dl, dr, left_volume = self._plane_major(ws, L, R, D, (lv, dhw[2]), (rv, dhw[3]), hwd, sups, m, timer, keep)
-        return self._post(ws, L, D, dl, dr, left_volume, self.pixel_major(), m, timer, keep, out, _static_out)
+        res = self._post(ws, L, D, dl, dr, left_volume, self.pixel_major(), m, timer, keep, out, _static_out)
+        if not self.confidence:
+            return res
+        return res, self._confidence(ws, D, dr, left_volume, self.pixel_major(), timer, keep, confidence_out, _static_out)
 
     def _ingest_buffers(self, H, W):
         """Static float32 inputs + ingest scratch of the eager byte path: kept per shape, so that a pair allocates
@@ -1760,7 +1858,7 @@ class StereoMatcher(object):
             self._ingest = b
         return b[1:]
 
-    def match_u8(self, left_u8, right_u8, ndisp, out=None):
+    def match_u8(self, left_u8, right_u8, ndisp, out=None, confidence_out=None):
         """match() straight from the decoded bytes of the two PNGs: uint8 device tensors [H,W] or [H,W,C] (C = 1, 3, 4;
         see ingest_u8), or pinned host tensors, which are copied in stream order without blocking.  The standardisation runs on the device, bit-identical to match.py's on the host, so the map is
         what match() returns on the host-standardised images."""
@@ -1769,7 +1867,7 @@ class StereoMatcher(object):
         left_u8 = left_u8.to(self.device, non_blocking=True).contiguous()
         right_u8 = right_u8.to(self.device, non_blocking=True).contiguous()
         ingest_u8_pair(left_u8, right_u8, sl, sr, scratch)
-        return self.match(sl, sr, ndisp, out=out)
+        return self.match(sl, sr, ndisp, out=out, confidence_out=confidence_out)
 
     def _capture(self, key, shape, make_static, prologue=None):
         """One pair captured as a graph: self._graphs[key] = (graph, static, out).  make_static() allocates and fills
@@ -1804,6 +1902,14 @@ class StereoMatcher(object):
         self._graphs[key] = (graph, static, out)
         return self._graphs[key]
 
+    def _saturated_graph_pair(self, sl, sr, ndisp, out):
+        """on_saturation behind a replay (one host synchronisation unless "ignore"): a repeated pair writes the static
+        map - and the static confidence planes, where the matcher produces them."""
+        if self.confidence:
+            self._saturated_pair(sl, sr, ndisp, out[0], confidence_out=out[1])
+        else:
+            self._saturated_pair(sl, sr, ndisp, out)
+
     def _static_u8(self, left_u8, right_u8, H, W):
         """The static buffers of match_graph_u8: (float32 left, right, the byte images, the ingest scratch)."""
         bl = torch.empty(tuple(left_u8.shape), dtype=torch.uint8, device=self.device)
@@ -1831,7 +1937,7 @@ class StereoMatcher(object):
         bl.copy_(left_u8, non_blocking=True)
         br.copy_(right_u8, non_blocking=True)
         graph.replay()
-        self._saturated_pair(sl, sr, ndisp, out)      # on_saturation (one host synchronisation unless "ignore")
+        self._saturated_graph_pair(sl, sr, ndisp, out)
         return out
 
     @staticmethod
@@ -1844,7 +1950,7 @@ class StereoMatcher(object):
     def match_graph(self, left_image, right_image, ndisp):
         """match() replayed as ONE hipGraph launch: the ~75 kernel launches of a pair are captured once per image
         shape (_capture) and replayed on static input/output buffers.  Returns the static output map [H,W] (overwritten
-        by the next call).  The images are copied into the static inputs in stream order; nothing synchronises."""
+        by the next call; with confidence measures (map, planes), both static).  The images are copied into the static inputs in stream order; nothing synchronises."""
         L = left_image.reshape(left_image.shape[0], left_image.shape[1])
         R = right_image.reshape(right_image.shape[0], right_image.shape[1])
         key = (L.shape[0], L.shape[1], int(ndisp))
@@ -1852,5 +1958,5 @@ class StereoMatcher(object):
         sl.copy_(L)
         sr.copy_(R)
         graph.replay()
-        self._saturated_pair(sl, sr, ndisp, out)      # on_saturation (one host synchronisation unless "ignore")
+        self._saturated_graph_pair(sl, sr, ndisp, out)
         return out
