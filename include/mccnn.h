@@ -391,6 +391,28 @@ int mccnn_interpolate(const float *disp_left, const int32_t *status, int H, int 
 int mccnn_interpolate_ex(const float *disp_left, const int32_t *status, int H, int W, int directions,
                          int occlusion_from_left, float *out, mccnn_stream_t stream);
 
+/* ---- a8 for the RIGHT view: the consistency check and the interpolation of the right disparity map ------------------
+ * Definition (binding): what mccnn_lr_status / mccnn_interpolate_ex give on the horizontally flipped pair, flipped back.
+ * With F(a) = a[:, ::-1]:  status_R = F(lr_status(F(disp_right), F(disp_left), D)),
+ *                          interp_R = F(interpolate_ex(F(disp_right), F(status_R), directions, occlusion_from_right)).
+ * In image coordinates, for a right pixel (h, x) with rf = disp_right[h][x] and rd = (int)rf (truncated, pf:287):
+ *   occlusion (2) if !(rf > -1) or x + rd > W-1;  match (0) if |rd - disp_left[h][x+rd]| <= 1;  mismatch (1) if some d
+ *   in 0 .. min(W-x, D)-1 has |d - disp_left[h][x+d]| <= 1, else occlusion (2).  The predicate is the float32 expression
+ *   of mccnn_lr_status; the left map may hold anything.  Rows wider than 16384 pixels: H <= 65535, as there.
+ * mccnn_interpolate_right: status 1 -> np.median (the -0.0 -> +0.0 and NaN rules of mccnn_interpolate) of the nearest
+ *   status-0 pixel left/right/below/above; status 2 -> the nearest status-0 pixel to the LEFT (the mirror of the
+ *   reference's "right"), with occlusion_from_right = 1 (the matcher's occlusion_from_left extra, mirrored) to the RIGHT;
+ *   else raw.  directions = 16: the mirrored ray set - steps of (-dx, dy) for the 16 (dx, dy) of mccnn_interpolate_ex, in
+ *   that order; the column of step k is ceil(x - k*dx - 0.5), i.e. positions round half DOWN along x (half up in the
+ *   flipped frame), the row floor(y + k*dy + 0.5) as before.  Any status word other than 0 is "no match", other than
+ *   1 / 2 leaves the raw value.  `out` must alias neither disp_right nor status (MCCNN_E_INVALID); H <= 65535
+ *   (MCCNN_E_UNSUPPORTED beyond); directions other than 4 / 16: MCCNN_E_INVALID.  (4, 0) runs without per-pixel walks,
+ *   like mccnn_interpolate. */
+int mccnn_lr_status_right(const float *disp_right, const float *disp_left, int H, int W, int D, int32_t *status,
+                          mccnn_stream_t stream);
+int mccnn_interpolate_right(const float *disp_right, const int32_t *status, int H, int W, int directions,
+                            int occlusion_from_right, float *out, mccnn_stream_t stream);
+
 /* ---- a9  subpixel_enhance (pf:381-400), float32 as NumPy 2 evaluates it ------------------------------------- */
 int mccnn_subpixel(const float *disp, const float *vol_dhw, int D, int H, int W, float *out, mccnn_stream_t stream);
 /* numpy1_promotion = 1: the scalar promotion of NumPy < 2 (the reference's own Python 2.7 environment): the
@@ -439,6 +461,15 @@ int mccnn_confidence_hwd(const float *vol_hwd /* [H][W][Dp] */, const float *dis
                          int H, int W, unsigned measures, float *out, mccnn_stream_t stream);
 int mccnn_confidence(const float *vol_dhw /* [D][H][W] */, const float *disp_right /* NULL unless LRC */, int D, int H,
                      int W, unsigned measures, float *out, mccnn_stream_t stream);
+
+/* The same measures of the RIGHT disparity, from the final aggregated right volume: MSM, MMN and CUR by the definitions
+ * above on that volume, unchanged.  LRC: x = w + d1; if x > W-1 the value is -inf.  Otherwise l = disp_left[h*W + x];
+ * if !(l >= 0.0f) || l == +inf the value is -inf.  Otherwise the value is -fabsf((float)d1 - l).  The same refusals, with
+ * disp_left in the place of disp_right. */
+int mccnn_confidence_right_hwd(const float *vol_right_hwd /* [H][W][Dp] */, const float *disp_left /* NULL unless LRC */,
+                               int D, int H, int W, unsigned measures, float *out, mccnn_stream_t stream);
+int mccnn_confidence_right(const float *vol_right_dhw /* [D][H][W] */, const float *disp_left /* NULL unless LRC */, int D,
+                           int H, int W, unsigned measures, float *out, mccnn_stream_t stream);
 
 /* ---- a10 median_filter (pf:403-421): clipped fh x fw window (odd sizes, fh*fw <= 49), np.median -------------
  * np.median to the bit: NaN in the window gives NaN, and a median of -0.0 is +0.0 (np.mean's sum starts from +0).

@@ -21,6 +21,9 @@ __device__ __forceinline__ void scan(float v, int d, float &b1, int &bd, float &
 }
 
 // The planes of one pixel from its winner d1 (< 0: none), the runner-up's cost c2 and the pixel's costs c[d * stride].
+// MIRROR: the right view's measures (mccnn_confidence_right*): the volume is the right one, `dr` the LEFT disparity map,
+// and LRC looks up column w + d1.
+template <bool MIRROR>
 __device__ __forceinline__ void write_planes(const float *__restrict__ c, size_t stride, int d1, float c2, int D, int W,
                                              long n, long N, const float *__restrict__ dr, unsigned measures,
                                              float *__restrict__ out)
@@ -42,9 +45,9 @@ __device__ __forceinline__ void write_planes(const float *__restrict__ c, size_t
         }
         if (measures & MCCNN_CONF_LRC) {
             const int w = (int)(n % W);
-            const int x = w - d1;
-            if (x >= 0) {
-                const float r = dr[n - d1];       // row h, column x
+            const int x = MIRROR ? w + d1 : w - d1;
+            if (MIRROR ? x <= W - 1 : x >= 0) {
+                const float r = dr[MIRROR ? n + d1 : n - d1];       // row h, column x
                 if (r >= 0.0f && r != __builtin_huge_valf()) lrc = -fabsf((float)d1 - r);
             }
         }
@@ -62,6 +65,7 @@ __device__ __forceinline__ void write_planes(const float *__restrict__ c, size_t
 // the minimum of what is left - the owner of d1 offers its second value, every other lane its lowest.  A minimum's BITS
 // are not unique for zero alone (-0.0 == +0.0): a runner-up that compares equal to zero is looked up again, first
 // index first, as the definition's scan meets it.  c[d1], c[d1 +- 1] and the right map are fetched by the storing lane.
+template <bool MIRROR>
 __global__ __launch_bounds__(256) void confidence_hwd_kernel(const float *__restrict__ vol, const float *__restrict__ dr,
                                                              int D, int Dp, int W, long N, unsigned measures,
                                                              float *__restrict__ out, int per_wave)
@@ -130,7 +134,7 @@ __global__ __launch_bounds__(256) void confidence_hwd_kernel(const float *__rest
             const long n = nb + lane;
             const float *p = vol + (size_t)n * Dp;
             if (i2 >= 0) c2 = p[i2];
-            write_planes(p, 1, d1, c2, D, W, n, N, dr, measures, out);
+            write_planes<MIRROR>(p, 1, d1, c2, D, W, n, N, dr, measures, out);
         }
     }
 }
@@ -138,6 +142,7 @@ __global__ __launch_bounds__(256) void confidence_hwd_kernel(const float *__rest
 // ---- plane-major [D][H][W] ------------------------------------------------------------------------------------------
 // wta_kernel's shape (post.hip): one thread per pixel, adjacent lanes on adjacent columns.  The scan is sequential in d,
 // so among equal costs the earlier index takes each place, zeros included.
+template <bool MIRROR>
 __global__ __launch_bounds__(256) void confidence_kernel(const float *__restrict__ vol, const float *__restrict__ dr,
                                                          int D, int W, long N, unsigned measures,
                                                          float *__restrict__ out)
@@ -157,23 +162,23 @@ __global__ __launch_bounds__(256) void confidence_kernel(const float *__restrict
         scan(v3, d + 3, b1, bd, b2);
     }
     for (; d < D; ++d) scan(p[(size_t)d * N], d, b1, bd, b2);
-    write_planes(p, (size_t)N, bd, b2, D, W, n, N, dr, measures, out);
+    write_planes<MIRROR>(p, (size_t)N, bd, b2, D, W, n, N, dr, measures, out);
 }
 
 static int validate(const char *who, const float *vol, const float *dr, int D, int H, int W, unsigned measures,
-                    const float *out)
+                    const float *out, const char *other = "disp_right")
 {
     MCCNN_REQUIRE(vol && out, MCCNN_E_INVALID, "%s: null pointer", who);
     MCCNN_REQUIRE(D >= 2, MCCNN_E_INVALID, "%s: D=%d, the measures need at least two disparities", who, D);
     MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "%s: non-positive size", who);
     MCCNN_REQUIRE(measures != 0 && (measures & ~kAll) == 0, MCCNN_E_INVALID,
                   "%s: measures=0x%x is not a non-empty set of MCCNN_CONF_* bits", who, measures);
-    MCCNN_REQUIRE(dr || !(measures & MCCNN_CONF_LRC), MCCNN_E_INVALID, "%s: MCCNN_CONF_LRC without disp_right", who);
+    MCCNN_REQUIRE(dr || !(measures & MCCNN_CONF_LRC), MCCNN_E_INVALID, "%s: MCCNN_CONF_LRC without %s", who, other);
     if (dr) {
         const size_t plane = (size_t)H * W * sizeof(float);
         const uintptr_t o0 = (uintptr_t)out, o1 = o0 + plane * (size_t)__builtin_popcount(measures);
         const uintptr_t r0 = (uintptr_t)dr, r1 = r0 + plane;
-        MCCNN_REQUIRE(o1 <= r0 || r1 <= o0, MCCNN_E_INVALID, "%s: out overlaps disp_right", who);
+        MCCNN_REQUIRE(o1 <= r0 || r1 <= o0, MCCNN_E_INVALID, "%s: out overlaps %s", who, other);
     }
     return 0;
 }
@@ -190,7 +195,7 @@ extern "C" int mccnn_confidence_hwd(const float *vol_hwd, const float *disp_righ
     const long N = (long)H * W;
     const int per_wave = 64;   // pixels per wave: 8 rounds of 8
     const long waves = (N + per_wave - 1) / per_wave;
-    hipLaunchKernelGGL(conf::confidence_hwd_kernel, dim3((unsigned)cdiv(waves, 4)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(conf::confidence_hwd_kernel<false>, dim3((unsigned)cdiv(waves, 4)), dim3(256), 0, (hipStream_t)stream,
                        vol_hwd, disp_right, D, mccnn_hwd_pitch(D), W, N, measures, out, per_wave);
     return check_launch("mccnn_confidence_hwd");
 }
@@ -201,7 +206,36 @@ extern "C" int mccnn_confidence(const float *vol_dhw, const float *disp_right, i
     using namespace mccnn;
     if (const int rc = conf::validate("mccnn_confidence", vol_dhw, disp_right, D, H, W, measures, out)) return rc;
     const long N = (long)H * W;
-    hipLaunchKernelGGL(conf::confidence_kernel, dim3(cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, vol_dhw,
+    hipLaunchKernelGGL(conf::confidence_kernel<false>, dim3(cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, vol_dhw,
                        disp_right, D, W, N, measures, out);
     return check_launch("mccnn_confidence");
+}
+
+extern "C" int mccnn_confidence_right_hwd(const float *vol_right_hwd, const float *disp_left, int D, int H, int W,
+                                          unsigned measures, float *out, mccnn_stream_t stream)
+{
+    using namespace mccnn;
+    if (const int rc = conf::validate("mccnn_confidence_right_hwd", vol_right_hwd, disp_left, D, H, W, measures, out,
+                                      "disp_left"))
+        return rc;
+    MCCNN_REQUIRE(D <= 1024, MCCNN_E_UNSUPPORTED, "mccnn_confidence_right_hwd: D=%d above 1024", D);
+    const long N = (long)H * W;
+    const int per_wave = 64;   // pixels per wave: 8 rounds of 8
+    const long waves = (N + per_wave - 1) / per_wave;
+    hipLaunchKernelGGL(conf::confidence_hwd_kernel<true>, dim3((unsigned)cdiv(waves, 4)), dim3(256), 0,
+                       (hipStream_t)stream, vol_right_hwd, disp_left, D, mccnn_hwd_pitch(D), W, N, measures, out, per_wave);
+    return check_launch("mccnn_confidence_right_hwd");
+}
+
+extern "C" int mccnn_confidence_right(const float *vol_right_dhw, const float *disp_left, int D, int H, int W,
+                                      unsigned measures, float *out, mccnn_stream_t stream)
+{
+    using namespace mccnn;
+    if (const int rc = conf::validate("mccnn_confidence_right", vol_right_dhw, disp_left, D, H, W, measures, out,
+                                      "disp_left"))
+        return rc;
+    const long N = (long)H * W;
+    hipLaunchKernelGGL(conf::confidence_kernel<true>, dim3(cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream,
+                       vol_right_dhw, disp_left, D, W, N, measures, out);
+    return check_launch("mccnn_confidence_right");
 }

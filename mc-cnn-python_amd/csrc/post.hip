@@ -39,6 +39,12 @@ __global__ __launch_bounds__(256) void wta_kernel(const float *__restrict__ vol,
 constexpr int MAX_GRID_Y = 65535;   // kernels that put image rows on blockIdx.y refuse taller images
 constexpr int LR_MAX_WORDS = 512;   // rows up to 16384 pixels; wider rows take lr_status_walk_kernel
 
+//
+// MIRROR: the right view's rule (mccnn_lr_status_right) - the same rule on the horizontally flipped pair, in image
+// coordinates: `dl` is then the map being judged (the right one), `dr` the other (the left one), the partner of pixel w
+// at disparity d is w + d, the candidates are d < min(W - w, D), and a pixel x of the other map with value r sets the
+// bits of w = x - d.
+template <bool MIRROR>
 __global__ __launch_bounds__(256) void lr_status_kernel(const float *__restrict__ dl, const float *__restrict__ dr,
                                                         int H, int W, int D, int32_t *__restrict__ status)
 {
@@ -54,8 +60,9 @@ __global__ __launch_bounds__(256) void lr_status_kernel(const float *__restrict_
         const int f = (int)floorf(r);
 #pragma unroll
         for (int k = -2; k <= 3; ++k) {              // |d - r| <= 1 in float32 implies d within [floor(r) - 2, floor(r) + 3]
-            const int d = f + k, w = x + d;
-            if (d >= 0 && d < D && w < W && fabsf((float)d - r) <= 1.f) atomicOr(&hit[w >> 5], 1u << (w & 31));
+            const int d = f + k, w = MIRROR ? x - d : x + d;
+            if (d >= 0 && d < D && (MIRROR ? w >= 0 : w < W) && fabsf((float)d - r) <= 1.f)
+                atomicOr(&hit[w >> 5], 1u << (w & 31));
         }
     }
     __syncthreads();
@@ -63,13 +70,13 @@ __global__ __launch_bounds__(256) void lr_status_kernel(const float *__restrict_
         const float lf = dl[(size_t)h * W + w];
         const int ld = (int)lf;  // pf:287 int() truncation
         int st;
-        if (!(lf > -1.f) || w < ld) {
+        if (!(lf > -1.f) || (MIRROR ? ld > W - 1 - w : w < ld)) {
             // pf:289-291.  A disparity <= -1 or NaN cannot come out of the reference (its WTA asserts a finite
             // minimum, pf:253); mccnn_wta writes -1 for a pixel whose costs are all NaN/+inf, and such a pixel is treated
             // as occluded here instead of indexing the right map out of bounds.  Values in (-1, 0) truncate to 0
             // (pf:287) like everywhere else.
             st = 2;
-        } else if (fabsf((float)ld - drow[w - ld]) <= 1.f) {
+        } else if (fabsf((float)ld - drow[MIRROR ? w + ld : w - ld]) <= 1.f) {
             st = 0;  // pf:294
         } else {
             st = (hit[w >> 5] >> (w & 31)) & 1u ? 1 : 2;   // pf:299-303
@@ -78,6 +85,7 @@ __global__ __launch_bounds__(256) void lr_status_kernel(const float *__restrict_
     }
 }
 
+template <bool MIRROR>
 __global__ __launch_bounds__(256) void lr_status_walk_kernel(const float *__restrict__ dl, const float *__restrict__ dr,
                                                              int H, int W, int D, int32_t *__restrict__ status)
 {
@@ -88,15 +96,15 @@ __global__ __launch_bounds__(256) void lr_status_walk_kernel(const float *__rest
     const float lf = dl[(size_t)h * W + w];
     const int ld = (int)lf;
     int st;
-    if (!(lf > -1.f) || w < ld) {
+    if (!(lf > -1.f) || (MIRROR ? ld > W - 1 - w : w < ld)) {
         st = 2;
-    } else if (fabsf((float)ld - drow[w - ld]) <= 1.f) {
+    } else if (fabsf((float)ld - drow[MIRROR ? w + ld : w - ld]) <= 1.f) {
         st = 0;
     } else {
         st = 2;
-        const int lim = min(w + 1, D);
+        const int lim = min(MIRROR ? W - w : w + 1, D);
         for (int d = 0; d < lim; ++d)
-            if (fabsf((float)d - drow[w - d]) <= 1.f) { st = 1; break; }
+            if (fabsf((float)d - drow[MIRROR ? w + d : w - d]) <= 1.f) { st = 1; break; }
     }
     status[(size_t)h * W + w] = st;
 }
@@ -127,7 +135,12 @@ __device__ __forceinline__ float median_upto4(float *v, int n)
 __constant__ float kRay16[16][2] = {{1, 0}, {1, 0.5f}, {1, 1}, {0.5f, 1}, {0, 1}, {-0.5f, 1}, {-1, 1}, {-1, 0.5f},
                                     {-1, 0}, {-1, -0.5f}, {-1, -1}, {-0.5f, -1}, {0, -1}, {0.5f, -1}, {1, -1}, {1, -0.5f}};
 
-template <bool RAYS16, bool OCC_LEFT>
+//
+// MIRROR: the right view's rules (mccnn_interpolate_right) - the same rules on the flipped map, in image coordinates.
+// The rays run the other way along x and their columns round half DOWN (W - 1 - floor(W - 1 - x + 0.5) =
+// ceil(x - 0.5)), rows still half up; the four axis neighbours come in the order left, right, below, above; an
+// occlusion takes the nearest match to its LEFT, and with OCC_LEFT (the flipped frame's "left") to its RIGHT.
+template <bool RAYS16, bool OCC_LEFT, bool MIRROR = false>
 __global__ __launch_bounds__(256) void interpolate_paper_kernel(const float *__restrict__ dl,
                                                                 const int32_t *__restrict__ st, int H, int W,
                                                                 float *__restrict__ out)
@@ -143,25 +156,28 @@ __global__ __launch_bounds__(256) void interpolate_paper_kernel(const float *__r
         int c = 0;
         if (RAYS16) {
             for (int r = 0; r < 16; ++r) {
-                const float dx = kRay16[r][0], dy = kRay16[r][1];
+                const float dx = MIRROR ? -kRay16[r][0] : kRay16[r][0], dy = kRay16[r][1];
                 float xx = (float)w, yy = (float)h;
                 for (;;) {
                     xx += dx;
                     yy += dy;
-                    const int xi = (int)floorf(xx + 0.5f), yi = (int)floorf(yy + 0.5f);
+                    const int xi = MIRROR ? (int)ceilf(xx - 0.5f) : (int)floorf(xx + 0.5f), yi = (int)floorf(yy + 0.5f);
                     if (xi < 0 || xi >= W || yi < 0 || yi >= H) break;
                     if (st[(size_t)yi * W + xi] == 0) { nb[c++] = dl[(size_t)yi * W + xi]; break; }
                 }
             }
         } else {   // the reference's four axis directions, in its order (pf:321-347)
+            if (MIRROR)
+                for (int x = w - 1; x >= 0; --x) if (st[(size_t)h * W + x] == 0) { nb[c++] = dl[(size_t)h * W + x]; break; }
             for (int x = w + 1; x < W; ++x) if (st[(size_t)h * W + x] == 0) { nb[c++] = dl[(size_t)h * W + x]; break; }
-            for (int x = w - 1; x >= 0; --x) if (st[(size_t)h * W + x] == 0) { nb[c++] = dl[(size_t)h * W + x]; break; }
+            if (!MIRROR)
+                for (int x = w - 1; x >= 0; --x) if (st[(size_t)h * W + x] == 0) { nb[c++] = dl[(size_t)h * W + x]; break; }
             for (int y = h + 1; y < H; ++y) if (st[(size_t)y * W + w] == 0) { nb[c++] = dl[(size_t)y * W + w]; break; }
             for (int y = h - 1; y >= 0; --y) if (st[(size_t)y * W + w] == 0) { nb[c++] = dl[(size_t)y * W + w]; break; }
         }
         if (c > 0) res = median_upto4(nb, c);
     } else if (s == 2) {
-        if (OCC_LEFT) {
+        if (OCC_LEFT != MIRROR) {
             for (int x = w - 1; x >= 0; --x) if (st[(size_t)h * W + x] == 0) { res = dl[(size_t)h * W + x]; break; }
         } else {
             for (int x = w + 1; x < W; ++x) if (st[(size_t)h * W + x] == 0) { res = dl[(size_t)h * W + x]; break; }
@@ -227,6 +243,27 @@ __global__ __launch_bounds__(64) void interpolate_vertical_kernel(const int32_t 
 
 constexpr int INTERP_MAX_WORDS = 256;   // rows up to 16384 pixels
 
+// nearest set bit of the row mask at a column > w (nearest_right) / < w (nearest_left), -1 if there is none
+__device__ __forceinline__ int nearest_right(const unsigned long long *mask, int nwords, int w, int W)
+{
+    if (w + 1 >= W) return -1;
+    int i = (w + 1) >> 6;
+    unsigned long long m = mask[i] & (~0ull << ((w + 1) & 63));
+    while (m == 0 && ++i < nwords) m = mask[i];
+    return m ? i * 64 + __ffsll((long long)m) - 1 : -1;
+}
+
+__device__ __forceinline__ int nearest_left(const unsigned long long *mask, int w)
+{
+    if (w < 1) return -1;
+    int i = (w - 1) >> 6;
+    unsigned long long m = mask[i] & (~0ull >> (63 - ((w - 1) & 63)));
+    while (m == 0 && --i >= 0) m = mask[i];
+    return m ? i * 64 + 63 - __clzll((long long)m) : -1;
+}
+
+// MIRROR: the right view's rule - neighbours in the order left, right, below, above, occlusions from the LEFT.
+template <bool MIRROR>
 __global__ __launch_bounds__(256) void interpolate_row_kernel(const float *__restrict__ dl,
                                                               const int32_t *__restrict__ st, int H, int W,
                                                               float *__restrict__ out)
@@ -251,29 +288,21 @@ __global__ __launch_bounds__(256) void interpolate_row_kernel(const float *__res
         float res = dl[p];
         const uint32_t vert = bits[p];
         if (s != 0) {
-            int xr = -1;   // nearest match to the right
-            if (w + 1 < W) {
-                int i = (w + 1) >> 6;
-                unsigned long long m = mask[i] & (~0ull << ((w + 1) & 63));
-                while (m == 0 && ++i < nwords) m = mask[i];
-                if (m) xr = i * 64 + __ffsll((long long)m) - 1;
-            }
-            if (s == 1) {  // pf:316-356: nearest match right, left, below, above (reads the raw map only)
+            // the side an occlusion is filled from, and the first neighbour of a mismatch: right (left when MIRROR)
+            const int x1 = MIRROR ? nearest_left(mask, w) : nearest_right(mask, nwords, w, W);
+            if (s == 1) {  // pf:316-356: nearest match right, left (MIRROR: left, right), below, above (raw map only)
                 float nb[4];
                 int c = 0;
-                if (xr >= 0) nb[c++] = dl[row + xr];
-                if (w >= 1) {
-                    int i = (w - 1) >> 6;
-                    unsigned long long m = mask[i] & (~0ull >> (63 - ((w - 1) & 63)));
-                    while (m == 0 && --i >= 0) m = mask[i];
-                    if (m) nb[c++] = dl[row + i * 64 + 63 - __clzll((long long)m)];
-                }
+                if (x1 >= 0) nb[c++] = dl[row + x1];
+                const int x2 = MIRROR ? nearest_right(mask, nwords, w, W) : nearest_left(mask, w);
+                if (x2 >= 0) nb[c++] = dl[row + x2];
                 const uint32_t below = vert >> 16, above = vert & 0xffffu;
                 if (below != 0xffffu) nb[c++] = dl[(size_t)below * W + w];
                 if (above != 0xffffu) nb[c++] = dl[(size_t)above * W + w];
                 if (c > 0) res = median_upto4(nb, c);
-            } else if (s == 2 && xr >= 0) {  // pf:358-373: nearest match to the right (any other word: the raw value)
-                res = dl[row + xr];
+            } else if (s == 2 && x1 >= 0) {  // pf:358-373: nearest match to the right, MIRROR: to the left (any other
+                                             // word: the raw value)
+                res = dl[row + x1];
             }
         }
         out[p] = res;
@@ -612,10 +641,10 @@ extern "C" int mccnn_lr_status(const float *disp_left, const float *disp_right, 
     MCCNN_REQUIRE(W <= 32 * LR_MAX_WORDS || H <= MAX_GRID_Y, MCCNN_E_UNSUPPORTED,
                   "mccnn_lr_status: H=%d exceeds grid.y for rows wider than %d", H, 32 * LR_MAX_WORDS);
     if (W <= 32 * LR_MAX_WORDS)
-        hipLaunchKernelGGL(lr_status_kernel, dim3(H), dim3(256), 0, (hipStream_t)stream, disp_left, disp_right, H, W, D,
+        hipLaunchKernelGGL(lr_status_kernel<false>, dim3(H), dim3(256), 0, (hipStream_t)stream, disp_left, disp_right, H, W, D,
                            status);
     else
-        hipLaunchKernelGGL(lr_status_walk_kernel, dim3(cdiv(W, 256), H), dim3(256), 0, (hipStream_t)stream, disp_left,
+        hipLaunchKernelGGL(lr_status_walk_kernel<false>, dim3(cdiv(W, 256), H), dim3(256), 0, (hipStream_t)stream, disp_left,
                            disp_right, H, W, D, status);
     return check_launch("mccnn_lr_status");
 }
@@ -635,7 +664,7 @@ extern "C" int mccnn_interpolate(const float *disp_left, const int32_t *status, 
                            W, reinterpret_cast<uint16_t *>(out));
         int rc = check_launch("mccnn_interpolate(vertical)");
         if (rc) return rc;
-        hipLaunchKernelGGL(interpolate_row_kernel, dim3(H), dim3(256), 0, (hipStream_t)stream, disp_left, status, H, W,
+        hipLaunchKernelGGL(interpolate_row_kernel<false>, dim3(H), dim3(256), 0, (hipStream_t)stream, disp_left, status, H, W,
                            out);
         return check_launch("mccnn_interpolate(rows)");
     }
@@ -667,6 +696,56 @@ extern "C" int mccnn_interpolate_ex(const float *disp_left, const int32_t *statu
     else
         hipLaunchKernelGGL(interpolate_kernel, grid, block, 0, s, disp_left, status, H, W, out);
     return check_launch("mccnn_interpolate_ex");
+}
+
+extern "C" int mccnn_lr_status_right(const float *disp_right, const float *disp_left, int H, int W, int D,
+                                     int32_t *status, mccnn_stream_t stream)
+{
+    using namespace mccnn;
+    MCCNN_REQUIRE(disp_right && disp_left && status, MCCNN_E_INVALID, "mccnn_lr_status_right: null pointer");
+    MCCNN_REQUIRE(D > 0 && H > 0 && W > 0, MCCNN_E_INVALID, "mccnn_lr_status_right: non-positive size");
+    MCCNN_REQUIRE(W <= 32 * LR_MAX_WORDS || H <= MAX_GRID_Y, MCCNN_E_UNSUPPORTED,
+                  "mccnn_lr_status_right: H=%d exceeds grid.y for rows wider than %d", H, 32 * LR_MAX_WORDS);
+    if (W <= 32 * LR_MAX_WORDS)
+        hipLaunchKernelGGL(lr_status_kernel<true>, dim3(H), dim3(256), 0, (hipStream_t)stream, disp_right, disp_left, H,
+                           W, D, status);
+    else
+        hipLaunchKernelGGL(lr_status_walk_kernel<true>, dim3(cdiv(W, 256), H), dim3(256), 0, (hipStream_t)stream,
+                           disp_right, disp_left, H, W, D, status);
+    return check_launch("mccnn_lr_status_right");
+}
+
+extern "C" int mccnn_interpolate_right(const float *disp_right, const int32_t *status, int H, int W, int directions,
+                                       int occlusion_from_right, float *out, mccnn_stream_t stream)
+{
+    using namespace mccnn;
+    MCCNN_REQUIRE(disp_right && status && out, MCCNN_E_INVALID, "mccnn_interpolate_right: null pointer");
+    MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "mccnn_interpolate_right: non-positive size");
+    MCCNN_REQUIRE(disp_right != out, MCCNN_E_INVALID, "mccnn_interpolate_right: out must not alias the input map");
+    MCCNN_REQUIRE((const void *)status != (const void *)out, MCCNN_E_INVALID,
+                  "mccnn_interpolate_right: out must not alias the status map");
+    MCCNN_REQUIRE(H <= MAX_GRID_Y, MCCNN_E_UNSUPPORTED, "mccnn_interpolate_right: H=%d exceeds grid.y", H);
+    MCCNN_REQUIRE(directions == 4 || directions == 16, MCCNN_E_INVALID,
+                  "mccnn_interpolate_right: directions=%d (4 or 16)", directions);
+    hipStream_t s = (hipStream_t)stream;
+    if (directions == 4 && !occlusion_from_right && H < 65535 && W <= 64 * INTERP_MAX_WORDS) {
+        hipLaunchKernelGGL(interpolate_vertical_kernel, dim3(cdiv(W, 64), 2), dim3(64), 0, s, status, H, W,
+                           reinterpret_cast<uint16_t *>(out));
+        int rc = check_launch("mccnn_interpolate_right(vertical)");
+        if (rc) return rc;
+        hipLaunchKernelGGL(interpolate_row_kernel<true>, dim3(H), dim3(256), 0, s, disp_right, status, H, W, out);
+        return check_launch("mccnn_interpolate_right(rows)");
+    }
+    const dim3 grid(cdiv(W, 256), H), block(256);
+    if (directions == 16 && occlusion_from_right)
+        hipLaunchKernelGGL((interpolate_paper_kernel<true, true, true>), grid, block, 0, s, disp_right, status, H, W, out);
+    else if (directions == 16)
+        hipLaunchKernelGGL((interpolate_paper_kernel<true, false, true>), grid, block, 0, s, disp_right, status, H, W, out);
+    else if (occlusion_from_right)
+        hipLaunchKernelGGL((interpolate_paper_kernel<false, true, true>), grid, block, 0, s, disp_right, status, H, W, out);
+    else
+        hipLaunchKernelGGL((interpolate_paper_kernel<false, false, true>), grid, block, 0, s, disp_right, status, H, W, out);
+    return check_launch("mccnn_interpolate_right");
 }
 
 extern "C" int mccnn_subpixel_ex(const float *disp, const float *vol_dhw, int D, int H, int W, int numpy1_promotion,

@@ -76,6 +76,8 @@ SIGNATURES = {
     "mccnn_subpixel_hwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "mccnn_confidence_hwd": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_uint, _vp, _vp]),
     "mccnn_confidence": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_uint, _vp, _vp]),
+    "mccnn_confidence_right_hwd": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_uint, _vp, _vp]),
+    "mccnn_confidence_right": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_uint, _vp, _vp]),
     "mccnn_hwd_pitch": (_i, [_i]),
     "mccnn_dhw_to_hwd": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "mccnn_hwd_to_dhw": (_i, [_vp, _vp, _i, _i, _i, _vp]),
@@ -93,6 +95,8 @@ SIGNATURES = {
     "mccnn_lr_status": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "mccnn_interpolate": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "mccnn_interpolate_ex": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "mccnn_lr_status_right": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "mccnn_interpolate_right": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "mccnn_subpixel": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "mccnn_subpixel_ex": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "mccnn_median": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),

@@ -48,9 +48,20 @@ class Middlebury(object):
     left_suffix, right_suffix, calib_suffix, gt_suffix = "im0.png", "im1.png", "calib.txt", "disp0GT.pfm"
     out_file, out_img_file, out_time_file, out_eval_file = "disp0MCCNN.pfm", "disp0MCCNN.pgm", "timeMCCNN.txt", "evalMCCNN.json"
     default_thresholds = "0.5,1,2,4"
+    # match.py --views both: the right view's map, preview and ground truth (Middlebury ships disp1GT.pfm / mask1nocc.png)
+    right_gt_suffix, right_out_file, right_out_img_file = "disp1GT.pfm", "disp1MCCNN.pfm", "disp1MCCNN.pgm"
 
     def right(self, left):
         return left.replace(self.left_suffix, self.right_suffix)
+
+    def load_truth_right(self, left):
+        """load_truth() of the RIGHT view: disp1GT.pfm / mask1nocc.png beside the left image, or None."""
+        import evaluation
+        return evaluation.load_ground_truth(left, view="right")
+
+    def save_right(self, disparity, paths):
+        util.saveDisparity(disparity, paths["out_img_right"])
+        util.writePfm(disparity, paths["out_right"])
 
     def calib(self, left):
         return left.replace(self.left_suffix, self.calib_suffix)
@@ -74,7 +85,9 @@ class Middlebury(object):
         img_dir = pair_dir.replace(data_dir, image_root)
         return dict(res_dir=res_dir, img_dir=img_dir, dirs=(res_dir, img_dir), out=os.path.join(res_dir, self.out_file),
                     out_time=os.path.join(res_dir, self.out_time_file), out_img=os.path.join(img_dir, self.out_img_file),
-                    out_eval=os.path.join(res_dir, self.out_eval_file))
+                    out_eval=os.path.join(res_dir, self.out_eval_file),
+                    out_right=os.path.join(res_dir, self.right_out_file),
+                    out_img_right=os.path.join(img_dir, self.right_out_img_file))
 
     def parse_thresholds(self, text):
         import evaluation
@@ -90,9 +103,9 @@ class Middlebury(object):
             raise ValueError("expected one threshold, got %r" % (text,))
         return values[0]
 
-    def confidence_path(self, paths, measure):
-        """match.py --confidence: the plane of `measure` beside disp0MCCNN.pfm."""
-        return os.path.join(paths["res_dir"], "conf0MCCNN_%s.pfm" % measure)
+    def confidence_path(self, paths, measure, view=0):
+        """match.py --confidence: the plane of `measure` beside disp0MCCNN.pfm (view 1, --views both: conf1MCCNN_*)."""
+        return os.path.join(paths["res_dir"], "conf%dMCCNN_%s.pfm" % (int(view), measure))
 
     def evaluator(self, thresholds, slots=1, interpolate=False, device=None):
         import evaluation

@@ -25,6 +25,8 @@ import util
 GT_SUFFIX = "disp0GT.pfm"        # beside im0.png, like match.py's left_gt_suffix
 MASK_SUFFIX = "mask0nocc.png"    # 255 non-occluded, 128 occluded, 0 unknown
 LEFT_SUFFIX = "im0.png"
+RIGHT_GT_SUFFIX = "disp1GT.pfm"      # the right view's, match.py --views both
+RIGHT_MASK_SUFFIX = "mask1nocc.png"
 DEFAULT_THRESHOLDS = (0.5, 1.0, 2.0, 4.0)
 REGIONS = ("all", "nonocc")
 RESULT_BYTES = 192
@@ -126,15 +128,16 @@ def mean_of(metrics):
     return out
 
 
-def load_ground_truth(left_path):
+def load_ground_truth(left_path, view="left"):
     """(gt float32 [H,W] with +inf where unknown, mask uint8 [H,W] or None) from disp0GT.pfm / mask0nocc.png beside the
-    left image; None when there is no ground-truth file."""
+    left image; None when there is no ground-truth file.  view="right": disp1GT.pfm / mask1nocc.png."""
     pair_dir = os.path.dirname(left_path)
-    gt_path = os.path.join(pair_dir, GT_SUFFIX)
+    gt_name, mask_name = (GT_SUFFIX, MASK_SUFFIX) if view == "left" else (RIGHT_GT_SUFFIX, RIGHT_MASK_SUFFIX)
+    gt_path = os.path.join(pair_dir, gt_name)
     if not os.path.isfile(gt_path):
         return None
     gt = np.ascontiguousarray(util.readPfm(gt_path), dtype=np.float32)
-    mask_path = os.path.join(pair_dir, MASK_SUFFIX)
+    mask_path = os.path.join(pair_dir, mask_name)
     mask = np.ascontiguousarray(util.read_gray(mask_path), dtype=np.uint8) if os.path.isfile(mask_path) else None
     if mask is not None and mask.shape != gt.shape:
         raise ValueError("%s is %s, %s is %s" % (mask_path, mask.shape, gt_path, gt.shape))
@@ -394,29 +397,52 @@ class ListReport(object):
     """What match.py --evaluate collects over a list: per-pair metrics by list index (set by the thread that writes the
     pair's files), the skipped pairs, and at the end the file with the pooled totals of the device accumulator."""
 
-    def __init__(self, evaluator):
+    def __init__(self, evaluator, right_evaluator=None):
         self.evaluator = evaluator
         self.extra = evaluator.describe() if hasattr(evaluator, "describe") else {}     # more keys in every file
         self.pairs = {}          # index -> (name, Metrics)
         self.skipped = {}        # index -> name
         self.sparsification = {} # index -> the pair's sparsification figures (match.py --confidence only)
+        # match.py --views both: a second evaluator, whose total pools the RIGHT maps against disp1GT.pfm; a pair's right
+        # view is scored where its left view is and it has that file, and listed as skipped for the right view otherwise
+        self.right_evaluator = right_evaluator
+        self.right = {}          # index -> dict(metrics=Metrics[, sparsification=figures])
+        self.right_skipped = {}  # index -> name
+
+    def _right_block(self, index):
+        """The "right" entry of a pair: the fields of the left block for the right map; none without --views both or
+        without right-view ground truth, so that the files keep their bytes."""
+        r = self.right.get(index)
+        if r is None:
+            return {}
+        block = r["metrics"].to_dict()
+        if r.get("sparsification") is not None:
+            block["sparsification"] = r["sparsification"]
+        return dict(right=block)
 
     def _pair_extra(self, index):
         """The keys a pair's entry gains with --confidence; none without it, so that the files keep their bytes."""
         return dict(sparsification=self.sparsification[index]) if index in self.sparsification else {}
 
-    def pair(self, index, name, metrics, path=None, sparsification=None):
+    def pair(self, index, name, metrics, path=None, sparsification=None, right=None):
         self.pairs[index] = (name, metrics)
+        if right is not None:
+            self.right[index] = right
+        else:
+            self.right.pop(index, None)
         if sparsification is not None:
             self.sparsification[index] = sparsification
         else:
             self.sparsification.pop(index, None)
         if path is not None:
             write_json(path, dict(metrics.to_dict(), pair=name, thresholds=list(metrics.thresholds), **self.extra,
-                                  **self._pair_extra(index)))
+                                  **self._pair_extra(index), **self._right_block(index)))
 
     def skip(self, index, name):
         self.skipped[index] = name
+
+    def skip_right(self, index, name):
+        self.right_skipped[index] = name
 
     def write(self, path):
         order = sorted(self.pairs)
@@ -424,8 +450,18 @@ class ListReport(object):
         mean = mean_of(metrics)
         if self.sparsification:
             mean["sparsification"] = mean_sparsification([self.sparsification[i] for i in order if i in self.sparsification])
+        right = {}
+        if self.right_evaluator is not None:
+            scored = [i for i in order if i in self.right]
+            right_mean = mean_of([self.right[i]["metrics"] for i in scored])
+            figures = [self.right[i]["sparsification"] for i in scored if self.right[i].get("sparsification") is not None]
+            if figures:
+                right_mean["sparsification"] = mean_sparsification(figures)
+            right = dict(right=dict(pooled=self.right_evaluator.report().to_dict(), mean=right_mean,
+                                    skipped=[self.right_skipped[i] for i in sorted(self.right_skipped)]))
         write_json(path, dict(thresholds=list(self.evaluator.thresholds),
-                              pairs=[dict(self.pairs[i][1].to_dict(), pair=self.pairs[i][0], index=i, **self._pair_extra(i))
+                              pairs=[dict(self.pairs[i][1].to_dict(), pair=self.pairs[i][0], index=i, **self._pair_extra(i),
+                                          **self._right_block(i))
                                      for i in order],
                               pooled=self.evaluator.report().to_dict(), mean=mean,
-                              skipped=[self.skipped[i] for i in sorted(self.skipped)], **self.extra))
+                              skipped=[self.skipped[i] for i in sorted(self.skipped)], **self.extra, **right))

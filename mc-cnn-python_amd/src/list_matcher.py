@@ -204,14 +204,15 @@ def pinned(a):
     return torch.from_numpy(np.ascontiguousarray(a)).pin_memory()
 
 
-def make_reader(paths, check_shape, to_host_buffer=pinned_u8, truth=None, shape=None):
+def make_reader(paths, check_shape, to_host_buffer=pinned_u8, truth=None, shape=None, truth_right=None):
     """read(index) for ListPipeline on top of match.py's file layout.  `paths(index)` -> dict(left, right, calib, out,
     out_time, out_img, res_dir, img_dir[, dirs: every directory the outputs need]); `check_shape(H, W, ndisp)` raises for
     a pair outside the envelope - before anything of that pair reaches the GPU.  `shape`: None - the size and ndisp are
     those of the pair's calib.txt, checked before anything is decoded - or shape(left_path, left_image) -> (H, W, ndisp)
     for a data set whose size is the decoded left image's (datasets.py: the KITTI layouts).  `truth(left_path)` (match.py
     --evaluate: the layout's load_truth) -> (ground truth, mask or None) or None: read here as well, into pinned memory
-    beside the images (job.gt, job.mask; job.gt None = a pair without ground truth)."""
+    beside the images (job.gt, job.mask; job.gt None = a pair without ground truth).  `truth_right` (--views both): the
+    same for the right view's ground truth (job.gt_right, job.mask_right)."""
     def read(index):
         p = paths(index)
         if shape is None:
@@ -239,8 +240,16 @@ def make_reader(paths, check_shape, to_host_buffer=pinned_u8, truth=None, shape=
                 raise ValueError("%s: the ground truth is %s, the disparity map %s (resampling is not supported)"
                                  % (p["left"], found[0].shape, (height, width)))
             gt, mask = pinned(found[0]), (pinned(found[1]) if found[1] is not None else None)
+        gt_right = mask_right = None
+        found = truth_right(p["left"]) if truth_right is not None else None
+        if found is not None:
+            if found[0].shape != (height, width):
+                raise ValueError("%s: the right view's ground truth is %s, the disparity map %s (resampling is not "
+                                 "supported)" % (p["left"], found[0].shape, (height, width)))
+            gt_right, mask_right = pinned(found[0]), (pinned(found[1]) if found[1] is not None else None)
         return Job(index, p["left"], (height, width, ndisp, channels), height=height, width=width, ndisp=ndisp,
-                   left=to_host_buffer(left), right=to_host_buffer(right), paths=p, gt=gt, mask=mask)
+                   left=to_host_buffer(left), right=to_host_buffer(right), paths=p, gt=gt, mask=mask, gt_right=gt_right,
+                   mask_right=mask_right)
     return read
 
 
@@ -254,7 +263,9 @@ def make_writer(rank=0, log=print, report=None, eval_file="evalMCCNN.json", save
     `report` (evaluation.ListReport) also the pair's evaluation, once its 192 bytes are on the host.  `save(result,
     paths)` writes the map and its preview (datasets.py: a KITTI layout's result is the 16-bit plane);
     with match.py --confidence the backend's result is the pair (map, planes) of one ticket - a repeated pair's files get
-    the repeated pair's planes - and `save_confidence(planes, paths)` writes the planes."""
+    the repeated pair's planes - and `save_confidence(planes, paths)` writes the planes.  With --views both the map is
+    [2,H,W] and the planes [2,K,H,W] (`save` / `save_confidence` know), and a right view that was scored (job.score_right)
+    joins the pair's evaluation as its "right" block."""
     from datetime import datetime
 
     def write(job, disparity, seconds):
@@ -270,8 +281,14 @@ def make_writer(rank=0, log=print, report=None, eval_file="evalMCCNN.json", save
         score = getattr(job, "score", None)       # of the map these files hold, or of the repeat that replaces it
         if report is not None and score is not None:
             auc = getattr(job, "auc", None)
+            extra = dict(sparsification=auc.figures()) if auc is not None else {}
+            score_right = getattr(job, "score_right", None)
+            if score_right is not None:
+                auc_right = getattr(job, "auc_right", None)
+                extra["right"] = dict(metrics=score_right.metrics(),
+                                      sparsification=auc_right.figures() if auc_right is not None else None)
             report.pair(job.index, job.name, score.metrics(), p.get("out_eval") or os.path.join(p["res_dir"], eval_file),
-                        **(dict(sparsification=auc.figures()) if auc is not None else {}))
+                        **extra)
     return write
 
 
@@ -281,13 +298,14 @@ class Ticket(object):
         # with --confidence: the planes in a second pinned buffer, copied behind the map, and where they are on the device
         self.host_planes, self.device_planes = host_planes, device_planes
         self.truth = None            # with --evaluate: the pair's (ground truth, mask) on the device
+        self.truth_right = None      # with --views both besides: the right view's, where the pair has one
 
 
 class MatcherBackend(object):
     """ListPipeline's backend on StereoMatchers: one matcher and one stream per slot, as match.py --pairs_in_flight."""
 
     def __init__(self, matchers, streams, make_library_matcher, rank=0, log=print, report=None, device_output=None,
-                 confidence=(), sparsifier=None):
+                 confidence=(), sparsifier=None, views="left"):
         import torch
         self.torch = torch
         self.matchers, self.streams = matchers, streams
@@ -309,6 +327,10 @@ class MatcherBackend(object):
         # (evaluation.Sparsifier) behind the pair's evaluation, outside the graph like it
         self.confidence = tuple(confidence)
         self.sparsifier = sparsifier
+        # match.py --views both: the matchers return [2,H,W] maps (and [2,K,H,W] planes), which cross to the host whole;
+        # index 0 is scored as before, index 1 by the report's right evaluator against the right view's ground truth
+        self.both = views == "both"
+        self.right_evaluator = report.right_evaluator if (report is not None and self.both) else None
 
     def _map_and_planes(self, result):
         return result if self.confidence else (result, None)
@@ -336,12 +358,19 @@ class MatcherBackend(object):
         done.record()
         return Ticket(host, done, scored, host_planes, planes)
 
-    def _score(self, slot, job, ticket, truth):
-        """The evaluation of ticket.device_map behind it on the current stream; the writer finds it as job.score."""
-        ticket.truth = truth
-        job.score = self.evaluator.score(ticket.device_map, truth[0], truth[1], slot)
+    def _score(self, slot, job, ticket, truth, truth_right=None):
+        """The evaluation of ticket.device_map behind it on the current stream; the writer finds it as job.score (and,
+        --views both with right-view ground truth, job.score_right)."""
+        ticket.truth, ticket.truth_right = truth, truth_right
+        maps, planes = ticket.device_map, ticket.device_planes
+        left, left_planes = (maps[0], planes[0] if planes is not None else None) if self.both else (maps, planes)
+        job.score = self.evaluator.score(left, truth[0], truth[1], slot)
         if self.sparsifier is not None:
-            job.auc = self.sparsifier.score(ticket.device_map, ticket.device_planes, truth[0])
+            job.auc = self.sparsifier.score(left, left_planes, truth[0])
+        if truth_right is not None:
+            job.score_right = self.right_evaluator.score(maps[1], truth_right[0], truth_right[1], slot)
+            if self.sparsifier is not None:
+                job.auc_right = self.sparsifier.score(maps[1], planes[1], truth_right[0])
 
     def submit(self, slot, job, mode):
         self.log("[{}] pair {}: {}  ({}x{}, ndisp {}, {} byte(s) per pixel, {})".format(
@@ -354,12 +383,20 @@ class MatcherBackend(object):
                 disparity, planes = self._map_and_planes(m.match_graph_u8(job.left, job.right, job.ndisp))
             ticket = self._to_host(disparity, planes)
             if self.evaluator is not None:
+                gt_right = getattr(job, "gt_right", None) if getattr(job, "gt", None) is not None else None
+                if self.both and gt_right is None:
+                    self.report.skip_right(job.index, job.name)
                 if getattr(job, "gt", None) is None:
                     self.report.skip(job.index, job.name)
                 else:
                     dev = m.device
+                    truth_right = None
+                    if self.both and gt_right is not None:
+                        truth_right = (gt_right.to(dev, non_blocking=True),
+                                       job.mask_right.to(dev, non_blocking=True) if job.mask_right is not None else None)
                     self._score(slot, job, ticket, (job.gt.to(dev, non_blocking=True),
-                                                    job.mask.to(dev, non_blocking=True) if job.mask is not None else None))
+                                                    job.mask.to(dev, non_blocking=True) if job.mask is not None else None),
+                                truth_right)
             return ticket
 
     def wait(self, ticket):
@@ -388,7 +425,7 @@ class MatcherBackend(object):
         self.torch.cuda.synchronize()
         if ticket.truth is not None:
             with self._stream(slot):     # the slot's result buffer and scratch belong to the slot's stream
-                self._score(slot, job, again, ticket.truth)      # the redone map, not the discarded one
+                self._score(slot, job, again, ticket.truth, ticket.truth_right)      # the redone map, not the discarded one
             self._commit(slot, again)
             self.torch.cuda.synchronize()    # the library matcher's output is overwritten by the next repeat
         return again
@@ -398,4 +435,7 @@ class MatcherBackend(object):
         a replayed graph's static output)."""
         if ticket.truth is not None:
             with self._stream(slot):
-                self.evaluator.commit(ticket.device_map, ticket.truth[0], ticket.truth[1])
+                self.evaluator.commit(ticket.device_map[0] if self.both else ticket.device_map, ticket.truth[0],
+                                      ticket.truth[1])
+                if ticket.truth_right is not None:
+                    self.right_evaluator.commit(ticket.device_map[1], ticket.truth_right[0], ticket.truth_right[1])

@@ -17,6 +17,9 @@ iteration), the fast variant of rounds 2-3, which the bit-exact aggregation has 
 hipGraph replay per pair where a shape repeats, a writer thread - the same files, byte for byte.
 --confidence msm,mmn,cur,lrc (any subset) writes the confidence planes of every map, conf0MCCNN_<measure>.pfm beside
 disp0MCCNN.pfm, in all three loops; with --evaluate their sparsification figures join evalMCCNN.json and eval.json.
+--views both writes the post-processed RIGHT disparity map as well: disp1MCCNN.pfm / .pgm beside the left files (and
+conf1MCCNN_<measure>.pfm with --confidence), in all three loops; with --evaluate it is scored against disp1GT.pfm (and
+mask1nocc.png) and every evaluation file gains a "right" block.  Middlebury layout only.
 Multi-GPU: launch one process per GPU with different -g / -s / -e, as the reference intends (match.py:17, 26-28),
 or use `torchrun --nproc-per-node N match.py ...`: rank r then takes the pairs i = r (mod N) of the window.
 """
@@ -155,6 +158,13 @@ parser.add_argument("--confidence", type=str, default=None,
 parser.add_argument("--eval_auc_threshold", type=str, default=None,
                     help="with --evaluate --confidence: the error that makes a pixel bad on the sparsification curve, in "
                          "pixels (default 1.0); with a KITTI --dataset abs[:rel] (default 3:0.05)")
+parser.add_argument("--views", choices=("left", "both"), default="left",
+                    help="'both': also the post-processed right disparity map (the left view's rules on the mirrored pair, "
+                         "include/mccnn.h), written as disp1MCCNN.pfm / disp1MCCNN.pgm beside the left files, with "
+                         "--confidence conf1MCCNN_<measure>.pfm; with --evaluate it is scored against disp1GT.pfm (and "
+                         "mask1nocc.png) beside im0.png: a \"right\" block in evalMCCNN.json and eval.json, a pair without "
+                         "disp1GT.pfm listed as skipped for the right view.  timeMCCNN.txt stays the whole pair's time.  "
+                         "Not with a KITTI --dataset.  Without it every file keeps its bytes")
 
 CONFIDENCE_MEASURES = ("msm", "mmn", "cur", "lrc")      # stereo_device.CONFIDENCE_MEASURES (not imported before the GPU is pinned)
 
@@ -173,7 +183,7 @@ def parse_confidence(text):
 left_image_suffix = datasets.Middlebury.left_suffix
 left_gt_suffix = datasets.Middlebury.gt_suffix
 right_image_suffix = datasets.Middlebury.right_suffix
-right_gt_suffix = "disp1GT.pfm"
+right_gt_suffix = datasets.Middlebury.right_gt_suffix
 calib_suffix = datasets.Middlebury.calib_suffix
 
 out_file = datasets.Middlebury.out_file
@@ -215,6 +225,10 @@ def main(argv=None):
         parser.error("--eval_auc_threshold: %s" % e)
     if args.eval_interpolate and not layout.kitti:
         parser.error("--eval_interpolate goes with a KITTI --dataset")
+    both = args.views == "both"
+    if both and layout.kitti:
+        parser.error("--views both is not available with --dataset %s: the KITTI development kit has neither right-view "
+                     "ground truth nor a submission slot for a right map" % args.dataset)
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -266,27 +280,43 @@ def main(argv=None):
                         interpolation_directions=16 if args.paper_interpolation else 4,
                         occlusion_from_left=args.paper_interpolation, numpy1_promotion=args.numpy1_promotion,
                         sgm_independent_directions=args.paper_sgm),
-            confidence=conf_names)
+            confidence=conf_names, views=args.views)
 
     def map_and_planes(result):
         """What a matcher returns, as (map, planes or None)."""
         return result if conf_names else (result, None)
 
     def save_confidence(planes, out):
-        """One PFM per measure from the host planes [K,H,W] (layout.confidence_path names the file)."""
-        for k, name in enumerate(conf_names):
-            path = layout.confidence_path(out, name)
-            util.recurMk(os.path.abspath(os.path.dirname(path)))
-            util.writePfm(planes[k], path)
+        """One PFM per measure from the host planes [K,H,W] (layout.confidence_path names the file); --views both:
+        [2,K,H,W], the right view's as conf1MCCNN_<measure>.pfm."""
+        for view, view_planes in enumerate(planes if both else (planes,)):
+            for k, name in enumerate(conf_names):
+                path = layout.confidence_path(out, name, view) if both else layout.confidence_path(out, name)
+                util.recurMk(os.path.abspath(os.path.dirname(path)))
+                util.writePfm(view_planes[k], path)
+
+    def save_maps(result, out):
+        """The map's files from what crossed to the host; --views both: [2,H,W], the right map as disp1MCCNN.*."""
+        if not both:
+            return layout.save(result, out)
+        layout.save(result[0], out)
+        layout.save_right(result[1], out)
+
+    def left_of(t):
+        """The left view's part of a matcher's map or planes (None stays None)."""
+        return t[0] if (both and t is not None) else t
 
     matchers = [make_matcher("miopen" if args.features == "library" else "auto") for _ in range(in_flight)]
     footprint_kw = dict(pairs_in_flight=in_flight, arch=args.arch,
-                        fc_units=net.num_fc_units if accurate else sd.DECISION_UNITS, confidence=len(conf_names))
+                        fc_units=net.num_fc_units if accurate else sd.DECISION_UNITS, confidence=len(conf_names),
+                        views=args.views)
     streams = [torch.cuda.Stream() for _ in range(in_flight)] if in_flight > 1 else [None]
     # --evaluate: one result buffer and scratch per slot, the list's running total on the device (src/evaluation.py)
-    report = ev.ListReport(layout.evaluator(eval_thresholds, slots=in_flight,
-                                            interpolate=args.eval_interpolate)) if args.evaluate else None
+    # (--views both: a second evaluator of the same kind, whose total pools the right maps against disp1GT.pfm)
+    report = ev.ListReport(layout.evaluator(eval_thresholds, slots=in_flight, interpolate=args.eval_interpolate),
+                           layout.evaluator(eval_thresholds, slots=in_flight) if both else None) if args.evaluate else None
     evaluator = report.evaluator if report is not None else None
+    evaluator_right = report.right_evaluator if report is not None else None
     # --evaluate --confidence: the sparsification figures of every scored pair, behind its evaluation on its stream
     sparsifier = ev.Sparsifier(conf_names, auc_threshold) if (report is not None and conf_names) else None
     eval_path = os.path.join(result_root, "eval.json" if world == 1 else "eval_rank{}.json".format(rank))
@@ -304,12 +334,13 @@ def main(argv=None):
 
         backend = lm.MatcherBackend(matchers, streams, lambda: make_matcher("miopen", "library"), rank=rank,
                                     report=report, device_output=layout.device_output if layout.kitti else None,
-                                    confidence=conf_names, sparsifier=sparsifier)
+                                    confidence=conf_names, sparsifier=sparsifier, views=args.views)
         # a KITTI frame's size is its decoded left image's: the capture policy sees every change through the job's key
         reader = lm.make_reader(paths, check_shape, truth=layout.load_truth if args.evaluate else None,
-                                shape=(lambda left, image: layout.shape(left, ndisp_flag, image)) if layout.kitti else None)
+                                shape=(lambda left, image: layout.shape(left, ndisp_flag, image)) if layout.kitti else None,
+                                truth_right=layout.load_truth_right if (args.evaluate and both) else None)
         pipeline = lm.ListPipeline(reader, backend,
-                                   lm.make_writer(rank, report=report, eval_file=out_eval_file, save=layout.save,
+                                   lm.make_writer(rank, report=report, eval_file=out_eval_file, save=save_maps,
                                                   save_confidence=save_confidence if conf_names else None),
                                    slots=in_flight, readers=args.readers)
         try:
@@ -327,7 +358,7 @@ def main(argv=None):
     redo = {"left": 0, "matcher": None}
 
     def finish(entry):
-        disparity, planes, crossing, kept, done, stTime, out, images, scored = entry
+        disparity, planes, crossing, kept, done, stTime, out, images, scored, scored_right = entry
         out_path, out_time_path = out["out"], out["out_time"]
         done.synchronize()
         redone = False
@@ -350,23 +381,35 @@ def main(argv=None):
             index, name, score, auc, gt, mask, slot, json_path = scored
             with torch.cuda.stream(streams[slot]) if in_flight > 1 else contextlib.nullcontext():
                 if redone:
-                    score = evaluator.score(kept, gt, mask, slot)
+                    score = evaluator.score(left_of(kept), gt, mask, slot)
                     if sparsifier is not None:
-                        auc = sparsifier.score(kept, planes, gt)
-                evaluator.commit(kept, gt, mask)
+                        auc = sparsifier.score(left_of(kept), left_of(planes), gt)
+                evaluator.commit(left_of(kept), gt, mask)
+                if scored_right is not None:
+                    score_r, auc_r, gt_r, mask_r = scored_right
+                    if redone:
+                        score_r = evaluator_right.score(kept[1], gt_r, mask_r, slot)
+                        if sparsifier is not None:
+                            auc_r = sparsifier.score(kept[1], planes[1], gt_r)
+                        scored_right = (score_r, auc_r, gt_r, mask_r)
+                    evaluator_right.commit(kept[1], gt_r, mask_r)
             if redone:
                 torch.cuda.synchronize()     # the library matcher's output is overwritten by the next repeat
         left_disparity_map = crossing.cpu().numpy()     # the float32 map, or a KITTI layout's 16-bit plane
         host_planes = planes.cpu().numpy() if planes is not None else None
         endTime = time.time()
-        layout.save(left_disparity_map, out)
+        save_maps(left_disparity_map, out)
         if host_planes is not None:
             save_confidence(host_planes, out)
         util.saveTimeFile(endTime - stTime, out_time_path)
         print("[{}] {}: {:.3f} s -> {}".format(rank, datetime.now(), endTime - stTime, out_path))
         if scored is not None:
+            right = None
+            if scored_right is not None:
+                right = dict(metrics=scored_right[0].metrics(),
+                             sparsification=scored_right[1].figures() if scored_right[1] is not None else None)
             report.pair(index, name, score.metrics(), json_path,
-                        sparsification=auc.figures() if auc is not None else None)
+                        sparsification=auc.figures() if auc is not None else None, right=right)
 
     for index in shard_indices(args.start, args.end, len(left_paths), rank, world):
         left_path = left_paths[index]
@@ -393,6 +436,12 @@ def main(argv=None):
             ev.check_shape(truth[0], (height, width), left_path)
         elif args.evaluate:
             report.skip(index, left_path)
+        # --views both: the right view is scored where the left one is and disp1GT.pfm exists
+        truth_right = layout.load_truth_right(left_path) if (both and truth is not None) else None
+        if truth_right is not None:
+            ev.check_shape(truth_right[0], (height, width), left_path)
+        elif both and args.evaluate:
+            report.skip_right(index, left_path)
 
         # decode + standardise (match.py:118-125): population std, no /255
         views = []
@@ -419,19 +468,24 @@ def main(argv=None):
             dev_l = torch.from_numpy(left_image).cuda()
             dev_r = torch.from_numpy(right_image).cuda()
             disparity, planes = map_and_planes(matchers[slot].match(dev_l, dev_r, ndisp))
-            scored = None
+            scored = scored_right = None
             # what crosses to the host and what is scored: the map, or a KITTI layout's 16-bit code and what it holds,
             # behind the map on this stream
             crossing, kept = layout.device_output(disparity, truth is not None)
             if truth is not None:        # behind the map, on the pair's stream
                 gt = torch.from_numpy(truth[0]).cuda()
                 mask = torch.from_numpy(truth[1]).cuda() if truth[1] is not None else None
-                scored = (index, left_path, evaluator.score(kept, gt, mask, slot),
-                          sparsifier.score(kept, planes, gt) if sparsifier is not None else None, gt, mask, slot,
-                          out["out_eval"])
+                scored = (index, left_path, evaluator.score(left_of(kept), gt, mask, slot),
+                          sparsifier.score(left_of(kept), left_of(planes), gt) if sparsifier is not None else None, gt,
+                          mask, slot, out["out_eval"])
+            if truth_right is not None:
+                gt_r = torch.from_numpy(truth_right[0]).cuda()
+                mask_r = torch.from_numpy(truth_right[1]).cuda() if truth_right[1] is not None else None
+                scored_right = (evaluator_right.score(kept[1], gt_r, mask_r, slot),
+                                sparsifier.score(kept[1], planes[1], gt_r) if sparsifier is not None else None, gt_r, mask_r)
             done = torch.cuda.Event()
             done.record()
-        pending.append((disparity, planes, crossing, kept, done, stTime, out, (dev_l, dev_r, ndisp), scored))
+        pending.append((disparity, planes, crossing, kept, done, stTime, out, (dev_l, dev_r, ndisp), scored, scored_right))
         if in_flight == 1:
             finish(pending.pop(0))
     while pending:

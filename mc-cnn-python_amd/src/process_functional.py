@@ -56,7 +56,7 @@ _CBCA_ORDERS = {"separable": hip.MCCNN_CBCA_SEPARABLE, "reference": hip.MCCNN_CB
 
 __all__ = ["compute_features", "compute_cost_volume", "compute_cost_volume_accurate", "cost_volume_aggregation", "SGM_average",
            "disparity_prediction", "interpolation", "subpixel_enhance", "median_filter", "bilateral_filter",
-           "semi_global_matching", "compute_cross_region", "confidence_measures"]
+           "semi_global_matching", "compute_cross_region", "confidence_measures", "interpolation_right"]
 
 
 def _dev(x, dtype=torch.float32):
@@ -291,6 +291,19 @@ def interpolation(left_disparity_map, right_disparity_map, ndisp):
                 was_np)
 
 
+def interpolation_right(right_disparity_map, left_disparity_map, ndisp):
+    """Not in the reference: interpolation() for the RIGHT map - what it gives on the horizontally flipped pair, flipped
+    back (include/mccnn.h: mccnn_lr_status_right, mccnn_interpolate_right).  Occlusions are filled from the left, and
+    with OCCLUSION_FROM_LEFT (mirrored) from the right; INTERPOLATION_DIRECTIONS = 16 walks the mirrored rays.  The
+    later stages are view-agnostic: subpixel_enhance, median_filter and bilateral_filter take the right view's map,
+    volume and image as they are."""
+    dr, was_np = _dev(right_disparity_map)
+    dl, _ = _dev(left_disparity_map)
+    st = sd.lr_status_right(dr, dl, int(ndisp))
+    return _ret(sd.interpolate_right(dr, st, directions=INTERPOLATION_DIRECTIONS,
+                                     occlusion_from_right=OCCLUSION_FROM_LEFT), was_np)
+
+
 def subpixel_enhance(left_disparity_map, left_cost_volume):
     """pf:381-400."""
     dl, was_np = _dev(left_disparity_map)
@@ -314,12 +327,16 @@ def bilateral_filter(left_image, left_disparity_map, filter_height, filter_width
 CONFIDENCE_MEASURES = sd.CONFIDENCE_MEASURES
 
 
-def confidence_measures(left_cost_volume, right_disparity_map=None, measures=CONFIDENCE_MEASURES):
+def confidence_measures(left_cost_volume, right_disparity_map=None, measures=CONFIDENCE_MEASURES, view="left"):
     """Not in the reference: how far each pixel of the left winner-take-all map can be trusted (include/mccnn.h has the
     definitions; larger is more confident).  left_cost_volume: the final left volume [D,H,W] that disparity_prediction
-    reads; right_disparity_map: its right map, needed by "lrc" alone.  Returns {measure: [H,W] float32 map}."""
+    reads; right_disparity_map: its right map, needed by "lrc" alone.  Returns {measure: [H,W] float32 map}.
+    view="right": the measures of the RIGHT map - the first argument is then the final right volume and the second the
+    LEFT winner-take-all map ("lrc" looks it up at column w + d1)."""
+    if view not in ("left", "right"):
+        raise ValueError("view must be 'left' or 'right'")
     v, was_np = _dev(left_cost_volume)
     dr = None if right_disparity_map is None else _dev(right_disparity_map)[0]
     names = sd.confidence_names(measures)
-    planes = sd.confidence(v, dr, names)
+    planes = (sd.confidence if view == "left" else sd.confidence_right)(v, dr, names)
     return dict((n, _ret(planes[i].clone(), was_np)) for i, n in enumerate(names))

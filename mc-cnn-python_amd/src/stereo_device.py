@@ -1121,9 +1121,9 @@ def _confidence(entry, vol, D, H, W, disp_right, measures, out):
     mask = confidence_mask(measures)
     k = bin(mask).count("1")
     if mask & hip.MCCNN_CONF_LRC and disp_right is None:
-        raise ValueError("%s: the lrc measure needs the right disparity map" % entry)
+        raise ValueError("%s: the lrc measure needs the other view's disparity map" % entry)
     if disp_right is not None and (tuple(disp_right.shape) != (H, W) or disp_right.dtype != torch.float32):
-        raise ValueError("%s: disp_right must be a float32 [H,W] map" % entry)
+        raise ValueError("%s: the other view's disparity must be a float32 [H,W] map" % entry)
     if vol.dtype != torch.float32:
         raise ValueError("%s: the volume must be float32" % entry)
     if out is None:
@@ -1149,12 +1149,46 @@ def confidence(vol_dhw, disp_right=None, measures=CONFIDENCE_MEASURES, out=None)
     return _confidence("mccnn_confidence", vol_dhw, D, H, W, disp_right, measures, out)
 
 
+def confidence_right_hwd(vol_right_hwd, D, disp_left=None, measures=CONFIDENCE_MEASURES, out=None):
+    """confidence_hwd() for the RIGHT view: planes [K,H,W] of a pixel-major right volume; disp_left: the left
+    winner-take-all map ("lrc" only, looked up at column w + d1)."""
+    H, W, Dp = vol_right_hwd.shape
+    assert Dp == hwd_pitch(D)
+    return _confidence("mccnn_confidence_right_hwd", vol_right_hwd, D, H, W, disp_left, measures, out)
+
+
+def confidence_right(vol_right_dhw, disp_left=None, measures=CONFIDENCE_MEASURES, out=None):
+    """confidence_right_hwd() on a plane-major volume [D,H,W]: the same bits."""
+    D, H, W = vol_right_dhw.shape
+    return _confidence("mccnn_confidence_right", vol_right_dhw, D, H, W, disp_left, measures, out)
+
+
 def lr_status(dl, dr, ndisp, out=None):
     H, W = dl.shape
     st = out if out is not None else torch.empty((H, W), dtype=torch.int32, device=dl.device)
     hip.check(hip.load().mccnn_lr_status(hip.ptr(dl), hip.ptr(dr), H, W, int(ndisp), hip.ptr(st), hip.stream()),
               "mccnn_lr_status")
     return st
+
+
+def lr_status_right(dr, dl, ndisp, out=None):
+    """lr_status() for the RIGHT view (mccnn_lr_status_right): the status of the right map `dr` against the left `dl`."""
+    H, W = dr.shape
+    st = out if out is not None else torch.empty((H, W), dtype=torch.int32, device=dr.device)
+    hip.check(hip.load().mccnn_lr_status_right(hip.ptr(dr), hip.ptr(dl), H, W, int(ndisp), hip.ptr(st), hip.stream()),
+              "mccnn_lr_status_right")
+    return st
+
+
+def interpolate_right(dr, status, out=None, directions=4, occlusion_from_right=False):
+    """interpolate() for the RIGHT view (mccnn_interpolate_right): occlusions from the left, or - occlusion_from_right,
+    the mirror of the occlusion_from_left extra - from the right; directions = 16: the mirrored ray set."""
+    H, W = dr.shape
+    out = out if out is not None else torch.empty_like(dr)
+    hip.check(hip.load().mccnn_interpolate_right(hip.ptr(dr), hip.ptr(status), H, W, int(directions),
+                                                 1 if occlusion_from_right else 0, hip.ptr(out), hip.stream()),
+              "mccnn_interpolate_right")
+    return out
 
 
 def interpolate(dl, status, out=None, directions=4, occlusion_from_left=False):
@@ -1240,6 +1274,9 @@ COST_VOLUME_HWD_MAX_D = 1024   # mccnn_cost_volume_hwd (larger D: the plane-majo
 DECISION_AUTO = "kernel"
 
 
+VIEWS = ("left", "both")       # StereoMatcher(views=...): the left map alone, or [2,H,W] = left, right
+
+
 def check_envelope(H, W, D):
     """Raises ValueError for a pair shape the kernels do not serve: 2 <= D <= SGM_MAX_D and D <= W - 2 (the reference's
     border rule).  Volumes of any size within device memory are served (SGM rebases past 4 GiB)."""
@@ -1253,7 +1290,7 @@ def check_envelope(H, W, D):
 
 
 def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flight=1, arch="fast",
-                    fc_units=DECISION_UNITS, confidence=0):
+                    fc_units=DECISION_UNITS, confidence=0, views="left"):
     """Device bytes StereoMatcher.workspace(H, W, D) allocates, times `pairs_in_flight` (match.py --pairs_in_flight:
     one matcher per pair in flight): four volumes of H*W*Dp*4 bytes (Dp = hwd_pitch(D)), the SGM scratch and the flag
     planes of the four directions, both support planes, the status and map planes, and - on pixel-major volumes with
@@ -1261,8 +1298,12 @@ def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flig
     the feature maps (2 x H*W*64*4 bytes while the cost volume is built) and the conv activations.
     arch="accurate": plus the two [H,W,fc_units] float32 halves of the first fully-connected layer.
     confidence: the number K of confidence planes the matcher was asked for (StereoMatcher(confidence=...)): plus one
-    [K,H,W] float32 buffer; 0 (default): none."""
+    [K,H,W] float32 buffer; 0 (default): none.
+    views="both" (StereoMatcher(views="both")): plus the right view's status plane, its three intermediate maps, the
+    [2,H,W] result and a second set of confidence planes."""
     check_envelope(H, W, D)
+    if views not in VIEWS:
+        raise ValueError("views must be 'left' or 'both'")
     lib = hip.load()
     H, W, D = int(H), int(W), int(D)
     dp = (D + 3) & ~3
@@ -1277,6 +1318,8 @@ def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flig
     if arch == "accurate":
         n += 2 * H * W * int(fc_units) * 4
     n += int(confidence) * H * W * 4
+    if views == "both":
+        n += (1 + 3 + 2 + int(confidence)) * H * W * 4
     return n * max(1, int(pairs_in_flight))
 
 
@@ -1310,7 +1353,7 @@ class StereoMatcher(object):
     def __init__(self, net, hp=None, cv_mode=hip.MCCNN_CV_EXACT, cbca_order=hip.MCCNN_CBCA_REFERENCE_ORDER,
                  feature_tile_rows=None, extras=None, features="auto", layout="auto", cbca_kernel="auto",
                  on_saturation="fallback", skip_unit_regions=True, two_chains=True, free_chains=True, refresh_first=True,
-                 sgm_flags_once=True, decision="auto", confidence=()):
+                 sgm_flags_once=True, decision="auto", confidence=(), views="left"):
         self.device = hip.require_device()
         self.net = net
         self.hp = dict(DEFAULT_HP)
@@ -1389,6 +1432,14 @@ class StereoMatcher(object):
         # more launch per pair behind the post-processing, and every match entry returns (map, planes [K,H,W]).
         # Empty (default): nothing changes - no launch, no buffer, the map alone is returned.
         self.confidence = confidence_names(confidence) if confidence else ()
+        # "both": every match entry returns [2,H,W] = the left map (the same bits) and the post-processed RIGHT map
+        # (include/mccnn.h: the left rules on the flipped pair, flipped back); confidence planes become [2,K,H,W].  The
+        # WTA-carrying launch then stores the right result volume and the right view's a8 .. a11 run beside the left's.
+        # "left" (default): nothing changes - the same launches, workspace and graphs.
+        if views not in VIEWS:
+            raise ValueError("views must be 'left' or 'both'")
+        self.views = views
+        self.both = views == "both"
         self._ws = {}
         self._graphs = {}
         self._side = None
@@ -1427,7 +1478,7 @@ class StereoMatcher(object):
             need = workspace_bytes(H, W, D, self.pixel_major(), self.workspace_cbca_kernel(H, W, D),
                                    arch="accurate" if self.accurate else "fast",
                                    fc_units=self.net.num_fc_units if self.accurate else DECISION_UNITS,
-                                   confidence=len(self.confidence))
+                                   confidence=len(self.confidence), views=self.views)
             self._ws, self._graphs = {}, {}          # one shape resident at a time: the previous one goes first
             _require_device_memory(need, "StereoMatcher: the workspace of a %dx%d pair with ndisp=%d" % (W, H, D))
             dp = hwd_pitch(D)
@@ -1445,7 +1496,12 @@ class StereoMatcher(object):
                 ws["halves"] = tuple(torch.empty((H, W, self.net.num_fc_units), dtype=torch.float32, device=dev)
                                      for _ in range(2))
             if self.confidence:
-                ws["confidence"] = torch.empty((len(self.confidence), H, W), dtype=torch.float32, device=dev)
+                ws["confidence"] = torch.empty(((2,) if self.both else ()) + (len(self.confidence), H, W),
+                                               dtype=torch.float32, device=dev)
+            if self.both:
+                ws["status_right"] = torch.empty((H, W), dtype=torch.int32, device=dev)
+                ws["maps_right"] = torch.empty((3, H, W), dtype=torch.float32, device=dev)   # interp, subpixel, median
+                ws["both"] = torch.empty((2, H, W), dtype=torch.float32, device=dev)         # the result: left, right
             ws["progs"] = None
             # (distances above CBCA_HWD_MAX_DISTANCE: the aggregation programs do not encode such arms - the joined
             # two-volume path of mccnn_cbca_iter_hwd_long_pair runs, as for shapes the programs do not encode)
@@ -1493,7 +1549,7 @@ class StereoMatcher(object):
             self._library_twin = StereoMatcher(self.net, hp=self.hp, cv_mode=self.cv_mode, cbca_order=self.cbca_order,
                                                extras=self.extras, features="miopen", layout=self.layout,
                                                cbca_kernel=self.cbca_kernel, on_saturation="ignore", decision="library",
-                                               confidence=self.confidence)
+                                               confidence=self.confidence, views=self.views)
         if keep is not None:
             keep.clear()
         return self._library_twin.match(left_image, right_image, ndisp, out=out, keep=keep, confidence_out=confidence_out)
@@ -1599,7 +1655,8 @@ class StereoMatcher(object):
         """Pixel-major volumes, free-running chains (default): each volume's aggregation -> SGM -> aggregation is ONE
         chain of one-volume launches on its own stream - the left on the current stream, the right on the matcher's right
         stream; the two chains meet again only in front of the WTA-carrying last launch.  left / right: (volume, spare
-        buffer); returns (dl, dr, left_volume)."""
+        buffer); returns (dl, dr, left_volume, right_volume) - the right volume holds the result only where somebody
+        reads it (views="both")."""
         hp, progs, dist = self.hp, ws["progs"], self.hp["cbca_distance"]
         n1, n2 = int(hp["cbca_num_iterations1"]), int(hp["cbca_num_iterations2"])
         if flag_planes is None and self.sgm_flags_once:      # (per-stage timing: nothing ran beside the cost volume)
@@ -1638,10 +1695,11 @@ class StereoMatcher(object):
         main_s.wait_stream(right_s)
         (lh, lt), (rh, rt) = ends
         if not fuse:
-            return self._wta_hwd(lh, rh, D, m, timer) + (lh,)
-        # (the right result volume, which nothing else reads, stays unwritten)
-        _prog_launch_wta((lh, lt, sups[0], progs[0]), (rh, rt, sups[1], progs[1]), D, dist, (m[0], m[1]), False, timer)
-        return m[0], m[1], lt
+            return self._wta_hwd(lh, rh, D, m, timer) + (lh, rh)
+        # (the right result volume stays unwritten unless the right view's post-processing reads it)
+        _prog_launch_wta((lh, lt, sups[0], progs[0]), (rh, rt, sups[1], progs[1]), D, dist, (m[0], m[1]), self.both,
+                         timer)
+        return m[0], m[1], lt, rt
 
     def _aggregate_hwd(self, progs, left, right, sups, D, n, timer, **kw):
         """One aggregation of both pixel-major volumes, joined to the current stream when it returns: the program-driven
@@ -1677,11 +1735,12 @@ class StereoMatcher(object):
         # (with the WTA in the last launch the right result volume, which nothing else reads, stays unwritten)
         timer.span_start("aggregation_2")
         (lh, lt), (rh, rt) = self._aggregate_hwd(progs, (lh, lt), (rh, rt), sups, D, hp["cbca_num_iterations2"], timer,
-                                                 wta_out=(m[0], m[1]) if fuse else None, store_right=keep is not None)
+                                                 wta_out=(m[0], m[1]) if fuse else None,
+                                                 store_right=keep is not None or self.both)
         timer.span_stop("aggregation_2")
         if keep is not None:
             keep["cbca2"] = (hwd_to_dhw(lh, D), hwd_to_dhw(rh, D))
-        return ((m[0], m[1]) if fuse else self._wta_hwd(lh, rh, D, m, timer)) + (lh,)
+        return ((m[0], m[1]) if fuse else self._wta_hwd(lh, rh, D, m, timer)) + (lh, rh)
 
     def _aggregate_dhw(self, left, right, sups, n, timer):
         """One aggregation of both plane-major volumes: the separable kernel takes both views in one launch; the other
@@ -1737,7 +1796,7 @@ class StereoMatcher(object):
         timer.start("wta")
         dl, dr = wta(lcv, out=m[0]), wta(rcv, out=m[1])
         timer.stop()
-        return dl, dr, lcv
+        return dl, dr, lcv, rcv
 
     def _confidence(self, ws, D, dr, left_volume, pixel_major, timer, keep, out, static_out):
         """The confidence planes of the pair, from the left result volume and the right WTA map: one launch on the
@@ -1781,6 +1840,81 @@ class StereoMatcher(object):
         # the workspace map is overwritten by the next pair: hand out a copy unless the caller passed its own tensor
         # or (match_graph) wants the static buffer
         return db if (static_out or out is not None) else db.clone()
+
+    def _post_right(self, ws, R, D, dl, dr, right_volume, pixel_major, timer, keep, out, confidence_out):
+        """views="both": a8 .. a11 and the confidence planes of the RIGHT view, on the WTA maps, the right result volume
+        and the right image - the mirrored check and interpolation, then the view-agnostic kernels on the right view's
+        operands.  Writes the map into `out` [H,W] and the planes into `confidence_out` [K,H,W].  Without per-stage
+        timing the launches go to the matcher's right stream, forked from the current one here, so that they run beside
+        the left view's; returns that stream, which the caller joins - None under per-stage timing, where everything
+        stays on the current stream.  Nothing is allocated (but under `keep`) and nothing blocks."""
+        hp, ex = self.hp, self.extras
+        main_s = torch.cuda.current_stream()
+        fork = timer is _NO_TIMER
+        st = self._right_stream() if fork else main_s
+        if fork:
+            st.wait_stream(main_s)
+        mr = ws["maps_right"] if keep is None else torch.empty_like(ws["maps_right"])
+        with torch.cuda.stream(st):
+            timer.start("post_right")
+            status = lr_status_right(dr, dl, D, out=ws["status_right"] if keep is None else None)
+            di = interpolate_right(dr, status, out=mr[0], directions=ex["interpolation_directions"],
+                                   occlusion_from_right=ex["occlusion_from_left"])
+            if pixel_major:
+                ds = subpixel_hwd(di, right_volume, D, out=mr[1], numpy1_promotion=ex["numpy1_promotion"])
+            else:
+                ds = subpixel(di, right_volume, out=mr[1], numpy1_promotion=ex["numpy1_promotion"])
+            dm = median(ds, 5, 5, out=mr[2])
+            db = bilateral(R, dm, 5, 5, 0, hp["blur_sigma"], hp["blur_threshold"], out=out)
+            timer.stop()
+            planes = None
+            if self.confidence:
+                timer.start("confidence_right")
+                if pixel_major:
+                    planes = confidence_right_hwd(right_volume, D, dl, self.confidence, out=confidence_out)
+                else:
+                    planes = confidence_right(right_volume, dl, self.confidence, out=confidence_out)
+                timer.stop()
+        if keep is not None:
+            keep.update(status_right=status, interp_right=di, subpixel_right=ds, median_right=dm, bilateral_right=db,
+                        cbca2_right=hwd_to_dhw(right_volume, D) if pixel_major else right_volume.clone())
+            if planes is not None:
+                keep["confidence_right"] = planes
+        return st if fork else None
+
+    def _match_both(self, ws, L, R, D, dl, dr, volumes, m, timer, keep, out, confidence_out, static_out):
+        """views="both": the two views' post-processing into one [2,H,W] tensor (and [2,K,H,W] planes) - the workspace's,
+        the caller's `out` / `confidence_out`, or under `keep` fresh ones; handed out by _post's rules."""
+        H, W = L.shape
+        k = len(self.confidence)
+        if out is not None and (tuple(out.shape) != (2, H, W) or out.dtype != torch.float32 or not out.is_contiguous()
+                                or out.device != L.device):
+            raise ValueError("match: with views='both' `out` must be a contiguous float32 [2,H,W] tensor on the images' "
+                             "device")
+        if confidence_out is not None and (tuple(confidence_out.shape) != (2, k, H, W) or confidence_out.dtype != torch.float32
+                                           or not confidence_out.is_contiguous() or confidence_out.device != L.device):
+            raise ValueError("match: with views='both' `confidence_out` must be a contiguous float32 [2,K,H,W] tensor on "
+                             "the images' device")
+        pair = out if out is not None else (ws["both"] if keep is None else torch.empty_like(ws["both"]))
+        planes = None
+        if k:
+            planes = confidence_out if confidence_out is not None else (
+                ws["confidence"] if keep is None else torch.empty_like(ws["confidence"]))
+        pm = self.pixel_major()
+        # (the right view first: its launches are queued on the right stream and run beside the left view's, which
+        # follow on the current one; the two join in front of nothing but the hand-out)
+        main_s = torch.cuda.current_stream()
+        right_s = self._post_right(ws, R, D, dl, dr, volumes[1], pm, timer, keep, pair[1], planes[1] if k else None)
+        self._post(ws, L, D, dl, dr, volumes[0], pm, m, timer, keep, pair[0], True)
+        if k:
+            self._confidence(ws, D, dr, volumes[0], pm, timer, keep, planes[0], True)
+        if right_s is not None:
+            main_s.wait_stream(right_s)
+        handed = static_out or keep is not None
+        res = pair if (handed or out is not None) else pair.clone()
+        if not k:
+            return res
+        return res, (planes if (handed or confidence_out is not None) else planes.clone())
 
     def _match(self, left_image, right_image, ndisp, timer=_NO_TIMER, keep=None, _static_out=False, out=None,
                confidence_out=None):
@@ -1835,13 +1969,17 @@ class StereoMatcher(object):
             fuse = (int(self.hp["cbca_num_iterations2"]) >= 1 and D <= cbca_hwd_wta_max_d()
                     and int(self.hp["cbca_distance"]) <= CBCA_HWD_MAX_DISTANCE)
             if free:
-                dl, dr, left_volume = self._pixel_major_free(ws, L, R, D, (lv, hwd[0]), (rv, hwd[1]), sups, flag_planes,
-                                                             fuse, m, timer)
+                dl, dr, left_volume, right_volume = self._pixel_major_free(ws, L, R, D, (lv, hwd[0]), (rv, hwd[1]), sups,
+                                                                           flag_planes, fuse, m, timer)
             else:
-                dl, dr, left_volume = self._pixel_major_joined(ws, L, R, D, (lv, hwd[0]), (rv, hwd[1]), sups, fuse, m,
-                                                               timer, keep)
+                dl, dr, left_volume, right_volume = self._pixel_major_joined(ws, L, R, D, (lv, hwd[0]), (rv, hwd[1]), sups,
+                                                                             fuse, m, timer, keep)
         else:
-            dl, dr, left_volume = self._plane_major(ws, L, R, D, (lv, dhw[2]), (rv, dhw[3]), hwd, sups, m, timer, keep)
+            dl, dr, left_volume, right_volume = self._plane_major(ws, L, R, D, (lv, dhw[2]), (rv, dhw[3]), hwd, sups, m,
+                                                                  timer, keep)
+        if self.both:
+            return self._match_both(ws, L, R, D, dl, dr, (left_volume, right_volume), m, timer, keep, out,
+                                    confidence_out, _static_out)
         res = self._post(ws, L, D, dl, dr, left_volume, self.pixel_major(), m, timer, keep, out, _static_out)
         if not self.confidence:
             return res
