@@ -85,6 +85,16 @@ int mccnn_cost_volume_hwd(const float *fl, const float *fr, int H, int W, int C,
  * packed: their weights as mccnn_decision_pack laid them out for the same n_fc and mode with weight_scale (a power of
  *   two that brings max |w| near 1024); weights: [n_fc-1][units out][units in] float32; biases: [n_fc-1][units];
  *   w_final [units], b_final: the last layer.  mccnn_decision_pack_bytes: size of `packed` (0: outside the envelope).
+ *   weight_scale must be positive and FINITE (MCCNN_E_INVALID otherwise, nothing launched, in all three entry points),
+ *   and weight_scale * 256 and its reciprocal must be normal float32 numbers: weight_scale in [2^-126, 2^118].
+ *   Dynamic range of a caller's own packing: ONE scale serves every layer.  A split operand is w * scale = hi + lo in
+ *   f16: |w * scale| > 65504 is clamped; the pair carries 22 bits while |w * scale| >= 0.25, loses bits of `lo`
+ *   (an f16 subnormal) below that, is `hi` alone below 2^-13 and 0 below 2^-25.  With max |w| * scale in
+ *   (512, 1024] a weight 2^-11 of the largest still has all its bits; a whole LAYER that small next to a larger one
+ *   does not, and its error is not flagged.  Bring the layers' largest weights into one binade first - scale
+ *   (W_k, b_k) by a power of two c_k and W_k+1 by 1 / c_k, through to w_final: relu(c x) = c relu(x), exact in
+ *   float32 - as ACCURATE_NET.decision_layers does.  The activations carry the fixed factor 256 the same way: full
+ *   precision for 2^-10 <= x <= 255.875, flagged above, silently coarser below.
  * mode MCCNN_CV_EXACT: every float32 operand as two f16 numbers, three v_mfma_f32_32x32x16_f16 products per multiply,
  *   float32 accumulation - float32-accurate scores; MCCNN_CV_MFMA: one f16 product per multiply.
  * saturation_flag (device int, may be NULL): set to 1 when an activation of a stored voxel (w >= d, d < D, w < W)

@@ -223,6 +223,9 @@ __global__ __launch_bounds__(256) void decision_kernel(const float *__restrict__
 }
 
 static bool dk_mode_ok(int mode) { return mode == MCCNN_CV_EXACT || mode == MCCNN_CV_MFMA; }
+// finite, and scale * 256 and 1 / (scale * 256) normal float32 numbers (NaN fails either comparison): inf would pack
+// w * inf and make the reciprocal zero
+static bool dk_scale_ok(float scale) { return scale >= 0x1p-126f && scale <= 0x1p118f; }
 
 static int decision_check(const char *who, const void *aL, const void *aR, const void *packed, const void *biases,
                           const void *w_final, const void *lcv, const void *rcv, int H, int W, int C, int units, int n_fc,
@@ -274,7 +277,8 @@ extern "C" int mccnn_decision_pack(const float *weights, int n_fc, int units, fl
                   units, DK_UNITS);
     MCCNN_REQUIRE(n_fc == 3 || n_fc == 4, MCCNN_E_UNSUPPORTED,
                   "mccnn_decision_pack: %d fully-connected layers, the decision kernel serves 3 or 4", n_fc);
-    MCCNN_REQUIRE(weight_scale > 0.f, MCCNN_E_INVALID, "mccnn_decision_pack: weight_scale must be positive");
+    MCCNN_REQUIRE(dk_scale_ok(weight_scale), MCCNN_E_INVALID,
+                  "mccnn_decision_pack: weight_scale must be finite, in [2^-126, 2^118]");
     const int nl = n_fc - 1;
     const long n = (long)nl * (mode == MCCNN_CV_EXACT ? dk_chunks<true>() : dk_chunks<false>()) * 12 * 64;
     hipStream_t s = (hipStream_t)stream;
@@ -296,7 +300,8 @@ extern "C" int mccnn_cost_volume_accurate(const float *aL, const float *aR, int 
     int rc = decision_check("mccnn_cost_volume_accurate", aL, aR, packed, biases, w_final, lcv, rcv, H, W, C, units, n_fc, D,
                             mode);
     if (rc) return rc;
-    MCCNN_REQUIRE(weight_scale > 0.f, MCCNN_E_INVALID, "mccnn_cost_volume_accurate: weight_scale must be positive");
+    MCCNN_REQUIRE(dk_scale_ok(weight_scale), MCCNN_E_INVALID,
+                  "mccnn_cost_volume_accurate: weight_scale must be finite, in [2^-126, 2^118]");
     hipStream_t s = (hipStream_t)stream;
     const size_t plane = (size_t)H * W;
     if (mode == MCCNN_CV_EXACT)
@@ -319,7 +324,8 @@ extern "C" int mccnn_cost_volume_accurate_hwd(const float *aL, const float *aR, 
     int rc = decision_check("mccnn_cost_volume_accurate_hwd", aL, aR, packed, biases, w_final, lcv_hwd, rcv_hwd, H, W, C,
                             units, n_fc, D, mode);
     if (rc) return rc;
-    MCCNN_REQUIRE(weight_scale > 0.f, MCCNN_E_INVALID, "mccnn_cost_volume_accurate_hwd: weight_scale must be positive");
+    MCCNN_REQUIRE(dk_scale_ok(weight_scale), MCCNN_E_INVALID,
+                  "mccnn_cost_volume_accurate_hwd: weight_scale must be finite, in [2^-126, 2^118]");
     const int Dp = mccnn_hwd_pitch(D);
     MCCNN_REQUIRE((size_t)W * Dp * 4 < ((size_t)1 << 31), MCCNN_E_UNSUPPORTED,
                   "mccnn_cost_volume_accurate_hwd: a %d x %d row exceeds a buffer descriptor's reach", W, D);

@@ -425,19 +425,57 @@ class ACCURATE_NET(NET):
         raise ValueError("the split-operand feature kernels are built for the fast network (64 maps, normalised)")
 
     # -- decision kernel operands ---------------------------------------------------------------------------------------
+    def decision_weights_key(self):
+        """Changes whenever a tensor of the decision network is replaced or written in place (an optimiser step, a
+        copy_ under no_grad): what everything derived from those tensors is keyed on - the packed operands below, and
+        the captured graphs of a StereoMatcher, which hold the packed buffer's address."""
+        return tuple((w.data_ptr(), w._version) for w in self.fc_weights + self.fc_biases)
+
+    def decision_layers(self):
+        """The layers the decision kernel evaluates, equalised (stereo_device.decision_equalise_exponents): (weights
+        [n_fc-1,units,units] of fc 2 .. n_fc, biases [n_fc-1,units], final weights [units], final bias [1], [log2 c_k]).
+        The same network function - relu(c x) = c relu(x), every factor a power of two, exact in float32 - with every
+        layer's largest weight in one binade, which is what a single weight_scale can serve: a trained network is free
+        to drift its layers' magnitudes apart (the ReLU is positively homogeneous), and a layer 2^8 below its
+        neighbour would otherwise lose the `lo` halves of its operands.  The hidden activations the kernel sees are
+        c_k times the network's, so the saturation flag is raised by |c_k x| > 255.875, not |x|: a flagged pair is
+        repeated on the library route, which uses the network's own weights, as before.  The first layer
+        (first_layer_halves) is not part of this: it is a float32 library product on either route, and its output's
+        range is the pair's, not the weights'.  Non-finite weights are refused, naming the layer.  Plain torch, any
+        device; reads one scalar per layer back to the host."""
+        import stereo_device
+        ws = [w.detach().float() for w in self.fc_weights[1:-1]]
+        bs = [b.detach().float() for b in self.fc_biases[1:-1]]
+        maxima = torch.stack([w.abs().max() for w in ws]).tolist()
+        try:
+            exps = stereo_device.decision_equalise_exponents(maxima)
+        except ValueError as e:
+            raise stereo_device.hip.MccnnHipError("ACCURATE_NET.decision_layers: %s" % e)
+        prev = 0
+        for k, c in enumerate(exps):
+            if c != prev:
+                ws[k] = ws[k] * 2.0 ** (c - prev)
+            if c != 0:
+                bs[k] = bs[k] * 2.0 ** c
+            prev = c
+        w_final = self.fc_weights[-1].detach().float().reshape(-1)
+        if prev != 0:
+            w_final = w_final * 2.0 ** (-prev)
+        return (torch.stack(ws).contiguous(), torch.stack(bs).contiguous(), w_final.contiguous(),
+                self.fc_biases[-1].detach().float().reshape(-1), exps)
+
     def decision_operands(self, mode):
         """What mccnn_cost_volume_accurate* reads besides aL / aR, rebuilt when a weight tensor changes: (packed weights
-        of fc 2 .. n_fc, weight_scale, biases [n_fc-1,units], final weights [units], final bias as a float).  Reads two
-        scalars back to the host: once per weight set, never inside a graph capture."""
+        of fc 2 .. n_fc, weight_scale, biases [n_fc-1,units], final weights [units], final bias as a float), all of the
+        equalised layers (decision_layers).  Reads a few scalars back to the host: once per weight set, never inside a
+        graph capture."""
         import stereo_device
-        key = (int(mode),) + tuple((w.data_ptr(), w._version) for w in self.fc_weights + self.fc_biases)
+        key = (int(mode),) + self.decision_weights_key()
         cache = getattr(self, "_decision_cache", None)
         if cache is None or cache[0] != key:
-            mid = torch.stack([w.detach() for w in self.fc_weights[1:-1]]).contiguous()
+            mid, biases, w_final, b_final, _exps = self.decision_layers()
             packed, scale = stereo_device.decision_pack(mid, self.num_fc_layers, mode)
-            biases = torch.stack([b.detach() for b in self.fc_biases[1:-1]]).contiguous()
-            cache = (key, (packed, scale, biases, self.fc_weights[-1].detach().reshape(-1).contiguous(),
-                           float(self.fc_biases[-1].detach().reshape(-1)[0])))
+            cache = (key, (packed, scale, biases, w_final, float(b_final[0])))
             self._decision_cache = cache
         return cache[1]
 

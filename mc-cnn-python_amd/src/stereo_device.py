@@ -206,9 +206,62 @@ def decision_kernel_refusal(net, W, D):
     return None
 
 
+DECISION_SCALE_MAX_EXP = 118            # scale <= 2^118: scale * 256 = 2^126 and 1 / (scale * 256) are normal float32
+DECISION_SCALE_MIN_EXP = -126
+DECISION_EQUALISE_MAX_EXP = 64          # |log2 c_k| <= 64: c_k * bias and w / c_k stay far from float32's ends
+
+
+def decision_weight_scale(m):
+    """The power of two the decision kernel's weights are packed with, from m = max |w| over the packed layers (pure:
+    no device).  scale = 2^e, e = floor(log2(1024 / m)), i.e. m * scale in (512, 1024] - the f16 operands then end at
+    1024 of 65504 and a hi + lo pair keeps 22 bits down to |w * scale| = 0.25 - and e clamped to [DECISION_SCALE_MIN_EXP,
+    DECISION_SCALE_MAX_EXP], so that scale, scale * 256 (the activations' factor) and the reciprocal the kernel
+    multiplies by are finite, normal float32 numbers whatever m is.  Weights below 2^-24 / scale then become 0: with
+    the clamp active that is |w| < 2^-142, nothing a float32 sum can see.  m = 0 (all-zero weights): 1.  A negative,
+    infinite or NaN m is refused: such weights have no packed form, and scale 1 with a clamp to +-65504 - the earlier
+    rule - returned finite scores where the network's are inf or NaN."""
+    m = float(m)
+    if not (math.isfinite(m) and m >= 0.0):
+        raise ValueError("decision_weight_scale: max |w| = %r, the decision kernel packs finite weights only" % m)
+    if m == 0.0:
+        return 1.0
+    f, x = math.frexp(m)                   # m = f * 2^x, f in [0.5, 1): 1024 / m = (1 / f) * 2^(10 - x), 1 / f in (1, 2]
+    e = 10 - x + (1 if f == 0.5 else 0)    # floor(log2(1024 / m)) without log2's rounding
+    return 2.0 ** max(DECISION_SCALE_MIN_EXP, min(DECISION_SCALE_MAX_EXP, e))
+
+
+def decision_equalise_exponents(maxima):
+    """maxima: max |w| of each hidden layer the decision kernel packs (fc 2 .. n_fc) -> [log2 c_k], the exact
+    power-of-two factors that bring every layer's largest weight into ONE binade, so that the single weight_scale of
+    the packed operands serves each of them with all 22 bits:
+        W'_k = W_k * c_k / c_(k-1),  b'_k = b_k * c_k  (c_1 = 1),  w_final' = w_final / c_n.
+    relu(c x) = c relu(x) for c > 0, so the network function is unchanged; in float32 the products are exact (powers
+    of two) short of overflow and underflow.  The common binade is the mean of the layers' own (rounded): the product
+    of the layer gains is kept, each layer gets an equal share, and log2 c_n stays within half the number of layers, so
+    the last hidden layer and w_final keep their magnitude.  Layers whose largest weights already share a binade
+    (glorot) get c_k = 1 and the same bits as before.  All-zero layers are left alone; |log2 c_k| is clamped to
+    DECISION_EQUALISE_MAX_EXP (the equalisation is then partial, and still exact).  Pure: no device."""
+    for k, m in enumerate(maxima):
+        if not (math.isfinite(float(m)) and float(m) >= 0.0):
+            raise ValueError("fc%d: max |w| = %r, the decision kernel packs finite weights only" % (k + 2, float(m)))
+    exps = [math.frexp(float(m))[1] if float(m) > 0.0 else None for m in maxima]
+    live = [e for e in exps if e is not None]
+    if not live:
+        return [0] * len(exps)
+    target = int(math.floor(sum(live) / float(len(live)) + 0.5))
+    out, c = [], 0
+    for e in exps:
+        if e is not None:
+            c = max(-DECISION_EQUALISE_MAX_EXP, min(DECISION_EQUALISE_MAX_EXP, c + target - e))
+        out.append(c)
+    return out
+
+
 def decision_pack(weights, n_fc, mode):
     """weights [n_fc-1, units, units] (torch layout [out,in]) of the hidden layers 2 .. n_fc -> (packed device buffer,
-    weight_scale) for mccnn_cost_volume_accurate*(mode).  Reads max |w| back to the host: once per weight set."""
+    weight_scale) for mccnn_cost_volume_accurate*(mode).  Reads max |w| back to the host: once per weight set.  ONE
+    scale serves all layers (decision_weight_scale): layers of different magnitude are equalised first
+    (ACCURATE_NET.decision_layers).  Non-finite weights are refused."""
     lib = hip.load()
     w = weights.detach().contiguous().float()
     units = int(w.shape[-1])
@@ -216,8 +269,10 @@ def decision_pack(weights, n_fc, mode):
     if nbytes == 0 or tuple(w.shape) != (n_fc - 1, units, units):
         raise hip.MccnnHipError("mccnn_decision_pack: %d fc layers of %d units are outside the decision kernel's "
                                 "envelope (3 or 4 layers of %d units)" % (n_fc, units, DECISION_UNITS))
-    m = float(w.abs().max())
-    scale = 2.0 ** math.floor(math.log2(1024.0 / m)) if m > 0.0 and math.isfinite(m) else 1.0
+    try:
+        scale = decision_weight_scale(float(w.abs().max()))      # (max propagates NaN)
+    except ValueError as e:
+        raise hip.MccnnHipError("mccnn_decision_pack: %s" % e)
     packed = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
     hip.check(lib.mccnn_decision_pack(hip.ptr(w), int(n_fc), units, scale, int(mode), hip.ptr(packed), hip.stream()),
               "mccnn_decision_pack")
@@ -2007,6 +2062,19 @@ class StereoMatcher(object):
         ingest_u8_pair(left_u8, right_u8, sl, sr, scratch)
         return self.match(sl, sr, ndisp, out=out, confidence_out=confidence_out)
 
+    def _graph_key(self, key):
+        """The key of a pair's captured graph.  An accurate network's graph holds the ADDRESS of the packed decision
+        operands and the final bias by value (ACCURATE_NET.decision_operands rebuilds both when a weight tensor changes),
+        so its key carries the network's decision_weights_key(): after an optimiser step or a load_state the pair is
+        captured again, and the graphs of the weights before are dropped (a replay of one would read the earlier
+        weights' buffer, or memory the allocator has handed on).  The tower's weights are read in place and need none."""
+        if not self.accurate:
+            return key
+        key = key + (self.net.decision_weights_key(),)
+        for k in [k for k in self._graphs if k[-1] != key[-1]]:
+            del self._graphs[k]
+        return key
+
     def _capture(self, key, shape, make_static, prologue=None):
         """One pair captured as a graph: self._graphs[key] = (graph, static, out).  make_static() allocates and fills
         the static inputs - static[0], static[1]: the float32 images the pair reads - once the workspace is resident;
@@ -2067,7 +2135,7 @@ class StereoMatcher(object):
         H, W, C = _u8_image(left_u8)
         if _u8_image(right_u8) != (H, W, C):
             raise ValueError("match_graph_u8: the two images must have the same shape")
-        key = (H, W, int(ndisp), "u8", C)
+        key = self._graph_key((H, W, int(ndisp), "u8", C))
         g = self._graphs.get(key) or self._capture(
             key, key[:3], lambda: self._static_u8(left_u8, right_u8, H, W),
             lambda sl, sr, bl, br, scratch: ingest_u8_pair(bl, br, sl, sr, scratch))
@@ -2091,8 +2159,8 @@ class StereoMatcher(object):
         by the next call; with confidence measures (map, planes), both static).  The images are copied into the static inputs in stream order; nothing synchronises."""
         L = left_image.reshape(left_image.shape[0], left_image.shape[1])
         R = right_image.reshape(right_image.shape[0], right_image.shape[1])
-        key = (L.shape[0], L.shape[1], int(ndisp))
-        graph, (sl, sr), out = self._graphs.get(key) or self._capture(key, key, lambda: self._static_f32(L, R))
+        key = self._graph_key((L.shape[0], L.shape[1], int(ndisp)))
+        graph, (sl, sr), out = self._graphs.get(key) or self._capture(key, key[:3], lambda: self._static_f32(L, R))
         sl.copy_(L)
         sr.copy_(R)
         graph.replay()

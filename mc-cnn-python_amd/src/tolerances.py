@@ -60,5 +60,9 @@ def fast_violations(pixels, flips_left, flips_right, frac_within_1e3, p99_abs_px
 #   layer's input activations are rounded to f16.
 ACCURATE_SCORE_ABS = 1e-5           # ACCURATE_NET's float32 torch forward (patch batches) vs float64: FEATURES_ABS's class
 ACCURATE_SPLIT_E32_FACTOR = 4       # default precision: <= 4 x E32 (a split operand carries 22 significand bits, float32 24)
+# The split bound holds on trained-looking weights too (tests/test_accurate_weights_gpu.py): layers of different
+# magnitude are equalised exactly before they are packed (ACCURATE_NET.decision_layers), and the spread INSIDE a layer
+# needs no guard - f16 subnormal operands survive the matrix-core path (measured), so a weight keeps an
+# absolute precision of 2^-25 / scale however small it is, 2^-34 of the layer's largest.  No family is routed away.
 ACCURATE_F16_E16_FACTOR = 2         # f16 precision: <= 2 x E16 + 4 x E32 (float32 accumulation can move an activation
                                     # across an f16 rounding boundary: twice the half-spacing error of the emulation)
