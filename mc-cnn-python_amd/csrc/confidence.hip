@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256) void confidence_kernel(const float *__restrict
 }
 
 static int validate(const char *who, const float *vol, const float *dr, int D, int H, int W, unsigned measures,
-                    const float *out, const char *other = "disp_right")
+                    const float *out, const char *other)
 {
     MCCNN_REQUIRE(vol && out, MCCNN_E_INVALID, "%s: null pointer", who);
     MCCNN_REQUIRE(D >= 2, MCCNN_E_INVALID, "%s: D=%d, the measures need at least two disparities", who, D);
@@ -183,59 +183,58 @@ static int validate(const char *who, const float *vol, const float *dr, int D, i
     return 0;
 }
 
+// One launcher per layout.  MIRROR: the right view's measures; `other`: the name of the other view's map in refusals.
+template <bool MIRROR>
+static int launch_hwd(const float *vol_hwd, const float *dr, int D, int H, int W, unsigned measures, float *out,
+                      hipStream_t s, const char *who, const char *other)
+{
+    if (const int rc = validate(who, vol_hwd, dr, D, H, W, measures, out, other)) return rc;
+    MCCNN_REQUIRE(D <= 1024, MCCNN_E_UNSUPPORTED, "%s: D=%d above 1024", who, D);
+    const long N = (long)H * W;
+    const int per_wave = 64;   // pixels per wave: 8 rounds of 8
+    const long waves = (N + per_wave - 1) / per_wave;
+    hipLaunchKernelGGL(confidence_hwd_kernel<MIRROR>, dim3((unsigned)cdiv(waves, 4)), dim3(256), 0, s, vol_hwd, dr, D,
+                       mccnn_hwd_pitch(D), W, N, measures, out, per_wave);
+    return check_launch(who);
+}
+
+template <bool MIRROR>
+static int launch_dhw(const float *vol_dhw, const float *dr, int D, int H, int W, unsigned measures, float *out,
+                      hipStream_t s, const char *who, const char *other)
+{
+    if (const int rc = validate(who, vol_dhw, dr, D, H, W, measures, out, other)) return rc;
+    const long N = (long)H * W;
+    hipLaunchKernelGGL(confidence_kernel<MIRROR>, dim3(cdiv(N, 256)), dim3(256), 0, s, vol_dhw, dr, D, W, N, measures, out);
+    return check_launch(who);
+}
+
 }  // namespace conf
 }  // namespace mccnn
 
 extern "C" int mccnn_confidence_hwd(const float *vol_hwd, const float *disp_right, int D, int H, int W, unsigned measures,
                                     float *out, mccnn_stream_t stream)
 {
-    using namespace mccnn;
-    if (const int rc = conf::validate("mccnn_confidence_hwd", vol_hwd, disp_right, D, H, W, measures, out)) return rc;
-    MCCNN_REQUIRE(D <= 1024, MCCNN_E_UNSUPPORTED, "mccnn_confidence_hwd: D=%d above 1024", D);
-    const long N = (long)H * W;
-    const int per_wave = 64;   // pixels per wave: 8 rounds of 8
-    const long waves = (N + per_wave - 1) / per_wave;
-    hipLaunchKernelGGL(conf::confidence_hwd_kernel<false>, dim3((unsigned)cdiv(waves, 4)), dim3(256), 0, (hipStream_t)stream,
-                       vol_hwd, disp_right, D, mccnn_hwd_pitch(D), W, N, measures, out, per_wave);
-    return check_launch("mccnn_confidence_hwd");
+    return mccnn::conf::launch_hwd<false>(vol_hwd, disp_right, D, H, W, measures, out, (hipStream_t)stream,
+                                          "mccnn_confidence_hwd", "disp_right");
 }
 
 extern "C" int mccnn_confidence(const float *vol_dhw, const float *disp_right, int D, int H, int W, unsigned measures,
                                 float *out, mccnn_stream_t stream)
 {
-    using namespace mccnn;
-    if (const int rc = conf::validate("mccnn_confidence", vol_dhw, disp_right, D, H, W, measures, out)) return rc;
-    const long N = (long)H * W;
-    hipLaunchKernelGGL(conf::confidence_kernel<false>, dim3(cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, vol_dhw,
-                       disp_right, D, W, N, measures, out);
-    return check_launch("mccnn_confidence");
+    return mccnn::conf::launch_dhw<false>(vol_dhw, disp_right, D, H, W, measures, out, (hipStream_t)stream,
+                                          "mccnn_confidence", "disp_right");
 }
 
 extern "C" int mccnn_confidence_right_hwd(const float *vol_right_hwd, const float *disp_left, int D, int H, int W,
                                           unsigned measures, float *out, mccnn_stream_t stream)
 {
-    using namespace mccnn;
-    if (const int rc = conf::validate("mccnn_confidence_right_hwd", vol_right_hwd, disp_left, D, H, W, measures, out,
-                                      "disp_left"))
-        return rc;
-    MCCNN_REQUIRE(D <= 1024, MCCNN_E_UNSUPPORTED, "mccnn_confidence_right_hwd: D=%d above 1024", D);
-    const long N = (long)H * W;
-    const int per_wave = 64;   // pixels per wave: 8 rounds of 8
-    const long waves = (N + per_wave - 1) / per_wave;
-    hipLaunchKernelGGL(conf::confidence_hwd_kernel<true>, dim3((unsigned)cdiv(waves, 4)), dim3(256), 0,
-                       (hipStream_t)stream, vol_right_hwd, disp_left, D, mccnn_hwd_pitch(D), W, N, measures, out, per_wave);
-    return check_launch("mccnn_confidence_right_hwd");
+    return mccnn::conf::launch_hwd<true>(vol_right_hwd, disp_left, D, H, W, measures, out, (hipStream_t)stream,
+                                         "mccnn_confidence_right_hwd", "disp_left");
 }
 
 extern "C" int mccnn_confidence_right(const float *vol_right_dhw, const float *disp_left, int D, int H, int W,
                                       unsigned measures, float *out, mccnn_stream_t stream)
 {
-    using namespace mccnn;
-    if (const int rc = conf::validate("mccnn_confidence_right", vol_right_dhw, disp_left, D, H, W, measures, out,
-                                      "disp_left"))
-        return rc;
-    const long N = (long)H * W;
-    hipLaunchKernelGGL(conf::confidence_kernel<true>, dim3(cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream,
-                       vol_right_dhw, disp_left, D, W, N, measures, out);
-    return check_launch("mccnn_confidence_right");
+    return mccnn::conf::launch_dhw<true>(vol_right_dhw, disp_left, D, H, W, measures, out, (hipStream_t)stream,
+                                         "mccnn_confidence_right", "disp_left");
 }

@@ -620,6 +620,83 @@ __global__ __launch_bounds__(256) void l2norm_chw_to_hwc_kernel(const float *__r
     }
 }
 
+// ---- launchers of a8 / a9: one per kernel family; `who` names the entry in every refusal and launch error ------------
+// a8, the check.  MIRROR: the right view's rule; the operands are (the map being judged, the other view's map).
+template <bool MIRROR>
+static int launch_lr_status(const float *own, const float *other, int H, int W, int D, int32_t *status, hipStream_t s,
+                            const char *who)
+{
+    MCCNN_REQUIRE(own && other && status, MCCNN_E_INVALID, "%s: null pointer", who);
+    MCCNN_REQUIRE(D > 0 && H > 0 && W > 0, MCCNN_E_INVALID, "%s: non-positive size", who);
+    MCCNN_REQUIRE(W <= 32 * LR_MAX_WORDS || H <= MAX_GRID_Y, MCCNN_E_UNSUPPORTED,
+                  "%s: H=%d exceeds grid.y for rows wider than %d", who, H, 32 * LR_MAX_WORDS);
+    if (W <= 32 * LR_MAX_WORDS)
+        hipLaunchKernelGGL(lr_status_kernel<MIRROR>, dim3(H), dim3(256), 0, s, own, other, H, W, D, status);
+    else
+        hipLaunchKernelGGL(lr_status_walk_kernel<MIRROR>, dim3(cdiv(W, 256), H), dim3(256), 0, s, own, other, H, W, D,
+                           status);
+    return check_launch(who);
+}
+
+// check_launch for one launch of an entry that makes two: the label is `who(step)`
+static int check_launch_step(const char *who, const char *step)
+{
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return 0;
+    set_error("%s(%s): %s", who, step, hipGetErrorString(e));
+    return (int)e;
+}
+
+// a8, the filling.  MIRROR: the right view's rules, `occlusion` then its occlusion_from_right.  allow_row_path: the
+// reference's rule (4 directions, occlusions from the far side) may take the vertical + row kernels where the image is
+// inside their limits; everything else walks per pixel - the left view's reference rule in interpolate_kernel, every
+// other rule in its interpolate_paper_kernel.
+template <bool MIRROR>
+static int launch_interpolate(int directions, int occlusion, bool allow_row_path, const float *disp, const int32_t *status,
+                              int H, int W, float *out, hipStream_t s, const char *who)
+{
+    MCCNN_REQUIRE(disp && status && out, MCCNN_E_INVALID, "%s: null pointer", who);
+    MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "%s: non-positive size", who);
+    MCCNN_REQUIRE(disp != out, MCCNN_E_INVALID, "%s: out must not alias the input map", who);
+    MCCNN_REQUIRE((const void *)status != (const void *)out, MCCNN_E_INVALID, "%s: out must not alias the status map", who);
+    MCCNN_REQUIRE(H <= MAX_GRID_Y, MCCNN_E_UNSUPPORTED, "%s: H=%d exceeds grid.y", who, H);
+    MCCNN_REQUIRE(directions == 4 || directions == 16, MCCNN_E_INVALID, "%s: directions=%d (4 or 16)", who, directions);
+    if (allow_row_path && directions == 4 && !occlusion && H < 65535 && W <= 64 * INTERP_MAX_WORDS) {
+        hipLaunchKernelGGL(interpolate_vertical_kernel, dim3(cdiv(W, 64), 2), dim3(64), 0, s, status, H, W,
+                           reinterpret_cast<uint16_t *>(out));
+        const int rc = check_launch_step(who, "vertical");
+        if (rc) return rc;
+        hipLaunchKernelGGL(interpolate_row_kernel<MIRROR>, dim3(H), dim3(256), 0, s, disp, status, H, W, out);
+        return check_launch_step(who, "rows");
+    }
+    const dim3 grid(cdiv(W, 256), H), block(256);
+    if (directions == 16 && occlusion)
+        hipLaunchKernelGGL((interpolate_paper_kernel<true, true, MIRROR>), grid, block, 0, s, disp, status, H, W, out);
+    else if (directions == 16)
+        hipLaunchKernelGGL((interpolate_paper_kernel<true, false, MIRROR>), grid, block, 0, s, disp, status, H, W, out);
+    else if (occlusion)
+        hipLaunchKernelGGL((interpolate_paper_kernel<false, true, MIRROR>), grid, block, 0, s, disp, status, H, W, out);
+    else if constexpr (MIRROR)
+        hipLaunchKernelGGL((interpolate_paper_kernel<false, false, true>), grid, block, 0, s, disp, status, H, W, out);
+    else
+        hipLaunchKernelGGL(interpolate_kernel, grid, block, 0, s, disp, status, H, W, out);
+    return check_launch(who);
+}
+
+// a9 on a plane-major volume
+static int launch_subpixel(const float *disp, const float *vol_dhw, int D, int H, int W, int numpy1_promotion, float *out,
+                           hipStream_t s, const char *who)
+{
+    MCCNN_REQUIRE(disp && vol_dhw && out, MCCNN_E_INVALID, "%s: null pointer", who);
+    MCCNN_REQUIRE(D > 0 && H > 0 && W > 0, MCCNN_E_INVALID, "%s: non-positive size", who);
+    const long N = (long)H * W;
+    if (numpy1_promotion)
+        hipLaunchKernelGGL(subpixel_kernel<true>, dim3(cdiv(N, 256)), dim3(256), 0, s, disp, vol_dhw, D, N, out);
+    else
+        hipLaunchKernelGGL(subpixel_kernel<false>, dim3(cdiv(N, 256)), dim3(256), 0, s, disp, vol_dhw, D, N, out);
+    return check_launch(who);
+}
+
 }  // namespace mccnn
 
 extern "C" int mccnn_wta(const float *vol_dhw, int D, int H, int W, float *disparity, mccnn_stream_t stream)
@@ -635,145 +712,47 @@ extern "C" int mccnn_wta(const float *vol_dhw, int D, int H, int W, float *dispa
 extern "C" int mccnn_lr_status(const float *disp_left, const float *disp_right, int H, int W, int D, int32_t *status,
                                mccnn_stream_t stream)
 {
-    using namespace mccnn;
-    MCCNN_REQUIRE(disp_left && disp_right && status, MCCNN_E_INVALID, "mccnn_lr_status: null pointer");
-    MCCNN_REQUIRE(D > 0 && H > 0 && W > 0, MCCNN_E_INVALID, "mccnn_lr_status: non-positive size");
-    MCCNN_REQUIRE(W <= 32 * LR_MAX_WORDS || H <= MAX_GRID_Y, MCCNN_E_UNSUPPORTED,
-                  "mccnn_lr_status: H=%d exceeds grid.y for rows wider than %d", H, 32 * LR_MAX_WORDS);
-    if (W <= 32 * LR_MAX_WORDS)
-        hipLaunchKernelGGL(lr_status_kernel<false>, dim3(H), dim3(256), 0, (hipStream_t)stream, disp_left, disp_right, H, W, D,
-                           status);
-    else
-        hipLaunchKernelGGL(lr_status_walk_kernel<false>, dim3(cdiv(W, 256), H), dim3(256), 0, (hipStream_t)stream, disp_left,
-                           disp_right, H, W, D, status);
-    return check_launch("mccnn_lr_status");
-}
-
-extern "C" int mccnn_interpolate(const float *disp_left, const int32_t *status, int H, int W, float *out,
-                                 mccnn_stream_t stream)
-{
-    using namespace mccnn;
-    MCCNN_REQUIRE(disp_left && status && out, MCCNN_E_INVALID, "mccnn_interpolate: null pointer");
-    MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "mccnn_interpolate: non-positive size");
-    MCCNN_REQUIRE(disp_left != out, MCCNN_E_INVALID, "mccnn_interpolate: out must not alias the input map");
-    MCCNN_REQUIRE((const void *)status != (const void *)out, MCCNN_E_INVALID,
-                  "mccnn_interpolate: out must not alias the status map");
-    MCCNN_REQUIRE(H <= MAX_GRID_Y, MCCNN_E_UNSUPPORTED, "mccnn_interpolate: H=%d exceeds grid.y", H);
-    if (H < 65535 && W <= 64 * INTERP_MAX_WORDS) {
-        hipLaunchKernelGGL(interpolate_vertical_kernel, dim3(cdiv(W, 64), 2), dim3(64), 0, (hipStream_t)stream, status, H,
-                           W, reinterpret_cast<uint16_t *>(out));
-        int rc = check_launch("mccnn_interpolate(vertical)");
-        if (rc) return rc;
-        hipLaunchKernelGGL(interpolate_row_kernel<false>, dim3(H), dim3(256), 0, (hipStream_t)stream, disp_left, status, H, W,
-                           out);
-        return check_launch("mccnn_interpolate(rows)");
-    }
-    hipLaunchKernelGGL(interpolate_kernel, dim3(cdiv(W, 256), H), dim3(256), 0, (hipStream_t)stream, disp_left, status,
-                       H, W, out);
-    return check_launch("mccnn_interpolate");
-}
-
-extern "C" int mccnn_interpolate_ex(const float *disp_left, const int32_t *status, int H, int W, int directions,
-                                    int occlusion_from_left, float *out, mccnn_stream_t stream)
-{
-    using namespace mccnn;
-    MCCNN_REQUIRE(disp_left && status && out, MCCNN_E_INVALID, "mccnn_interpolate_ex: null pointer");
-    MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "mccnn_interpolate_ex: non-positive size");
-    MCCNN_REQUIRE(disp_left != out, MCCNN_E_INVALID, "mccnn_interpolate_ex: out must not alias the input map");
-    MCCNN_REQUIRE((const void *)status != (const void *)out, MCCNN_E_INVALID,
-                  "mccnn_interpolate_ex: out must not alias the status map");
-    MCCNN_REQUIRE(H <= MAX_GRID_Y, MCCNN_E_UNSUPPORTED, "mccnn_interpolate_ex: H=%d exceeds grid.y", H);
-    MCCNN_REQUIRE(directions == 4 || directions == 16, MCCNN_E_INVALID, "mccnn_interpolate_ex: directions=%d (4 or 16)",
-                  directions);
-    const dim3 grid(cdiv(W, 256), H), block(256);
-    hipStream_t s = (hipStream_t)stream;
-    if (directions == 16 && occlusion_from_left)
-        hipLaunchKernelGGL((interpolate_paper_kernel<true, true>), grid, block, 0, s, disp_left, status, H, W, out);
-    else if (directions == 16)
-        hipLaunchKernelGGL((interpolate_paper_kernel<true, false>), grid, block, 0, s, disp_left, status, H, W, out);
-    else if (occlusion_from_left)
-        hipLaunchKernelGGL((interpolate_paper_kernel<false, true>), grid, block, 0, s, disp_left, status, H, W, out);
-    else
-        hipLaunchKernelGGL(interpolate_kernel, grid, block, 0, s, disp_left, status, H, W, out);
-    return check_launch("mccnn_interpolate_ex");
+    return mccnn::launch_lr_status<false>(disp_left, disp_right, H, W, D, status, (hipStream_t)stream, "mccnn_lr_status");
 }
 
 extern "C" int mccnn_lr_status_right(const float *disp_right, const float *disp_left, int H, int W, int D,
                                      int32_t *status, mccnn_stream_t stream)
 {
-    using namespace mccnn;
-    MCCNN_REQUIRE(disp_right && disp_left && status, MCCNN_E_INVALID, "mccnn_lr_status_right: null pointer");
-    MCCNN_REQUIRE(D > 0 && H > 0 && W > 0, MCCNN_E_INVALID, "mccnn_lr_status_right: non-positive size");
-    MCCNN_REQUIRE(W <= 32 * LR_MAX_WORDS || H <= MAX_GRID_Y, MCCNN_E_UNSUPPORTED,
-                  "mccnn_lr_status_right: H=%d exceeds grid.y for rows wider than %d", H, 32 * LR_MAX_WORDS);
-    if (W <= 32 * LR_MAX_WORDS)
-        hipLaunchKernelGGL(lr_status_kernel<true>, dim3(H), dim3(256), 0, (hipStream_t)stream, disp_right, disp_left, H,
-                           W, D, status);
-    else
-        hipLaunchKernelGGL(lr_status_walk_kernel<true>, dim3(cdiv(W, 256), H), dim3(256), 0, (hipStream_t)stream,
-                           disp_right, disp_left, H, W, D, status);
-    return check_launch("mccnn_lr_status_right");
+    return mccnn::launch_lr_status<true>(disp_right, disp_left, H, W, D, status, (hipStream_t)stream,
+                                         "mccnn_lr_status_right");
+}
+
+extern "C" int mccnn_interpolate(const float *disp_left, const int32_t *status, int H, int W, float *out,
+                                 mccnn_stream_t stream)
+{
+    return mccnn::launch_interpolate<false>(4, 0, true, disp_left, status, H, W, out, (hipStream_t)stream,
+                                            "mccnn_interpolate");
+}
+
+extern "C" int mccnn_interpolate_ex(const float *disp_left, const int32_t *status, int H, int W, int directions,
+                                    int occlusion_from_left, float *out, mccnn_stream_t stream)
+{
+    return mccnn::launch_interpolate<false>(directions, occlusion_from_left, false, disp_left, status, H, W, out,
+                                            (hipStream_t)stream, "mccnn_interpolate_ex");
 }
 
 extern "C" int mccnn_interpolate_right(const float *disp_right, const int32_t *status, int H, int W, int directions,
                                        int occlusion_from_right, float *out, mccnn_stream_t stream)
 {
-    using namespace mccnn;
-    MCCNN_REQUIRE(disp_right && status && out, MCCNN_E_INVALID, "mccnn_interpolate_right: null pointer");
-    MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "mccnn_interpolate_right: non-positive size");
-    MCCNN_REQUIRE(disp_right != out, MCCNN_E_INVALID, "mccnn_interpolate_right: out must not alias the input map");
-    MCCNN_REQUIRE((const void *)status != (const void *)out, MCCNN_E_INVALID,
-                  "mccnn_interpolate_right: out must not alias the status map");
-    MCCNN_REQUIRE(H <= MAX_GRID_Y, MCCNN_E_UNSUPPORTED, "mccnn_interpolate_right: H=%d exceeds grid.y", H);
-    MCCNN_REQUIRE(directions == 4 || directions == 16, MCCNN_E_INVALID,
-                  "mccnn_interpolate_right: directions=%d (4 or 16)", directions);
-    hipStream_t s = (hipStream_t)stream;
-    if (directions == 4 && !occlusion_from_right && H < 65535 && W <= 64 * INTERP_MAX_WORDS) {
-        hipLaunchKernelGGL(interpolate_vertical_kernel, dim3(cdiv(W, 64), 2), dim3(64), 0, s, status, H, W,
-                           reinterpret_cast<uint16_t *>(out));
-        int rc = check_launch("mccnn_interpolate_right(vertical)");
-        if (rc) return rc;
-        hipLaunchKernelGGL(interpolate_row_kernel<true>, dim3(H), dim3(256), 0, s, disp_right, status, H, W, out);
-        return check_launch("mccnn_interpolate_right(rows)");
-    }
-    const dim3 grid(cdiv(W, 256), H), block(256);
-    if (directions == 16 && occlusion_from_right)
-        hipLaunchKernelGGL((interpolate_paper_kernel<true, true, true>), grid, block, 0, s, disp_right, status, H, W, out);
-    else if (directions == 16)
-        hipLaunchKernelGGL((interpolate_paper_kernel<true, false, true>), grid, block, 0, s, disp_right, status, H, W, out);
-    else if (occlusion_from_right)
-        hipLaunchKernelGGL((interpolate_paper_kernel<false, true, true>), grid, block, 0, s, disp_right, status, H, W, out);
-    else
-        hipLaunchKernelGGL((interpolate_paper_kernel<false, false, true>), grid, block, 0, s, disp_right, status, H, W, out);
-    return check_launch("mccnn_interpolate_right");
+    return mccnn::launch_interpolate<true>(directions, occlusion_from_right, true, disp_right, status, H, W, out,
+                                           (hipStream_t)stream, "mccnn_interpolate_right");
 }
 
 extern "C" int mccnn_subpixel_ex(const float *disp, const float *vol_dhw, int D, int H, int W, int numpy1_promotion,
                                  float *out, mccnn_stream_t stream)
 {
-    using namespace mccnn;
-    MCCNN_REQUIRE(disp && vol_dhw && out, MCCNN_E_INVALID, "mccnn_subpixel_ex: null pointer");
-    MCCNN_REQUIRE(D > 0 && H > 0 && W > 0, MCCNN_E_INVALID, "mccnn_subpixel_ex: non-positive size");
-    const long N = (long)H * W;
-    if (numpy1_promotion)
-        hipLaunchKernelGGL(subpixel_kernel<true>, dim3(cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, disp, vol_dhw, D,
-                           N, out);
-    else
-        hipLaunchKernelGGL(subpixel_kernel<false>, dim3(cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, disp, vol_dhw,
-                           D, N, out);
-    return check_launch("mccnn_subpixel_ex");
+    return mccnn::launch_subpixel(disp, vol_dhw, D, H, W, numpy1_promotion, out, (hipStream_t)stream, "mccnn_subpixel_ex");
 }
 
 extern "C" int mccnn_subpixel(const float *disp, const float *vol_dhw, int D, int H, int W, float *out,
                               mccnn_stream_t stream)
 {
-    using namespace mccnn;
-    MCCNN_REQUIRE(disp && vol_dhw && out, MCCNN_E_INVALID, "mccnn_subpixel: null pointer");
-    MCCNN_REQUIRE(D > 0 && H > 0 && W > 0, MCCNN_E_INVALID, "mccnn_subpixel: non-positive size");
-    const long N = (long)H * W;
-    hipLaunchKernelGGL(subpixel_kernel<false>, dim3(cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, disp, vol_dhw, D, N,
-                       out);
-    return check_launch("mccnn_subpixel");
+    return mccnn::launch_subpixel(disp, vol_dhw, D, H, W, 0, out, (hipStream_t)stream, "mccnn_subpixel");
 }
 
 extern "C" int mccnn_median(const float *disp, int H, int W, int fh, int fw, float *out, mccnn_stream_t stream)

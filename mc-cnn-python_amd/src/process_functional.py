@@ -338,5 +338,5 @@ def confidence_measures(left_cost_volume, right_disparity_map=None, measures=CON
     v, was_np = _dev(left_cost_volume)
     dr = None if right_disparity_map is None else _dev(right_disparity_map)[0]
     names = sd.confidence_names(measures)
-    planes = (sd.confidence if view == "left" else sd.confidence_right)(v, dr, names)
+    planes = sd.confidence(v, dr, names, view=view)
     return dict((n, _ret(planes[i].clone(), was_np)) for i, n in enumerate(names))

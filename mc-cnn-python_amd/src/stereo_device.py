@@ -4,6 +4,7 @@ Everything here takes and returns torch device tensors; nothing touches host mem
 PyTorch except the 5-layer conv stack (model.NET).  The NumPy-facing drop-in lives in process_functional.py and the
 whole-pair driver (the timed region of the reference's match.py:129-179) is StereoMatcher.match below.
 """
+import collections
 import ctypes
 import math
 
@@ -1134,6 +1135,11 @@ def wta_hwd(vol_hwd, D, out=None):
     return disp
 
 
+def wta_any(vol, D, pixel_major, out=None):
+    """wta_hwd() or wta(), as the volume's layout asks."""
+    return wta_hwd(vol, D, out=out) if pixel_major else wta(vol, out=out)
+
+
 def subpixel_hwd(dl, vol_hwd, D, out=None, numpy1_promotion=False):
     """subpixel() on a pixel-major volume [H,W,Dp]."""
     H, W, Dp = vol_hwd.shape
@@ -1172,12 +1178,21 @@ def confidence_names(measures):
     return tuple(n for n in CONFIDENCE_MEASURES if mask & _CONFIDENCE_BITS[n])
 
 
-def _confidence(entry, vol, D, H, W, disp_right, measures, out):
+VIEW_SUFFIX = {"left": "", "right": "_right"}     # view= of the wrappers below -> what the entry's name carries
+
+
+def _view_suffix(view):
+    if view not in VIEW_SUFFIX:
+        raise ValueError("view must be 'left' or 'right'")
+    return VIEW_SUFFIX[view]
+
+
+def _confidence(entry, vol, D, H, W, disp_other, measures, out):
     mask = confidence_mask(measures)
     k = bin(mask).count("1")
-    if mask & hip.MCCNN_CONF_LRC and disp_right is None:
+    if mask & hip.MCCNN_CONF_LRC and disp_other is None:
         raise ValueError("%s: the lrc measure needs the other view's disparity map" % entry)
-    if disp_right is not None and (tuple(disp_right.shape) != (H, W) or disp_right.dtype != torch.float32):
+    if disp_other is not None and (tuple(disp_other.shape) != (H, W) or disp_other.dtype != torch.float32):
         raise ValueError("%s: the other view's disparity must be a float32 [H,W] map" % entry)
     if vol.dtype != torch.float32:
         raise ValueError("%s: the volume must be float32" % entry)
@@ -1185,79 +1200,78 @@ def _confidence(entry, vol, D, H, W, disp_right, measures, out):
         out = torch.empty((k, H, W), dtype=torch.float32, device=vol.device)
     elif tuple(out.shape) != (k, H, W) or out.dtype != torch.float32:
         raise ValueError("%s: `out` must be a float32 [%d,%d,%d] tensor" % (entry, k, H, W))
-    hip.check(getattr(hip.load(), entry)(hip.ptr(vol), hip.ptr(disp_right) if disp_right is not None else None, int(D), H,
+    hip.check(getattr(hip.load(), entry)(hip.ptr(vol), hip.ptr(disp_other) if disp_other is not None else None, int(D), H,
                                          W, mask, hip.ptr(out), hip.stream()), entry)
     return out
 
 
-def confidence_hwd(vol_hwd, D, disp_right=None, measures=CONFIDENCE_MEASURES, out=None):
+def confidence_hwd(vol_hwd, D, disp_right=None, measures=CONFIDENCE_MEASURES, out=None, view="left"):
     """Confidence planes [K,H,W] of a pixel-major left volume [H,W,Dp], in the order of CONFIDENCE_MEASURES; disp_right:
-    the right winner-take-all map (needed by "lrc" only)."""
+    the right winner-take-all map (needed by "lrc" only).  view="right": the RIGHT view's planes - of a pixel-major
+    right volume and the LEFT winner-take-all map ("lrc" looks it up at column w + d1)."""
     H, W, Dp = vol_hwd.shape
     assert Dp == hwd_pitch(D)
-    return _confidence("mccnn_confidence_hwd", vol_hwd, D, H, W, disp_right, measures, out)
+    return _confidence("mccnn_confidence%s_hwd" % _view_suffix(view), vol_hwd, D, H, W, disp_right, measures, out)
 
 
-def confidence(vol_dhw, disp_right=None, measures=CONFIDENCE_MEASURES, out=None):
+def confidence(vol_dhw, disp_right=None, measures=CONFIDENCE_MEASURES, out=None, view="left"):
     """confidence_hwd() on a plane-major volume [D,H,W]: the same bits."""
     D, H, W = vol_dhw.shape
-    return _confidence("mccnn_confidence", vol_dhw, D, H, W, disp_right, measures, out)
+    return _confidence("mccnn_confidence" + _view_suffix(view), vol_dhw, D, H, W, disp_right, measures, out)
+
+
+def confidence_any(vol, D, pixel_major, disp_other=None, measures=CONFIDENCE_MEASURES, out=None, view="left"):
+    """confidence_hwd() or confidence(), as the volume's layout asks."""
+    if pixel_major:
+        return confidence_hwd(vol, D, disp_other, measures, out=out, view=view)
+    return confidence(vol, disp_other, measures, out=out, view=view)
 
 
 def confidence_right_hwd(vol_right_hwd, D, disp_left=None, measures=CONFIDENCE_MEASURES, out=None):
-    """confidence_hwd() for the RIGHT view: planes [K,H,W] of a pixel-major right volume; disp_left: the left
-    winner-take-all map ("lrc" only, looked up at column w + d1)."""
-    H, W, Dp = vol_right_hwd.shape
-    assert Dp == hwd_pitch(D)
-    return _confidence("mccnn_confidence_right_hwd", vol_right_hwd, D, H, W, disp_left, measures, out)
+    """confidence_hwd(view="right")."""
+    return confidence_hwd(vol_right_hwd, D, disp_left, measures, out=out, view="right")
 
 
 def confidence_right(vol_right_dhw, disp_left=None, measures=CONFIDENCE_MEASURES, out=None):
-    """confidence_right_hwd() on a plane-major volume [D,H,W]: the same bits."""
-    D, H, W = vol_right_dhw.shape
-    return _confidence("mccnn_confidence_right", vol_right_dhw, D, H, W, disp_left, measures, out)
+    """confidence(view="right")."""
+    return confidence(vol_right_dhw, disp_left, measures, out=out, view="right")
 
 
-def lr_status(dl, dr, ndisp, out=None):
+def lr_status(dl, dr, ndisp, out=None, view="left"):
+    """The status of the map `dl` against the other view's `dr`; view="right" (mccnn_lr_status_right): `dl` is the right
+    map and `dr` the left one."""
+    entry = "mccnn_lr_status" + _view_suffix(view)
     H, W = dl.shape
     st = out if out is not None else torch.empty((H, W), dtype=torch.int32, device=dl.device)
-    hip.check(hip.load().mccnn_lr_status(hip.ptr(dl), hip.ptr(dr), H, W, int(ndisp), hip.ptr(st), hip.stream()),
-              "mccnn_lr_status")
+    hip.check(getattr(hip.load(), entry)(hip.ptr(dl), hip.ptr(dr), H, W, int(ndisp), hip.ptr(st), hip.stream()), entry)
     return st
 
 
 def lr_status_right(dr, dl, ndisp, out=None):
-    """lr_status() for the RIGHT view (mccnn_lr_status_right): the status of the right map `dr` against the left `dl`."""
-    H, W = dr.shape
-    st = out if out is not None else torch.empty((H, W), dtype=torch.int32, device=dr.device)
-    hip.check(hip.load().mccnn_lr_status_right(hip.ptr(dr), hip.ptr(dl), H, W, int(ndisp), hip.ptr(st), hip.stream()),
-              "mccnn_lr_status_right")
-    return st
+    """lr_status(view="right"): the status of the right map `dr` against the left `dl`."""
+    return lr_status(dr, dl, ndisp, out=out, view="right")
+
+
+def interpolate(dl, status, out=None, directions=4, occlusion_from_left=False, view="left"):
+    """directions / occlusion_from_left: the paper's rules the reference leaves out (pf:318, pf:361), opt-in.
+    view="right" (mccnn_interpolate_right): `dl` is the right map; occlusions are filled from the left, with
+    occlusion_from_left - mirrored - from the right; directions = 16 walks the mirrored ray set."""
+    H, W = dl.shape
+    out = out if out is not None else torch.empty_like(dl)
+    rules = (int(directions), 1 if occlusion_from_left else 0)
+    if _view_suffix(view):
+        entry = "mccnn_interpolate_right"
+    elif rules == (4, 0):
+        entry, rules = "mccnn_interpolate", ()      # the reference's rule: the entry without the two arguments
+    else:
+        entry = "mccnn_interpolate_ex"
+    hip.check(getattr(hip.load(), entry)(hip.ptr(dl), hip.ptr(status), H, W, *rules, hip.ptr(out), hip.stream()), entry)
+    return out
 
 
 def interpolate_right(dr, status, out=None, directions=4, occlusion_from_right=False):
-    """interpolate() for the RIGHT view (mccnn_interpolate_right): occlusions from the left, or - occlusion_from_right,
-    the mirror of the occlusion_from_left extra - from the right; directions = 16: the mirrored ray set."""
-    H, W = dr.shape
-    out = out if out is not None else torch.empty_like(dr)
-    hip.check(hip.load().mccnn_interpolate_right(hip.ptr(dr), hip.ptr(status), H, W, int(directions),
-                                                 1 if occlusion_from_right else 0, hip.ptr(out), hip.stream()),
-              "mccnn_interpolate_right")
-    return out
-
-
-def interpolate(dl, status, out=None, directions=4, occlusion_from_left=False):
-    """directions / occlusion_from_left: the paper's rules the reference leaves out (pf:318, pf:361), opt-in."""
-    H, W = dl.shape
-    out = out if out is not None else torch.empty_like(dl)
-    if int(directions) == 4 and not occlusion_from_left:
-        hip.check(hip.load().mccnn_interpolate(hip.ptr(dl), hip.ptr(status), H, W, hip.ptr(out), hip.stream()),
-                  "mccnn_interpolate")
-    else:
-        hip.check(hip.load().mccnn_interpolate_ex(hip.ptr(dl), hip.ptr(status), H, W, int(directions),
-                                                  1 if occlusion_from_left else 0, hip.ptr(out), hip.stream()),
-                  "mccnn_interpolate_ex")
-    return out
+    """interpolate(view="right"); occlusion_from_right: the mirror of the occlusion_from_left extra."""
+    return interpolate(dr, status, out=out, directions=directions, occlusion_from_left=occlusion_from_right, view="right")
 
 
 def subpixel(dl, vol, out=None, numpy1_promotion=False):
@@ -1271,6 +1285,13 @@ def subpixel(dl, vol, out=None, numpy1_promotion=False):
         hip.check(hip.load().mccnn_subpixel(hip.ptr(dl), hip.ptr(vol), D, H, W, hip.ptr(out), hip.stream()),
                   "mccnn_subpixel")
     return out
+
+
+def subpixel_any(dl, vol, D, pixel_major, out=None, numpy1_promotion=False):
+    """subpixel_hwd() or subpixel(), as the volume's layout asks."""
+    if pixel_major:
+        return subpixel_hwd(dl, vol, D, out=out, numpy1_promotion=numpy1_promotion)
+    return subpixel(dl, vol, out=out, numpy1_promotion=numpy1_promotion)
 
 
 def median(dl, fh, fw, out=None):
@@ -1330,6 +1351,11 @@ DECISION_AUTO = "kernel"
 
 
 VIEWS = ("left", "both")       # StereoMatcher(views=...): the left map alone, or [2,H,W] = left, right
+# What StereoMatcher._post_view runs on for one view.  name / suffix: the wrappers' view= and what the view's keep= keys and
+# timer entries carry (VIEW_SUFFIX); image, own / other (the view's and the other view's WTA map), volume (the view's
+# result volume): the inputs; status (None: a fresh tensor), maps (three planes: interp, subpixel, median), dst (the final
+# map) and planes (the confidence planes; None without measures): where the results go; stream: where it runs.
+PostView = collections.namedtuple("PostView", "name suffix image own other volume status maps dst planes stream")
 
 
 def check_envelope(H, W, D):
@@ -1700,9 +1726,9 @@ class StereoMatcher(object):
     def _sgm_hp(self):
         return [self.hp[k] for k in ("sgm_P1", "sgm_P2", "sgm_Q1", "sgm_Q2", "sgm_D", "sgm_V")]
 
-    def _wta_hwd(self, lh, rh, D, m, timer):
+    def _wta(self, lv, rv, D, pixel_major, m, timer):
         timer.start("wta")
-        dl, dr = wta_hwd(lh, D, out=m[0]), wta_hwd(rh, D, out=m[1])
+        dl, dr = wta_any(lv, D, pixel_major, out=m[0]), wta_any(rv, D, pixel_major, out=m[1])
         timer.stop()
         return dl, dr
 
@@ -1750,7 +1776,7 @@ class StereoMatcher(object):
         main_s.wait_stream(right_s)
         (lh, lt), (rh, rt) = ends
         if not fuse:
-            return self._wta_hwd(lh, rh, D, m, timer) + (lh, rh)
+            return self._wta(lh, rh, D, True, m, timer) + (lh, rh)
         # (the right result volume stays unwritten unless the right view's post-processing reads it)
         _prog_launch_wta((lh, lt, sups[0], progs[0]), (rh, rt, sups[1], progs[1]), D, dist, (m[0], m[1]), self.both,
                          timer)
@@ -1795,7 +1821,7 @@ class StereoMatcher(object):
         timer.span_stop("aggregation_2")
         if keep is not None:
             keep["cbca2"] = (hwd_to_dhw(lh, D), hwd_to_dhw(rh, D))
-        return ((m[0], m[1]) if fuse else self._wta_hwd(lh, rh, D, m, timer)) + (lh, rh)
+        return ((m[0], m[1]) if fuse else self._wta(lh, rh, D, True, m, timer)) + (lh, rh)
 
     def _aggregate_dhw(self, left, right, sups, n, timer):
         """One aggregation of both plane-major volumes: the separable kernel takes both views in one launch; the other
@@ -1848,128 +1874,42 @@ class StereoMatcher(object):
         (lcv, t1d), (rcv, t2d) = self._aggregate_dhw((lcv, t1d), (rcv, t2d), sups, hp["cbca_num_iterations2"], timer)
         if keep is not None:
             keep["cbca2"] = (lcv.clone(), rcv.clone())
-        timer.start("wta")
-        dl, dr = wta(lcv, out=m[0]), wta(rcv, out=m[1])
-        timer.stop()
-        return dl, dr, lcv, rcv
+        return self._wta(lcv, rcv, D, False, m, timer) + (lcv, rcv)
 
-    def _confidence(self, ws, D, dr, left_volume, pixel_major, timer, keep, out, static_out):
-        """The confidence planes of the pair, from the left result volume and the right WTA map: one launch on the
-        current stream, into the workspace buffer (or `out`); handed out by _post's rules for the map."""
-        if out is not None and (out.device != dr.device or not out.is_contiguous()):
-            raise ValueError("match: `confidence_out` must be a contiguous float32 [K,H,W] tensor on the images' device")
-        dst = out if out is not None else (ws["confidence"] if keep is None else None)
-        timer.start("confidence")
-        if pixel_major:
-            planes = confidence_hwd(left_volume, D, dr, self.confidence, out=dst)
-        else:
-            planes = confidence(left_volume, dr, self.confidence, out=dst)
-        timer.stop()
-        if keep is not None:
-            keep["confidence"] = planes
-            return planes
-        return planes if (static_out or out is not None) else planes.clone()
-
-    def _post(self, ws, L, D, dl, dr, left_volume, pixel_major, m, timer, keep, out, static_out):
-        """a8 .. a11 on the WTA maps and the left result volume (in the layout `pixel_major` says).  Per-pair maps live
-        in the workspace unless the caller keeps intermediates (tests): apart from the returned map (see `out`) a pair
-        then allocates nothing but the conv activations and never blocks the host."""
+    def _post_view(self, v, D, pixel_major, timer, keep):
+        """a8 .. a11 of one view (PostView) and, in a matcher with measures, its confidence launch, on the current
+        stream: the check and interpolation of `v.name`, then the view-agnostic kernels on the view's operands.  Nothing
+        is allocated but what the record leaves open (None) and nothing blocks."""
         hp, ex = self.hp, self.extras
-        if out is not None and (tuple(out.shape) != tuple(L.shape) or out.dtype != torch.float32 or not out.is_contiguous()
-                                or out.device != L.device):
-            raise ValueError("match: `out` must be a contiguous float32 [H,W] tensor on the images' device")
-        timer.start("post")
-        st = lr_status(dl, dr, D, out=ws["status"] if keep is None else None)
-        di = interpolate(dl, st, out=m[2], directions=ex["interpolation_directions"],
-                         occlusion_from_left=ex["occlusion_from_left"])
-        if pixel_major:
-            ds = subpixel_hwd(di, left_volume, D, out=m[3], numpy1_promotion=ex["numpy1_promotion"])
-        else:
-            ds = subpixel(di, left_volume, out=m[3], numpy1_promotion=ex["numpy1_promotion"])
-        dm = median(ds, 5, 5, out=m[4])
-        db = bilateral(L, dm, 5, 5, 0, hp["blur_sigma"], hp["blur_threshold"], out=out if out is not None else m[5])
+        timer.start("post" + v.suffix)
+        st = lr_status(v.own, v.other, D, out=v.status, view=v.name)
+        di = interpolate(v.own, st, out=v.maps[0], directions=ex["interpolation_directions"],
+                         occlusion_from_left=ex["occlusion_from_left"], view=v.name)
+        ds = subpixel_any(di, v.volume, D, pixel_major, out=v.maps[1], numpy1_promotion=ex["numpy1_promotion"])
+        dm = median(ds, 5, 5, out=v.maps[2])
+        db = bilateral(v.image, dm, 5, 5, 0, hp["blur_sigma"], hp["blur_threshold"], out=v.dst)
         timer.stop()
-        if keep is not None:
-            keep.update(wta=(dl, dr), status=st, interp=di, subpixel=ds, median=dm, bilateral=db)
-            return db
-        # the workspace map is overwritten by the next pair: hand out a copy unless the caller passed its own tensor
-        # or (match_graph) wants the static buffer
-        return db if (static_out or out is not None) else db.clone()
-
-    def _post_right(self, ws, R, D, dl, dr, right_volume, pixel_major, timer, keep, out, confidence_out):
-        """views="both": a8 .. a11 and the confidence planes of the RIGHT view, on the WTA maps, the right result volume
-        and the right image - the mirrored check and interpolation, then the view-agnostic kernels on the right view's
-        operands.  Writes the map into `out` [H,W] and the planes into `confidence_out` [K,H,W].  Without per-stage
-        timing the launches go to the matcher's right stream, forked from the current one here, so that they run beside
-        the left view's; returns that stream, which the caller joins - None under per-stage timing, where everything
-        stays on the current stream.  Nothing is allocated (but under `keep`) and nothing blocks."""
-        hp, ex = self.hp, self.extras
-        main_s = torch.cuda.current_stream()
-        fork = timer is _NO_TIMER
-        st = self._right_stream() if fork else main_s
-        if fork:
-            st.wait_stream(main_s)
-        mr = ws["maps_right"] if keep is None else torch.empty_like(ws["maps_right"])
-        with torch.cuda.stream(st):
-            timer.start("post_right")
-            status = lr_status_right(dr, dl, D, out=ws["status_right"] if keep is None else None)
-            di = interpolate_right(dr, status, out=mr[0], directions=ex["interpolation_directions"],
-                                   occlusion_from_right=ex["occlusion_from_left"])
-            if pixel_major:
-                ds = subpixel_hwd(di, right_volume, D, out=mr[1], numpy1_promotion=ex["numpy1_promotion"])
-            else:
-                ds = subpixel(di, right_volume, out=mr[1], numpy1_promotion=ex["numpy1_promotion"])
-            dm = median(ds, 5, 5, out=mr[2])
-            db = bilateral(R, dm, 5, 5, 0, hp["blur_sigma"], hp["blur_threshold"], out=out)
+        stages = dict(status=st, interp=di, subpixel=ds, median=dm, bilateral=db)
+        if self.confidence:
+            timer.start("confidence" + v.suffix)
+            stages["confidence"] = confidence_any(v.volume, D, pixel_major, v.other, self.confidence, out=v.planes,
+                                                  view=v.name)
             timer.stop()
-            planes = None
-            if self.confidence:
-                timer.start("confidence_right")
-                if pixel_major:
-                    planes = confidence_right_hwd(right_volume, D, dl, self.confidence, out=confidence_out)
-                else:
-                    planes = confidence_right(right_volume, dl, self.confidence, out=confidence_out)
-                timer.stop()
         if keep is not None:
-            keep.update(status_right=status, interp_right=di, subpixel_right=ds, median_right=dm, bilateral_right=db,
-                        cbca2_right=hwd_to_dhw(right_volume, D) if pixel_major else right_volume.clone())
-            if planes is not None:
-                keep["confidence_right"] = planes
-        return st if fork else None
+            keep.update((name + v.suffix, t) for name, t in stages.items())
 
-    def _match_both(self, ws, L, R, D, dl, dr, volumes, m, timer, keep, out, confidence_out, static_out):
-        """views="both": the two views' post-processing into one [2,H,W] tensor (and [2,K,H,W] planes) - the workspace's,
-        the caller's `out` / `confidence_out`, or under `keep` fresh ones; handed out by _post's rules."""
-        H, W = L.shape
-        k = len(self.confidence)
-        if out is not None and (tuple(out.shape) != (2, H, W) or out.dtype != torch.float32 or not out.is_contiguous()
-                                or out.device != L.device):
-            raise ValueError("match: with views='both' `out` must be a contiguous float32 [2,H,W] tensor on the images' "
-                             "device")
-        if confidence_out is not None and (tuple(confidence_out.shape) != (2, k, H, W) or confidence_out.dtype != torch.float32
-                                           or not confidence_out.is_contiguous() or confidence_out.device != L.device):
-            raise ValueError("match: with views='both' `confidence_out` must be a contiguous float32 [2,K,H,W] tensor on "
-                             "the images' device")
-        pair = out if out is not None else (ws["both"] if keep is None else torch.empty_like(ws["both"]))
-        planes = None
-        if k:
-            planes = confidence_out if confidence_out is not None else (
-                ws["confidence"] if keep is None else torch.empty_like(ws["confidence"]))
-        pm = self.pixel_major()
-        # (the right view first: its launches are queued on the right stream and run beside the left view's, which
-        # follow on the current one; the two join in front of nothing but the hand-out)
-        main_s = torch.cuda.current_stream()
-        right_s = self._post_right(ws, R, D, dl, dr, volumes[1], pm, timer, keep, pair[1], planes[1] if k else None)
-        self._post(ws, L, D, dl, dr, volumes[0], pm, m, timer, keep, pair[0], True)
-        if k:
-            self._confidence(ws, D, dr, volumes[0], pm, timer, keep, planes[0], True)
-        if right_s is not None:
-            main_s.wait_stream(right_s)
-        handed = static_out or keep is not None
-        res = pair if (handed or out is not None) else pair.clone()
-        if not k:
-            return res
-        return res, (planes if (handed or confidence_out is not None) else planes.clone())
+    def _check_given(self, t, shape, name, dims, like):
+        """Refuses a caller's `out` / `confidence_out` that the last kernel of a view could not write."""
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous()
+                              or t.device != like.device):
+            raise ValueError("match: %s`%s` must be a contiguous float32 [%s%s] tensor on the images' device" % (
+                "with views='both' " if self.both else "", name, "2," if self.both else "", dims))
+
+    @staticmethod
+    def _hand_out(t, given, handed):
+        """The hand-out rule of every result.  The workspace tensor is overwritten by the next pair: the caller gets a copy
+        unless the tensor is its own (`given`) or `handed`: a fresh one (keep=) or the static buffer (match_graph)."""
+        return t if (handed or given is not None) else t.clone()
 
     def _match(self, left_image, right_image, ndisp, timer=_NO_TIMER, keep=None, _static_out=False, out=None,
                confidence_out=None):
@@ -2032,13 +1972,47 @@ class StereoMatcher(object):
         else:
             dl, dr, left_volume, right_volume = self._plane_major(ws, L, R, D, (lv, dhw[2]), (rv, dhw[3]), hwd, sups, m,
                                                                   timer, keep)
-        if self.both:
-            return self._match_both(ws, L, R, D, dl, dr, (left_volume, right_volume), m, timer, keep, out,
-                                    confidence_out, _static_out)
-        res = self._post(ws, L, D, dl, dr, left_volume, self.pixel_major(), m, timer, keep, out, _static_out)
-        if not self.confidence:
-            return res
-        return res, self._confidence(ws, D, dr, left_volume, self.pixel_major(), timer, keep, confidence_out, _static_out)
+
+        # a8 .. a11 and the confidence planes, view by view.  Per-pair maps live in the workspace unless the caller keeps
+        # intermediates (tests: fresh tensors then): apart from the returned map (see `out`) a pair allocates nothing but
+        # the conv activations and never blocks the host.  views="both": one [2,H,W] tensor (and [2,K,H,W] planes) takes
+        # the two views' results.
+        both, k, fresh, pm = self.both, len(self.confidence), keep is not None, self.pixel_major()
+        lead = (2,) if both else ()
+        self._check_given(out, lead + (H, W), "out", "H,W", L)
+        if k or both:                              # (a left-only matcher without measures never looks at confidence_out)
+            self._check_given(confidence_out, lead + (k, H, W), "confidence_out", "K,H,W", L)
+
+        def dest(given, spare):         # the caller's tensor, else the workspace's - under keep= a fresh one like it
+            return given if given is not None else (torch.empty_like(spare) if fresh else spare)
+        res = dest(out, ws["both"] if both else ws["maps"][5])
+        planes = dest(confidence_out, ws["confidence"]) if k else None
+        main_s = torch.cuda.current_stream()
+        fork = both and timer is _NO_TIMER
+        if both:
+            # The right view first: without per-stage timing its launches are queued on the matcher's right stream, forked
+            # from the current one here, and run beside the left view's, which follow on the current one; the two join in
+            # front of nothing but the hand-out.  Under per-stage timing everything stays on the current stream.
+            right_s = self._right_stream() if fork else main_s
+            if fork:
+                right_s.wait_stream(main_s)
+            view = PostView("right", "_right", R, dr, dl, right_volume, None if fresh else ws["status_right"],
+                            torch.empty_like(ws["maps_right"]) if fresh else ws["maps_right"], res[1],
+                            planes[1] if k else None, right_s)
+            with torch.cuda.stream(view.stream):
+                self._post_view(view, D, pm, timer, keep)
+            if fresh:
+                keep["cbca2_right"] = hwd_to_dhw(right_volume, D) if pm else right_volume.clone()
+        view = PostView("left", "", L, dl, dr, left_volume, None if fresh else ws["status"], m[2:5],
+                        res[0] if both else res, planes[0] if k and both else planes, main_s)
+        self._post_view(view, D, pm, timer, keep)
+        if fork:
+            main_s.wait_stream(right_s)
+        if fresh:
+            keep["wta"] = (dl, dr)
+        handed = _static_out or fresh
+        res = self._hand_out(res, out, handed)
+        return (res, self._hand_out(planes, confidence_out, handed)) if k else res
 
     def _ingest_buffers(self, H, W):
         """Static float32 inputs + ingest scratch of the eager byte path: kept per shape, so that a pair allocates

@@ -113,6 +113,31 @@ def test_whole_pairs_against_the_oracle(env, golden_cases, name):
         release(m, mc)
 
 
+@pytest.mark.parametrize("route", [dict(), dict(layout="plane_major")], ids=["default", "plane_major"])
+def test_both_views_under_per_stage_timing(env, golden_cases, route):
+    """views="both" with a StageTimer: the right view does not fork - its launches go to the current stream in front of
+    the left view's - and the maps and planes are the untimed call's, bit for bit."""
+    sd = env["sd"]
+    g = dict(golden_cases)["ref_24x32x8_s0.npz"]
+    D = g["cv_l"].shape[0]
+    case = _case(env, g["left"], g["right"], D)
+    m = sd.StereoMatcher(env["net"], views="both", confidence=ALL, on_saturation="raise", **route)
+    try:
+        want, want_planes = m.match(case.l, case.r, D)
+        right_stream = m._right                  # (the default route's aggregation may have made it; the fork has, too)
+        timer = sd.StageTimer(True)
+        got, planes = m.match(case.l, case.r, D, timer=timer)
+        assert_bits(host(got), host(want), "timed: maps")
+        assert_bits(host(planes), host(want_planes), "timed: planes")
+        torch.cuda.synchronize()
+        ms = timer.summary_ms()
+        for stage in ("post", "post_right", "confidence", "confidence_right"):
+            assert len(ms.get(stage, ())) == 1, "%s: %d records" % (stage, len(ms.get(stage, ())))
+        assert m._right is right_stream
+    finally:
+        release(m)
+
+
 # ---- every route ------------------------------------------------------------------------------------------------------
 WINDOW = (24, 750, 256)
 ROUTE_SHAPES = [WINDOW, (1, 4, 2), (1, 21, 19), (14, 20, 2), (29, 67, 65)]      # H = 1, D = 2, D = W - 2 of the grid
