@@ -566,6 +566,48 @@ int mccnn_evaluate(const float *disp, const float *gt, const uint8_t *mask /* ma
                    const float *thresholds /* HOST, n_thr values */, int n_thr, int accumulate,
                    mccnn_eval_t *result /* device */, void *scratch, size_t scratch_bytes, mccnn_stream_t stream);
 
+/* ---- exact error quantiles (Middlebury's A50, A90, A95, A99) of a map, and a list's pooled quantiles, on the device -----
+ * Regions, validity and error are those of mccnn_evaluate: `all` is the pixels whose gt is finite, `nonocc` those with
+ *   also mask == 255 (mask == NULL: nonocc equals all); an estimate is invalid when it is not finite or < 0 (-0.0f is
+ *   valid).  A SCORED pixel of a region is one in the region with a valid estimate.  Its error is err = fabsf(disp - gt):
+ *   one float32 subtraction, subnormals kept, +inf when the subtraction overflows; a NaN cannot occur.  Its KEY is the
+ *   uint32 bit pattern of err: for non-negative floats the key order is the value order, so "smallest" means smallest key.
+ * Quantiles.  A quantile is an integer q_ppm in 1 .. 1 000 000, parts per million: A90 is 900000.  For a region with n
+ *   scored pixels the rank is r = max(ceil(q_ppm * n / 10^6) - 1, 0), in exact 64-bit integer arithmetic
+ *   (q_ppm * n + 999999) / 1000000 - 1; the value is the key of rank r (0-based) among the region's scored pixels in
+ *   ascending order - the nearest-rank quantile, NumPy's method="inverted_cdf".  n == 0: the value is the canonical NaN
+ *   0x7fc00000 and the rank 0.  Ties need no rule: equal keys are equal values.  Repeated and unordered q_ppm are allowed.
+ * Pool.  A list's pooled quantiles come from a device-resident histogram pool[2][65536] of uint64, region then key >> 16,
+ *   which the caller zeroes once and every call that is given it adds its scored pixels to.  The pooled value of a
+ *   quantile is the float whose bits are bin << 16 for the bin that holds rank r of the pooled counts, NaN when the pool
+ *   is empty.  Truncation to the top 16 bits is monotone, so the pooled value is the top 16 bits of the exact pooled order
+ *   statistic: a relative resolution of 2^-7, still defined to the bit.
+ * mccnn_evaluate_quantiles.  result != NULL: the pair's exact quantiles overwrite it, entries k >= n_q written as rank 0
+ *   and value +0.0f.  pool != NULL: the pair's scored pixels are added to the pool.  Both may be given, with both NULL the
+ *   call is refused; the bits of result do not depend on whether pool is given.  q_ppm: HOST array of n_q values, read at
+ *   call time and passed to the kernels by value.  scratch: mccnn_evaluate_quantiles_scratch_bytes(H, W) bytes, 8-byte
+ *   aligned like result and pool, private to one call in flight; the call clears what it needs of it on the stream, so
+ *   calls may follow each other on one scratch.  A four-pass radix selection over the key's bytes: every pass reads disp,
+ *   gt and mask again, no error map is stored, the ranks are computed on the device.  Only integer atomics touch memory,
+ *   and integer sums commute: the same bits from every call and every replay of a captured graph.  No allocation, no
+ *   synchronisation: capturable.
+ * mccnn_evaluate_quantiles_pooled: the pooled values of the pool as it stands, n_scored the pool's total; one launch.
+ * Refused before any HIP call: null disp / gt / q_ppm / scratch (pooled: pool / q_ppm / result), result and pool both
+ *   NULL, non-positive sizes, n_q outside 1..8, a q_ppm outside 1..10^6, misaligned scratch / result / pool
+ *   (MCCNN_E_INVALID); scratch_bytes too small (MCCNN_E_SCRATCH); H*W above 2^32 - 1, the reach of the 32-bit bin counts
+ *   (MCCNN_E_UNSUPPORTED). */
+#define MCCNN_EVAL_MAX_QUANTILES 8
+typedef struct { uint64_t n_scored; uint64_t rank[MCCNN_EVAL_MAX_QUANTILES]; float value[MCCNN_EVAL_MAX_QUANTILES]; } mccnn_quantile_region_t; /* 104 bytes */
+typedef struct { mccnn_quantile_region_t all, nonocc; } mccnn_eval_quantiles_t;                                                              /* 208 bytes */
+#define MCCNN_EVAL_POOL_BYTES (2 * 65536 * 8)
+size_t mccnn_evaluate_quantiles_scratch_bytes(int H, int W); /* 0 for non-positive sizes */
+int mccnn_evaluate_quantiles(const float *disp, const float *gt, const uint8_t *mask /* may be NULL */, int H, int W,
+                             const uint32_t *q_ppm /* HOST, n_q values */, int n_q,
+                             mccnn_eval_quantiles_t *result /* device, may be NULL */, uint64_t *pool /* device, may be NULL */,
+                             void *scratch, size_t scratch_bytes, mccnn_stream_t stream);
+int mccnn_evaluate_quantiles_pooled(const uint64_t *pool, const uint32_t *q_ppm /* HOST */, int n_q,
+                                    mccnn_eval_quantiles_t *result /* device */, mccnn_stream_t stream);
+
 /* ---- KITTI 2012 / 2015: the development kit's file code, background interpolation and error rule, on the device ------
  * Written down from memory of the kit; THIS text is the binding definition.  Throughout, a disparity is
  * VALID when it is finite and >= 0: -0.0f is valid; -1, NaN and +-inf are not (the rule of mccnn_evaluate).  Device

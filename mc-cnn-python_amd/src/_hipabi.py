@@ -27,6 +27,8 @@ MCCNN_E_UNSUPPORTED = -2  # shape / parameter the kernels are not built for
 MCCNN_E_SCRATCH = -3      # scratch buffer too small
 
 MCCNN_EVAL_MAX_THRESHOLDS = 8
+MCCNN_EVAL_MAX_QUANTILES = 8
+MCCNN_EVAL_POOL_BYTES = 2 * 65536 * 8   # mccnn_evaluate_quantiles: pool[2][65536] of uint64
 MCCNN_CONF_MSM = 1        # mccnn_confidence / mccnn_confidence_hwd: -c1
 MCCNN_CONF_MMN = 2        # c2 - c1
 MCCNN_CONF_CUR = 4        # c[d1+1] - 2 c1 + c[d1-1]
@@ -114,6 +116,9 @@ SIGNATURES = {
     "mccnn_sample_patches": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "mccnn_evaluate_scratch_bytes": (_sz, [_i, _i]),
     "mccnn_evaluate": (_i, [_vp, _vp, _vp, _i, _i, ctypes.POINTER(_f), _i, _i, _vp, _vp, _sz, _vp]),
+    "mccnn_evaluate_quantiles_scratch_bytes": (_sz, [_i, _i]),
+    "mccnn_evaluate_quantiles": (_i, [_vp, _vp, _vp, _i, _i, ctypes.POINTER(ctypes.c_uint32), _i, _vp, _vp, _vp, _sz, _vp]),
+    "mccnn_evaluate_quantiles_pooled": (_i, [_vp, ctypes.POINTER(ctypes.c_uint32), _i, _vp, _vp]),
     "mccnn_kitti_encode_u16": (_i, [_vp, _i, _i, _vp, _vp]),
     "mccnn_kitti_decode_u16": (_i, [_vp, _i, _i, _vp, _vp]),
     "mccnn_kitti_interpolate_background": (_i, [_vp, _i, _i, _vp, _vp]),
@@ -134,6 +139,17 @@ class EvalRegion(ctypes.Structure):
 class EvalResult(ctypes.Structure):
     """mccnn_eval_t, 192 bytes: what mccnn_evaluate writes."""
     _fields_ = [("all", EvalRegion), ("nonocc", EvalRegion)]
+
+
+class QuantileRegion(ctypes.Structure):
+    """mccnn_quantile_region_t, 104 bytes.  value holds the keys: the uint32 bit patterns of the float32 quantiles."""
+    _fields_ = [("n_scored", ctypes.c_uint64), ("rank", ctypes.c_uint64 * MCCNN_EVAL_MAX_QUANTILES),
+                ("value", ctypes.c_uint32 * MCCNN_EVAL_MAX_QUANTILES)]
+
+
+class QuantileResult(ctypes.Structure):
+    """mccnn_eval_quantiles_t, 208 bytes: what mccnn_evaluate_quantiles and mccnn_evaluate_quantiles_pooled write."""
+    _fields_ = [("all", QuantileRegion), ("nonocc", QuantileRegion)]
 
 
 _lib = None

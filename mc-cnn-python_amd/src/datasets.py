@@ -107,9 +107,9 @@ class Middlebury(object):
         """match.py --confidence: the plane of `measure` beside disp0MCCNN.pfm (view 1, --views both: conf1MCCNN_*)."""
         return os.path.join(paths["res_dir"], "conf%dMCCNN_%s.pfm" % (int(view), measure))
 
-    def evaluator(self, thresholds, slots=1, interpolate=False, device=None):
+    def evaluator(self, thresholds, slots=1, interpolate=False, device=None, quantiles=None):
         import evaluation
-        return evaluation.Evaluator(device, thresholds, slots)
+        return evaluation.Evaluator(device, thresholds, slots, quantiles=quantiles)
 
     def device_output(self, disparity, scored=False):
         """(what crosses to the host for a map, the map an evaluation scores): both the map itself."""
@@ -201,9 +201,9 @@ class Kitti(object):
         stem = os.path.splitext(os.path.basename(paths["out"]))[0]
         return os.path.join(root, "conf_%s" % measure, stem + ".pfm")
 
-    def evaluator(self, thresholds, slots=1, interpolate=False, device=None):
+    def evaluator(self, thresholds, slots=1, interpolate=False, device=None, quantiles=None):
         import evaluation
-        return evaluation.KittiEvaluator(device, thresholds, slots, interpolate)
+        return evaluation.KittiEvaluator(device, thresholds, slots, interpolate, quantiles=quantiles)
 
     def device_output(self, disparity, scored=False):
         """(the 16-bit plane that crosses to the host and becomes the PNG, the map an evaluation scores: what that PNG

@@ -12,6 +12,11 @@ results and the running total of a list on the device until somebody asks for th
     avgerr  = sum_abs / (n_valid - n_invalid)               over the pixels that have a disparity
     rms     = sqrt(sum_sq / (n_valid - n_invalid))
 A figure whose denominator is zero is None (JSON null).
+
+On request (Evaluator(quantiles=...), match.py --eval_quantiles) also the error quantiles of the Middlebury tables
+(A50, A90, A95, A99, ...): per map the exact nearest-rank quantiles of the error over each region's scored pixels
+(stereo_device.evaluate_quantiles, csrc/evaluate_quantiles.hip), for a list the quantiles of a device-resident histogram
+of the error's top 16 bits.  A quantile of a region without scored pixels is None.
 """
 import ctypes
 import json
@@ -64,18 +69,91 @@ def threshold_tag(t):
     return repr(float(t))
 
 
+QUANTILE_RESULT_BYTES = 208      # sizeof(mccnn_eval_quantiles_t)
+MAX_QUANTILES = 8                # MCCNN_EVAL_MAX_QUANTILES
+POOLED_QUANTILE_BITS = 16        # a list's pooled quantiles: the top 16 bits of the exact ones (include/mccnn.h)
+
+
+def parse_quantiles(text):
+    """'50,90,95,99.5' -> (500000, 900000, 950000, 995000): quantiles in per cent as the parts per million that
+    mccnn_evaluate_quantiles takes, parsed exactly through decimal.  1 to 8 values, each with 0 < q <= 100 and at most
+    four decimals; repeats and any order are allowed."""
+    import decimal
+    items = [t.strip() for t in str(text).split(",") if t.strip()]
+    if not 1 <= len(items) <= MAX_QUANTILES:
+        raise ValueError("expected 1 to %d comma-separated quantiles, got %r" % (MAX_QUANTILES, text))
+    ppm = []
+    for item in items:
+        try:
+            q = decimal.Decimal(item)
+        except decimal.InvalidOperation:
+            raise ValueError("%r is not a number" % (item,))
+        if not q.is_finite() or not 0 < q <= 100:
+            raise ValueError("a quantile is in per cent, 0 < q <= 100, got %r" % (item,))
+        scaled = q * 10000
+        if scaled != scaled.to_integral_value():
+            raise ValueError("a quantile has at most four decimals (one part per million), got %r" % (item,))
+        ppm.append(int(scaled))
+    return tuple(ppm)
+
+
+def quantile_percent(ppm):
+    """Parts per million as the per cent a JSON file shows: 995000 -> 99.5."""
+    return int(ppm) / 10000.0
+
+
+def quantile_tag(ppm):
+    """The name of a quantile in the JSON files, Middlebury's: 500000 -> 'A50', 995000 -> 'A99.5'."""
+    import decimal
+    return "A" + format((decimal.Decimal(int(ppm)) / 10000).normalize(), "f")
+
+
+def quantile_raw(host_bytes, quantiles):
+    """The 208 bytes of a mccnn_eval_quantiles_t (bytes, a NumPy array or a host tensor of any dtype) ->
+    {region: dict(n_scored, quantile_rank=[...], values=[float or None, ...])}, one entry per quantile; a value is the
+    float32 the device selected, None for a region without scored pixels."""
+    from _hipabi import QuantileResult
+    if hasattr(host_bytes, "numpy"):
+        host_bytes = host_bytes.numpy()
+    data = np.ascontiguousarray(host_bytes).tobytes() if not isinstance(host_bytes, (bytes, bytearray)) else bytes(host_bytes)
+    if len(data) != QUANTILE_RESULT_BYTES or ctypes.sizeof(QuantileResult) != QUANTILE_RESULT_BYTES:
+        raise ValueError("a quantile result is %d bytes, got %d" % (QUANTILE_RESULT_BYTES, len(data)))
+    res = QuantileResult.from_buffer_copy(data)
+    n = len(tuple(quantiles))
+    out = {}
+    for name in REGIONS:
+        reg = getattr(res, name)
+        bits = np.array([reg.value[k] for k in range(n)], dtype=np.uint32)
+        scored = int(reg.n_scored)
+        out[name] = dict(n_scored=scored, quantile_rank=[int(reg.rank[k]) for k in range(n)],
+                         values=[float(v) if scored > 0 else None for v in bits.view(np.float32)])
+    return out
+
+
 class Metrics(object):
     """The figures of one mccnn_eval_t.  raw[region]: n_valid, n_invalid, n_bad (one per threshold), sum_abs, sum_sq -
-    exactly what the device wrote; figures[region]: bad (dict by threshold tag), invalid, avgerr, rms."""
+    exactly what the device wrote; figures[region]: bad (dict by threshold tag), invalid, avgerr, rms.
 
-    def __init__(self, raw, thresholds):
+    With `quantiles` (parts per million) and the quantile_raw() of a mccnn_eval_quantiles_t also
+    figures[region]["quantiles"] = {tag: value or None}, raw[region]["n_scored"] and raw[region]["quantile_rank"];
+    quantile_bits: what a pooled result says about its values' resolution.  Without them nothing is added."""
+
+    def __init__(self, raw, thresholds, quantiles=None, quantile_values=None, quantile_bits=None):
         self.thresholds = tuple(float(t) for t in thresholds)
+        self.quantiles = tuple(int(q) for q in quantiles) if quantiles else None
+        self.quantile_bits = quantile_bits if self.quantiles else None
         self.raw = raw
         self.figures = {r: self._figures(raw[r]) for r in REGIONS}
+        if self.quantiles:
+            for r in REGIONS:
+                self.raw[r] = dict(self.raw[r], n_scored=quantile_values[r]["n_scored"],
+                                   quantile_rank=list(quantile_values[r]["quantile_rank"]))
+                self.figures[r]["quantiles"] = {quantile_tag(q): v for q, v in zip(self.quantiles, quantile_values[r]["values"])}
 
     @classmethod
-    def from_result(cls, host_bytes, thresholds):
-        """host_bytes: the 192 bytes of a mccnn_eval_t (bytes, a NumPy array or a host tensor of any dtype)."""
+    def from_result(cls, host_bytes, thresholds, quantile_bytes=None, quantiles=None, quantile_bits=None):
+        """host_bytes: the 192 bytes of a mccnn_eval_t (bytes, a NumPy array or a host tensor of any dtype);
+        quantile_bytes: the 208 bytes of the map's mccnn_eval_quantiles_t for `quantiles`, or None."""
         from _hipabi import EvalResult
         if hasattr(host_bytes, "numpy"):
             host_bytes = host_bytes.numpy()
@@ -89,7 +167,9 @@ class Metrics(object):
             reg = getattr(res, name)
             raw[name] = dict(n_valid=int(reg.n_valid), n_invalid=int(reg.n_invalid), n_bad=[int(reg.n_bad[k]) for k in range(n)],
                              sum_abs=float(reg.sum_abs), sum_sq=float(reg.sum_sq))
-        return cls(raw, thresholds)
+        if quantile_bytes is None:
+            return cls(raw, thresholds)
+        return cls(raw, thresholds, quantiles, quantile_raw(quantile_bytes, quantiles), quantile_bits)
 
     def _figures(self, r):
         n_valid, scored = r["n_valid"], r["n_valid"] - r["n_invalid"]
@@ -108,12 +188,14 @@ class Metrics(object):
         round-trips, so the sums survive the file bit for bit)."""
         out = {r: self.figures[r] for r in REGIONS}
         out["raw"] = self.raw
+        if self.quantile_bits is not None:
+            out["quantile_bits"] = self.quantile_bits
         return out
 
 
 def mean_of(metrics):
     """Unweighted mean over pairs of every figure, per region; a pair whose figure is None does not count, and a figure
-    that no pair has is None."""
+    that no pair has is None.  Pairs that carry quantiles add "quantiles": each tag averaged over the pairs that have it."""
     def mean(values):
         values = [v for v in values if v is not None]
         return sum(values) / len(values) if values else None
@@ -125,7 +207,28 @@ def mean_of(metrics):
         out[r] = dict(bad={t: mean(f["bad"][t] for f in figs) for t in tags},
                       invalid=mean(f["invalid"] for f in figs), avgerr=mean(f["avgerr"] for f in figs),
                       rms=mean(f["rms"] for f in figs))
+        with_q = [f["quantiles"] for f in figs if "quantiles" in f]
+        if with_q:
+            out[r]["quantiles"] = {t: mean(q[t] for q in with_q if t in q) for t in with_q[0]}
     return out
+
+
+def error_quantiles(disp, gt, mask=None, quantiles=(50, 90, 95, 99)):
+    """NumPy in, dict out, computed on the device: disp, gt float32 [H,W], mask uint8 [H,W] or None, quantiles in per
+    cent -> {region: dict(n_scored, quantiles={tag: value or None}, quantile_rank=[...])}: the exact nearest-rank
+    quantiles of fabsf(disp - gt) over the region's scored pixels (include/mccnn.h: mccnn_evaluate_quantiles)."""
+    import torch
+    import stereo_device as sd
+    device = sd.hip.require_device()
+    ppm = parse_quantiles(",".join(str(q) for q in quantiles))
+
+    def dev(a, dtype):
+        return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(device)
+
+    res = sd.evaluate_quantiles(dev(disp, np.float32), dev(gt, np.float32), dev(mask, np.uint8), ppm)
+    raw = quantile_raw(res.cpu(), ppm)
+    return {r: dict(n_scored=raw[r]["n_scored"], quantile_rank=raw[r]["quantile_rank"],
+                    quantiles={quantile_tag(q): v for q, v in zip(ppm, raw[r]["values"])}) for r in REGIONS}
 
 
 def load_ground_truth(left_path, view="left"):
@@ -151,15 +254,17 @@ def check_shape(gt, map_shape, name):
 
 
 class PairScore(object):
-    """A pair's result on its way to the host: pinned bytes + the event behind the copy."""
+    """A pair's result on its way to the host: pinned bytes + the event behind the copy (with quantiles: the 208 bytes
+    of the pair's mccnn_eval_quantiles_t as well, behind the same event)."""
 
-    def __init__(self, host, done, thresholds):
+    def __init__(self, host, done, thresholds, quantile_host=None, quantiles=None):
         self.host, self.done, self.thresholds = host, done, thresholds
+        self.quantile_host, self.quantiles = quantile_host, quantiles
 
     def metrics(self):
         """Blocks until the bytes are on the host."""
         self.done.synchronize()
-        return Metrics.from_result(self.host, self.thresholds)
+        return Metrics.from_result(self.host, self.thresholds, self.quantile_host, self.quantiles)
 
 
 class Evaluator(object):
@@ -171,9 +276,14 @@ class Evaluator(object):
     Scratch is private to a call in flight, so every slot has its own (a slot = one stream: match.py's pairs in flight),
     and so has the total.  The total's sums depend on the order of the additions: commits run in the order they are
     enqueued, whichever streams they are enqueued on - each waits for the event of the one before.  A caller that may
-    discard a map (match.py's saturation redo) scores at once and commits only the map it keeps."""
+    discard a map (match.py's saturation redo) scores at once and commits only the map it keeps.
 
-    def __init__(self, device=None, thresholds=DEFAULT_THRESHOLDS, slots=1):
+    quantiles (parts per million, parse_quantiles' result): score() also enqueues one mccnn_evaluate_quantiles into the
+    slot's quantile result and the copy of its 208 bytes, commit() the pool-only call that adds the map's scored pixels
+    to the list's pool (integer counts: their order does not matter), report() the pooled selection.  None: not one
+    launch or buffer more."""
+
+    def __init__(self, device=None, thresholds=DEFAULT_THRESHOLDS, slots=1, quantiles=None):
         import torch
         import stereo_device as sd
         self.torch, self.sd = torch, sd
@@ -184,6 +294,19 @@ class Evaluator(object):
         self._slot = [dict(result=sd.evaluate_result(self.device), scratch=None) for _ in range(max(1, int(slots)))]
         self._total_scratch = []       # grown, never shrunk or freed: earlier commits may still be queued on other streams
         self._last_commit = None
+        self.quantiles = tuple(int(q) for q in quantiles) if quantiles else None
+        if self.quantiles:
+            # the selection's scratch does not depend on the map's size: one per slot, one for the commits (which run
+            # one behind the other)
+            for st in self._slot:
+                st.update(quantile_result=sd.evaluate_quantiles_result(self.device),
+                          quantile_scratch=sd.evaluate_quantiles_scratch(1, 1, self.device))
+            self.pool = sd.evaluate_quantiles_pool(self.device)
+            self._pool_scratch = sd.evaluate_quantiles_scratch(1, 1, self.device)
+
+    def describe(self):
+        """What the JSON files say beside the figures."""
+        return dict(quantiles=[quantile_percent(q) for q in self.quantiles]) if self.quantiles else {}
 
     # the three places that name the entry point (KittiEvaluator puts mccnn_evaluate_kitti there)
     def _scratch_bytes(self, H, W):
@@ -209,9 +332,14 @@ class Evaluator(object):
         self._evaluate(disp, gt, mask, out=st["result"], scratch=st["scratch"])
         host = torch.empty((RESULT_BYTES // 8,), dtype=torch.int64, pin_memory=True)
         host.copy_(st["result"], non_blocking=True)
+        quantile_host = None
+        if self.quantiles:
+            sd.evaluate_quantiles(disp, gt, mask, self.quantiles, out=st["quantile_result"], scratch=st["quantile_scratch"])
+            quantile_host = torch.empty((QUANTILE_RESULT_BYTES // 8,), dtype=torch.int64, pin_memory=True)
+            quantile_host.copy_(st["quantile_result"], non_blocking=True)
         done = torch.cuda.Event()
         done.record()
-        return PairScore(host, done, self.thresholds)
+        return PairScore(host, done, self.thresholds, quantile_host, self.quantiles)
 
     def commit(self, disp, gt, mask=None):
         torch, sd = self.torch, self.sd
@@ -222,6 +350,8 @@ class Evaluator(object):
         if not self._total_scratch or scratch is not self._total_scratch[-1]:
             self._total_scratch.append(scratch)
         self._evaluate(disp, gt, mask, out=self.total, accumulate=True, scratch=scratch)
+        if self.quantiles:
+            sd.evaluate_quantiles(disp, gt, mask, self.quantiles, out=False, pool=self.pool, scratch=self._pool_scratch)
         self._last_commit = torch.cuda.Event()
         self._last_commit.record(stream)
         self.pairs += 1
@@ -236,7 +366,10 @@ class Evaluator(object):
         """The pooled Metrics of everything committed so far (synchronises)."""
         if self._last_commit is not None:
             self._last_commit.synchronize()
-        return Metrics.from_result(self.total.cpu(), self.thresholds)
+        if not self.quantiles:
+            return Metrics.from_result(self.total.cpu(), self.thresholds)
+        pooled = self.sd.evaluate_quantiles_pooled(self.pool, self.quantiles)
+        return Metrics.from_result(self.total.cpu(), self.thresholds, pooled.cpu(), self.quantiles, POOLED_QUANTILE_BITS)
 
 
 class KittiEvaluator(Evaluator):
@@ -244,7 +377,10 @@ class KittiEvaluator(Evaluator):
     plane (or None) as the kit stores them, thresholds are (abs, rel) pairs, interpolate fills the pixels without a
     disparity as the kit does before they are scored.  Metrics names a figure by the abs part of its pair."""
 
-    def __init__(self, device=None, thresholds=((3.0, 0.05),), slots=1, interpolate=False):
+    def __init__(self, device=None, thresholds=((3.0, 0.05),), slots=1, interpolate=False, quantiles=None):
+        if quantiles:
+            raise ValueError("KittiEvaluator: KITTI's protocol has no error quantiles (and the 16-bit truth has no "
+                             "quantile entry point)")
         self.pairs_thresholds = tuple((float(a), float(r)) for a, r in thresholds)
         self.interpolate = bool(interpolate)
         Evaluator.__init__(self, device, tuple(a for a, _ in self.pairs_thresholds), slots)

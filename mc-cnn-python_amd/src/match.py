@@ -20,6 +20,8 @@ disp0MCCNN.pfm, in all three loops; with --evaluate their sparsification figures
 --views both writes the post-processed RIGHT disparity map as well: disp1MCCNN.pfm / .pgm beside the left files (and
 conf1MCCNN_<measure>.pfm with --confidence), in all three loops; with --evaluate it is scored against disp1GT.pfm (and
 mask1nocc.png) and every evaluation file gains a "right" block.  Middlebury layout only.
+--evaluate --eval_quantiles 50,90,95,99 adds the error quantiles (Middlebury's A50 ... A99) of every scored map, selected
+exactly on the device, and the list's pooled quantiles at 16 bits, in all three loops.  Middlebury layout only.
 Multi-GPU: launch one process per GPU with different -g / -s / -e, as the reference intends (match.py:17, 26-28),
 or use `torchrun --nproc-per-node N match.py ...`: rank r then takes the pairs i = r (mod N) of the window.
 """
@@ -133,6 +135,13 @@ parser.add_argument("--eval_thresholds", type=str, default=None,
                          "0.5,1,2,4).  With a KITTI --dataset every item is abs[:rel] - a pixel is bad when its error "
                          "exceeds abs pixels and rel times the true disparity - and the default is the data set's own: "
                          "3:0.05 (D1) for kitti2015, 2,3,4,5 for kitti2012")
+parser.add_argument("--eval_quantiles", type=str, default=None,
+                    help="with --evaluate: the error quantiles of every map in per cent, 1 to 8 comma-separated values in "
+                         "(0, 100] with at most four decimals, e.g. 50,90,95,99 for Middlebury's A50, A90, A95 and A99: the "
+                         "exact nearest-rank quantiles of the error over the scored pixels of each region, selected on the "
+                         "device (include/mccnn.h), \"quantiles\" in evalMCCNN.json and eval.json; the list's pooled "
+                         "quantiles carry the top 16 bits of the exact ones.  Not with a KITTI --dataset.  Without it "
+                         "every file keeps its bytes")
 parser.add_argument("--dataset", choices=datasets.NAMES, default="middlebury",
                     help="the layout of the input tree and the format of the results (src/datasets.py).  'middlebury': "
                          "im0.png / im1.png / calib.txt per directory, PFM out.  'kitti2015': the list names "
@@ -225,6 +234,17 @@ def main(argv=None):
         parser.error("--eval_auc_threshold: %s" % e)
     if args.eval_interpolate and not layout.kitti:
         parser.error("--eval_interpolate goes with a KITTI --dataset")
+    eval_quantiles = None
+    if args.eval_quantiles is not None:
+        if not args.evaluate:
+            parser.error("--eval_quantiles goes with --evaluate")
+        if layout.kitti:
+            parser.error("--eval_quantiles is not available with --dataset %s: the KITTI protocol has no error quantiles"
+                         % args.dataset)
+        try:
+            eval_quantiles = ev.parse_quantiles(args.eval_quantiles)
+        except ValueError as e:
+            parser.error("--eval_quantiles: %s" % e)
     both = args.views == "both"
     if both and layout.kitti:
         parser.error("--views both is not available with --dataset %s: the KITTI development kit has neither right-view "
@@ -313,8 +333,11 @@ def main(argv=None):
     streams = [torch.cuda.Stream() for _ in range(in_flight)] if in_flight > 1 else [None]
     # --evaluate: one result buffer and scratch per slot, the list's running total on the device (src/evaluation.py)
     # (--views both: a second evaluator of the same kind, whose total pools the right maps against disp1GT.pfm)
-    report = ev.ListReport(layout.evaluator(eval_thresholds, slots=in_flight, interpolate=args.eval_interpolate),
-                           layout.evaluator(eval_thresholds, slots=in_flight) if both else None) if args.evaluate else None
+    # (--eval_quantiles: both evaluators also select the error quantiles of every map and pool them over the list)
+    report = ev.ListReport(layout.evaluator(eval_thresholds, slots=in_flight, interpolate=args.eval_interpolate,
+                                            quantiles=eval_quantiles),
+                           layout.evaluator(eval_thresholds, slots=in_flight, quantiles=eval_quantiles) if both else None
+                           ) if args.evaluate else None
     evaluator = report.evaluator if report is not None else None
     evaluator_right = report.right_evaluator if report is not None else None
     # --evaluate --confidence: the sparsification figures of every scored pair, behind its evaluation on its stream

@@ -436,6 +436,99 @@ def evaluate(disp, gt, mask=None, thresholds=EVAL_THRESHOLDS, out=None, accumula
     return out
 
 
+# ---- exact error quantiles and a list's pooled quantiles (csrc/evaluate_quantiles.hip) --------------------------------
+EVAL_QUANTILES_BYTES = 208   # sizeof(mccnn_eval_quantiles_t)
+EVAL_QUANTILES_PPM = (500000, 900000, 950000, 990000)    # A50, A90, A95, A99
+
+
+def evaluate_quantiles_scratch(H, W, device):
+    """Scratch of one evaluate_quantiles() in flight (the selection's histograms and state):
+    mccnn_evaluate_quantiles_scratch_bytes(H, W) bytes."""
+    nbytes = int(hip.load().mccnn_evaluate_quantiles_scratch_bytes(H, W))
+    return torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=device)
+
+
+def evaluate_quantiles_result(device):
+    """A zeroed mccnn_eval_quantiles_t on the device: 208 bytes as 26 int64 words."""
+    return torch.zeros((EVAL_QUANTILES_BYTES // 8,), dtype=torch.int64, device=device)
+
+
+def evaluate_quantiles_pool(device):
+    """A zeroed pool on the device: the uint64 counts [2][65536] (region, key >> 16) as int64 words; a list's pooled
+    quantiles start here."""
+    return torch.zeros((2, 65536), dtype=torch.int64, device=device)
+
+
+def _quantiles_ppm(quantiles_ppm, who):
+    ppm = [int(q) for q in quantiles_ppm]
+    if not 1 <= len(ppm) <= hip.MCCNN_EVAL_MAX_QUANTILES:
+        raise ValueError("%s: %d quantiles, expected 1..%d" % (who, len(ppm), hip.MCCNN_EVAL_MAX_QUANTILES))
+    if any(not 1 <= q <= 1000000 for q in ppm):
+        raise ValueError("%s: quantiles are parts per million, 1..1000000, got %r" % (who, ppm))
+    return (ctypes.c_uint32 * len(ppm))(*ppm), len(ppm)
+
+
+def _quantiles_pool(pool, device, who):
+    if pool.dtype != torch.int64 or pool.numel() * 8 != hip.MCCNN_EVAL_POOL_BYTES or pool.device != device:
+        raise ValueError("%s: `pool` must be an evaluate_quantiles_pool() on the map's device" % who)
+
+
+def evaluate_quantiles(disp, gt, mask=None, quantiles_ppm=EVAL_QUANTILES_PPM, out=None, pool=None, scratch=None):
+    """disp, gt: float32 device maps [H,W]; mask: uint8 [H,W] or None (255 = non-occluded) -> the 208-byte device tensor
+    (26 int64 words) holding mccnn_eval_quantiles_t: per region n_scored, and for every quantile its rank and the exact
+    nearest-rank value of fabsf(disp - gt) over the scored pixels, defined to the bit in include/mccnn.h.  pool: an
+    evaluate_quantiles_pool() the map's scored pixels are added to.  out=False: only that - the pool-only call - and None
+    is returned.  The quantiles (parts per million) are read here, on the host, at call time - inside a captured graph
+    they are baked in.  No synchronisation; evaluation.quantile_raw reads the bytes once they are on the
+    host.  `scratch`: an evaluate_quantiles_scratch()."""
+    if disp.dim() != 2 or disp.dtype != torch.float32 or gt.dtype != torch.float32:
+        raise ValueError("evaluate_quantiles: expected float32 maps [H,W], got %s %s and %s %s"
+                         % (disp.dtype, tuple(disp.shape), gt.dtype, tuple(gt.shape)))
+    if tuple(gt.shape) != tuple(disp.shape):
+        raise ValueError("evaluate_quantiles: the map is %s, the ground truth %s" % (tuple(disp.shape), tuple(gt.shape)))
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(disp.shape)):
+        raise ValueError("evaluate_quantiles: expected a uint8 mask %s, got %s %s"
+                         % (tuple(disp.shape), mask.dtype, tuple(mask.shape)))
+    pool_only = out is False
+    for t in (gt, mask, None if pool_only else out, pool, scratch):
+        if t is not None and t.device != disp.device:
+            raise ValueError("evaluate_quantiles: every tensor must live on the map's device")
+    q, n_q = _quantiles_ppm(quantiles_ppm, "evaluate_quantiles")
+    H, W = disp.shape
+    if pool_only:
+        if pool is None:
+            raise ValueError("evaluate_quantiles: out=False needs the `pool` to add to")
+        out = None
+    elif out is None:
+        out = torch.empty((EVAL_QUANTILES_BYTES // 8,), dtype=torch.int64, device=disp.device)
+    elif out.numel() * out.element_size() != EVAL_QUANTILES_BYTES:
+        raise ValueError("evaluate_quantiles: `out` must hold %d bytes" % EVAL_QUANTILES_BYTES)
+    if pool is not None:
+        _quantiles_pool(pool, disp.device, "evaluate_quantiles")
+    scratch = scratch if scratch is not None else evaluate_quantiles_scratch(H, W, disp.device)
+    hip.check(hip.load().mccnn_evaluate_quantiles(hip.ptr(disp), hip.ptr(gt), hip.ptr(mask) if mask is not None else None,
+                                                  H, W, q, n_q, hip.ptr(out) if out is not None else None,
+                                                  hip.ptr(pool) if pool is not None else None, hip.ptr(scratch),
+                                                  scratch.numel() * scratch.element_size(), hip.stream()),
+              "mccnn_evaluate_quantiles")
+    return out
+
+
+def evaluate_quantiles_pooled(pool, quantiles_ppm=EVAL_QUANTILES_PPM, out=None):
+    """pool: an evaluate_quantiles_pool() -> the 208-byte device tensor of evaluate_quantiles() with the pooled values of
+    the pool as it stands: the top 16 bits of the exact pooled order statistics (include/mccnn.h).  One launch, no
+    synchronisation."""
+    _quantiles_pool(pool, pool.device, "evaluate_quantiles_pooled")
+    q, n_q = _quantiles_ppm(quantiles_ppm, "evaluate_quantiles_pooled")
+    if out is None:
+        out = torch.empty((EVAL_QUANTILES_BYTES // 8,), dtype=torch.int64, device=pool.device)
+    elif out.numel() * out.element_size() != EVAL_QUANTILES_BYTES or out.device != pool.device:
+        raise ValueError("evaluate_quantiles_pooled: `out` must hold %d bytes on the pool's device" % EVAL_QUANTILES_BYTES)
+    hip.check(hip.load().mccnn_evaluate_quantiles_pooled(hip.ptr(pool), q, n_q, hip.ptr(out), hip.stream()),
+              "mccnn_evaluate_quantiles_pooled")
+    return out
+
+
 # ---- KITTI: the kit's 16-bit code, background interpolation and error rule (csrc/kitti.hip) ---------------------------
 def _kitti_map(disp, who):
     if disp.dim() != 2 or disp.dtype != torch.float32:
