@@ -108,14 +108,19 @@ def quantile_tag(ppm):
     return "A" + format((decimal.Decimal(int(ppm)) / 10000).normalize(), "f")
 
 
+def _host_bytes(host_bytes):
+    """A device result on the host (bytes, a NumPy array or a host tensor of any dtype) as bytes."""
+    if hasattr(host_bytes, "numpy"):
+        host_bytes = host_bytes.numpy()
+    return bytes(host_bytes) if isinstance(host_bytes, (bytes, bytearray)) else np.ascontiguousarray(host_bytes).tobytes()
+
+
 def quantile_raw(host_bytes, quantiles):
     """The 208 bytes of a mccnn_eval_quantiles_t (bytes, a NumPy array or a host tensor of any dtype) ->
     {region: dict(n_scored, quantile_rank=[...], values=[float or None, ...])}, one entry per quantile; a value is the
     float32 the device selected, None for a region without scored pixels."""
     from _hipabi import QuantileResult
-    if hasattr(host_bytes, "numpy"):
-        host_bytes = host_bytes.numpy()
-    data = np.ascontiguousarray(host_bytes).tobytes() if not isinstance(host_bytes, (bytes, bytearray)) else bytes(host_bytes)
+    data = _host_bytes(host_bytes)
     if len(data) != QUANTILE_RESULT_BYTES or ctypes.sizeof(QuantileResult) != QUANTILE_RESULT_BYTES:
         raise ValueError("a quantile result is %d bytes, got %d" % (QUANTILE_RESULT_BYTES, len(data)))
     res = QuantileResult.from_buffer_copy(data)
@@ -155,9 +160,7 @@ class Metrics(object):
         """host_bytes: the 192 bytes of a mccnn_eval_t (bytes, a NumPy array or a host tensor of any dtype);
         quantile_bytes: the 208 bytes of the map's mccnn_eval_quantiles_t for `quantiles`, or None."""
         from _hipabi import EvalResult
-        if hasattr(host_bytes, "numpy"):
-            host_bytes = host_bytes.numpy()
-        data = np.ascontiguousarray(host_bytes).tobytes() if not isinstance(host_bytes, (bytes, bytearray)) else bytes(host_bytes)
+        data = _host_bytes(host_bytes)
         if len(data) != RESULT_BYTES or ctypes.sizeof(EvalResult) != RESULT_BYTES:
             raise ValueError("a result is %d bytes, got %d" % (RESULT_BYTES, len(data)))
         res = EvalResult.from_buffer_copy(data)
@@ -193,13 +196,15 @@ class Metrics(object):
         return out
 
 
+def mean(values):
+    """The mean of the values that are not None; None where there is none."""
+    values = [v for v in values if v is not None]
+    return sum(values) / len(values) if values else None
+
+
 def mean_of(metrics):
     """Unweighted mean over pairs of every figure, per region; a pair whose figure is None does not count, and a figure
     that no pair has is None.  Pairs that carry quantiles add "quantiles": each tag averaged over the pairs that have it."""
-    def mean(values):
-        values = [v for v in values if v is not None]
-        return sum(values) / len(values) if values else None
-
     out = {}
     for r in REGIONS:
         figs = [m.figures[r] for m in metrics]
@@ -513,10 +518,6 @@ class Sparsifier(object):
 def mean_sparsification(figures):
     """Unweighted mean over the scored pairs of bad_rate, auc_optimal and every measure's auc; a pair whose figure is
     None (an empty region) does not count."""
-    def mean(values):
-        values = [v for v in values if v is not None]
-        return sum(values) / len(values) if values else None
-
     names = list(figures[0]["auc"]) if figures else []
     return dict(threshold=figures[0]["threshold"] if figures else None, pairs=len(figures),
                 bad_rate=mean(f["bad_rate"] for f in figures), auc_optimal=mean(f["auc_optimal"] for f in figures),
@@ -529,75 +530,134 @@ def write_json(path, obj):
         f.write("\n")
 
 
+class _ViewBook(object):
+    """One view's part of a ListReport: the scored maps by list index, the pairs skipped for this view, and the
+    evaluator whose device total pools the view over the list."""
+
+    def __init__(self, evaluator):
+        self.evaluator = evaluator
+        self.scored = {}         # index -> (Metrics, the map's sparsification figures or None: match.py --confidence)
+        self.skipped = {}        # index -> name
+
+    def block(self, index):
+        """The view's fields in a pair's entry: the metrics, with --confidence also "sparsification" (without it no
+        such key, so that the files keep their bytes).  None for a pair whose map of this view was not scored."""
+        if index not in self.scored:
+            return None
+        metrics, figures = self.scored[index]
+        return dict(metrics.to_dict(), **(dict(sparsification=figures) if figures is not None else {}))
+
+    def totals(self):
+        """The view's fields in the list's file: the device total, the means over the scored pairs, the skipped."""
+        order = sorted(self.scored)
+        means = mean_of([self.scored[i][0] for i in order])
+        figures = [self.scored[i][1] for i in order if self.scored[i][1] is not None]
+        if figures:
+            means["sparsification"] = mean_sparsification(figures)
+        return dict(pooled=self.evaluator.report().to_dict(), mean=means,
+                    skipped=[self.skipped[i] for i in sorted(self.skipped)])
+
+
 class ListReport(object):
     """What match.py --evaluate collects over a list: per-pair metrics by list index (set by the thread that writes the
-    pair's files), the skipped pairs, and at the end the file with the pooled totals of the device accumulator."""
+    pair's files), the skipped pairs, and at the end the file with the pooled totals of the device accumulator.
+
+    One book per view.  The right one (match.py --views both) has a second evaluator, whose total pools the RIGHT maps
+    against disp1GT.pfm; a pair's right view is scored where its left view is and it has that file, and listed as skipped
+    for the right view otherwise.  Without a right evaluator no file has a "right" key."""
 
     def __init__(self, evaluator, right_evaluator=None):
-        self.evaluator = evaluator
+        self.evaluator, self.right_evaluator = evaluator, right_evaluator
         self.extra = evaluator.describe() if hasattr(evaluator, "describe") else {}     # more keys in every file
-        self.pairs = {}          # index -> (name, Metrics)
-        self.skipped = {}        # index -> name
-        self.sparsification = {} # index -> the pair's sparsification figures (match.py --confidence only)
-        # match.py --views both: a second evaluator, whose total pools the RIGHT maps against disp1GT.pfm; a pair's right
-        # view is scored where its left view is and it has that file, and listed as skipped for the right view otherwise
-        self.right_evaluator = right_evaluator
-        self.right = {}          # index -> dict(metrics=Metrics[, sparsification=figures])
-        self.right_skipped = {}  # index -> name
+        self.left, self.right = _ViewBook(evaluator), _ViewBook(right_evaluator)
+        self.names = {}          # index -> name, of the pairs whose left map was scored
 
-    def _right_block(self, index):
-        """The "right" entry of a pair: the fields of the left block for the right map; none without --views both or
-        without right-view ground truth, so that the files keep their bytes."""
-        r = self.right.get(index)
-        if r is None:
-            return {}
-        block = r["metrics"].to_dict()
-        if r.get("sparsification") is not None:
-            block["sparsification"] = r["sparsification"]
-        return dict(right=block)
-
-    def _pair_extra(self, index):
-        """The keys a pair's entry gains with --confidence; none without it, so that the files keep their bytes."""
-        return dict(sparsification=self.sparsification[index]) if index in self.sparsification else {}
+    def _entry(self, index):
+        right = self.right.block(index)
+        return dict(self.left.block(index), pair=self.names[index], **(dict(right=right) if right is not None else {}))
 
     def pair(self, index, name, metrics, path=None, sparsification=None, right=None):
-        self.pairs[index] = (name, metrics)
+        """right: None or dict(metrics=Metrics, sparsification=figures or None).  A second call replaces the first."""
+        self.names[index] = name
+        self.left.scored[index] = (metrics, sparsification)
         if right is not None:
-            self.right[index] = right
+            self.right.scored[index] = (right["metrics"], right.get("sparsification"))
         else:
-            self.right.pop(index, None)
-        if sparsification is not None:
-            self.sparsification[index] = sparsification
-        else:
-            self.sparsification.pop(index, None)
+            self.right.scored.pop(index, None)
         if path is not None:
-            write_json(path, dict(metrics.to_dict(), pair=name, thresholds=list(metrics.thresholds), **self.extra,
-                                  **self._pair_extra(index), **self._right_block(index)))
+            write_json(path, dict(self._entry(index), thresholds=list(metrics.thresholds), **self.extra))
 
     def skip(self, index, name):
-        self.skipped[index] = name
+        self.left.skipped[index] = name
 
     def skip_right(self, index, name):
-        self.right_skipped[index] = name
+        self.right.skipped[index] = name
 
     def write(self, path):
-        order = sorted(self.pairs)
-        metrics = [self.pairs[i][1] for i in order]
-        mean = mean_of(metrics)
-        if self.sparsification:
-            mean["sparsification"] = mean_sparsification([self.sparsification[i] for i in order if i in self.sparsification])
-        right = {}
-        if self.right_evaluator is not None:
-            scored = [i for i in order if i in self.right]
-            right_mean = mean_of([self.right[i]["metrics"] for i in scored])
-            figures = [self.right[i]["sparsification"] for i in scored if self.right[i].get("sparsification") is not None]
-            if figures:
-                right_mean["sparsification"] = mean_sparsification(figures)
-            right = dict(right=dict(pooled=self.right_evaluator.report().to_dict(), mean=right_mean,
-                                    skipped=[self.right_skipped[i] for i in sorted(self.right_skipped)]))
-        write_json(path, dict(thresholds=list(self.evaluator.thresholds),
-                              pairs=[dict(self.pairs[i][1].to_dict(), pair=self.pairs[i][0], index=i, **self._pair_extra(i),
-                                          **self._right_block(i))
-                                     for i in order],
-                              pooled=self.evaluator.report().to_dict(), mean=mean,
-                              skipped=[self.skipped[i] for i in sorted(self.skipped)], **self.extra, **right))
+        right = dict(right=self.right.totals()) if self.right_evaluator is not None else {}
+        write_json(path, dict(self.left.totals(), thresholds=list(self.evaluator.thresholds),
+                              pairs=[dict(self._entry(i), index=i) for i in sorted(self.names)], **self.extra, **right))
+
+
+class Scored(object):
+    """A pair on its way through a ListScorer: which pair, the device ground truth (gt, mask or None) of every view that
+    is scored (left first), and per view the (PairScore, SparsificationScore or None) of the maps kept so far."""
+
+    def __init__(self, index, name, truths):
+        self.index, self.name, self.truths, self.scores = index, name, truths, None
+
+
+class ListScorer(object):
+    """match.py --evaluate, for every loop over a list: which views of a pair are scored, in which order the calls are
+    enqueued, what the running totals take and what the report is told.
+
+        scored = scorer.begin(index, name, truth, truth_right)    None: no ground truth, the pair is listed as skipped
+        scorer.score(scored, maps, planes, slot)                  behind the maps on the pair's stream; again with the
+                                                                  maps of a repeated pair (the saturation redo)
+        scorer.commit(scored, maps)                               once, in list order, with the maps that are kept
+        scorer.publish(scored, json_path)                         by whoever writes the pair's files
+
+    score() and commit() enqueue on the current stream and never block the host; publish() waits for the scores' own
+    events.  views="both": maps are [2,H,W] and planes [2,K,H,W], and the report's right evaluator scores the right map
+    of a pair with right-view ground truth.  sparsifier (--confidence): scores a map's planes behind its evaluation."""
+
+    def __init__(self, report, sparsifier=None, views="left"):
+        self.report, self.sparsifier, self.both = report, sparsifier, views == "both"
+        self.evaluators = (report.evaluator, report.right_evaluator)
+
+    def begin(self, index, name, truth, truth_right=None):
+        """truth, truth_right: (gt, mask or None) on the device, or None.  The right view is scored where the left one
+        is: right-view ground truth without the left view's is ignored."""
+        if truth is None or not self.both:
+            truth_right = None
+        if truth is None:
+            self.report.skip(index, name)
+        if self.both and truth_right is None:
+            self.report.skip_right(index, name)
+        if truth is None:
+            return None
+        return Scored(index, name, [truth] if truth_right is None else [truth, truth_right])
+
+    def _views(self, scored, maps, planes=None):
+        """(evaluator, map, planes, gt, mask) of every view of the pair that is scored, the left one first."""
+        for v, (gt, mask) in enumerate(scored.truths):
+            yield (self.evaluators[v], maps[v] if self.both else maps,
+                   planes[v] if (self.both and planes is not None) else planes, gt, mask)
+
+    def score(self, scored, maps, planes, slot):
+        """Per view the evaluation, then (--confidence) the sparsification; replaces what the record holds."""
+        scored.scores = [(e.score(m, gt, mask, slot), self.sparsifier.score(m, p, gt) if self.sparsifier is not None else None)
+                         for e, m, p, gt, mask in self._views(scored, maps, planes)]
+
+    def commit(self, scored, maps):
+        """The maps that are kept into the running totals (Evaluator.commit keeps the commits in call order)."""
+        for e, m, _, gt, mask in self._views(scored, maps):
+            e.commit(m, gt, mask)
+
+    def publish(self, scored, json_path):
+        """The pair's entry of the report and its evalMCCNN.json, from the scores the record holds now."""
+        views = [dict(metrics=s.metrics(), sparsification=a.figures() if a is not None else None) for s, a in scored.scores]
+        self.report.pair(scored.index, scored.name, views[0]["metrics"], json_path,
+                         sparsification=views[0]["sparsification"], right=views[1] if len(views) > 1 else None)
+
+

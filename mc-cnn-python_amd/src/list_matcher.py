@@ -233,20 +233,17 @@ def make_reader(paths, check_shape, to_host_buffer=pinned_u8, truth=None, shape=
                                                                  "its calib.txt" if shape is None else "the left view",
                                                                  width, height))
         channels = 1 if left.ndim == 2 else left.shape[2]
-        gt = mask = None
-        found = truth(p["left"]) if truth is not None else None
-        if found is not None:
+        def pinned_truth(load, what):
+            found = load(p["left"]) if load is not None else None
+            if found is None:
+                return None, None
             if found[0].shape != (height, width):
-                raise ValueError("%s: the ground truth is %s, the disparity map %s (resampling is not supported)"
-                                 % (p["left"], found[0].shape, (height, width)))
-            gt, mask = pinned(found[0]), (pinned(found[1]) if found[1] is not None else None)
-        gt_right = mask_right = None
-        found = truth_right(p["left"]) if truth_right is not None else None
-        if found is not None:
-            if found[0].shape != (height, width):
-                raise ValueError("%s: the right view's ground truth is %s, the disparity map %s (resampling is not "
-                                 "supported)" % (p["left"], found[0].shape, (height, width)))
-            gt_right, mask_right = pinned(found[0]), (pinned(found[1]) if found[1] is not None else None)
+                raise ValueError("%s: the %s is %s, the disparity map %s (resampling is not supported)"
+                                 % (p["left"], what, found[0].shape, (height, width)))
+            return pinned(found[0]), (pinned(found[1]) if found[1] is not None else None)
+
+        gt, mask = pinned_truth(truth, "ground truth")
+        gt_right, mask_right = pinned_truth(truth_right, "right view's ground truth")
         return Job(index, p["left"], (height, width, ndisp, channels), height=height, width=width, ndisp=ndisp,
                    left=to_host_buffer(left), right=to_host_buffer(right), paths=p, gt=gt, mask=mask, gt_right=gt_right,
                    mask_right=mask_right)
@@ -258,82 +255,61 @@ def _save_middlebury(disparity, p):
     util.writePfm(disparity, p["out"])
 
 
-def make_writer(rank=0, log=print, report=None, eval_file="evalMCCNN.json", save=_save_middlebury, save_confidence=None):
-    """write(job, map, seconds) for ListPipeline: the three files of match.py, with the existing util functions; with a
-    `report` (evaluation.ListReport) also the pair's evaluation, once its 192 bytes are on the host.  `save(result,
-    paths)` writes the map and its preview (datasets.py: a KITTI layout's result is the 16-bit plane);
-    with match.py --confidence the backend's result is the pair (map, planes) of one ticket - a repeated pair's files get
-    the repeated pair's planes - and `save_confidence(planes, paths)` writes the planes.  With --views both the map is
-    [2,H,W] and the planes [2,K,H,W] (`save` / `save_confidence` know), and a right view that was scored (job.score_right)
-    joins the pair's evaluation as its "right" block."""
+def map_and_planes(result):
+    """What a matcher returns, as (map, planes or None): one with confidence measures returns the pair (match.py
+    --confidence).  With --views both the map is [2,H,W] and the planes [2,K,H,W]."""
+    return result if isinstance(result, tuple) else (result, None)
+
+
+def make_writer(rank=0, log=print, scorer=None, eval_file="evalMCCNN.json", save=_save_middlebury, save_confidence=None):
+    """write(job, result, seconds) for ListPipeline: the three files of match.py, with the existing util functions; with a
+    `scorer` (evaluation.ListScorer, match.py --evaluate) also the evaluation of a pair that was scored (job.scored: of
+    the map these files hold, or of the repeat that replaces it), once its bytes are on the host.  `save(map, paths)`
+    writes the map and its preview (datasets.py: a KITTI layout's is the 16-bit plane); a result (map, planes) also has
+    its planes written by `save_confidence(planes, paths)` - a repeated pair's files get the repeated pair's planes."""
     from datetime import datetime
 
-    def write(job, disparity, seconds):
+    def write(job, result, seconds):
         p = job.paths
-        planes = None
-        if isinstance(disparity, tuple):
-            disparity, planes = disparity
+        disparity, planes = map_and_planes(result)
         save(disparity, p)
         if planes is not None:
             save_confidence(planes, p)
         util.saveTimeFile(seconds, p["out_time"])
         log("[{}] {}: {:.3f} s -> {}".format(rank, datetime.now(), seconds, p["out"]))
-        score = getattr(job, "score", None)       # of the map these files hold, or of the repeat that replaces it
-        if report is not None and score is not None:
-            auc = getattr(job, "auc", None)
-            extra = dict(sparsification=auc.figures()) if auc is not None else {}
-            score_right = getattr(job, "score_right", None)
-            if score_right is not None:
-                auc_right = getattr(job, "auc_right", None)
-                extra["right"] = dict(metrics=score_right.metrics(),
-                                      sparsification=auc_right.figures() if auc_right is not None else None)
-            report.pair(job.index, job.name, score.metrics(), p.get("out_eval") or os.path.join(p["res_dir"], eval_file),
-                        **extra)
+        if scorer is not None and job.scored is not None:
+            scorer.publish(job.scored, p.get("out_eval") or os.path.join(p["res_dir"], eval_file))
     return write
 
 
 class Ticket(object):
     def __init__(self, host, done, device_map=None, host_planes=None, device_planes=None):
+        # device_map: what an evaluation scores (a KITTI layout: what the written PNG holds, not the matcher's map)
         self.host, self.done, self.device_map = host, done, device_map
         # with --confidence: the planes in a second pinned buffer, copied behind the map, and where they are on the device
         self.host_planes, self.device_planes = host_planes, device_planes
-        self.truth = None            # with --evaluate: the pair's (ground truth, mask) on the device
-        self.truth_right = None      # with --views both besides: the right view's, where the pair has one
 
 
 class MatcherBackend(object):
-    """ListPipeline's backend on StereoMatchers: one matcher and one stream per slot, as match.py --pairs_in_flight."""
+    """ListPipeline's backend on StereoMatchers: one matcher and one stream per slot, as match.py --pairs_in_flight.
 
-    def __init__(self, matchers, streams, make_library_matcher, rank=0, log=print, report=None, device_output=None,
-                 confidence=(), sparsifier=None, views="left"):
+    scorer (evaluation.ListScorer, match.py --evaluate): a pair is scored behind the graph replay on the slot's stream,
+    NOT inside the captured graph - the thresholds stay call-time arguments - and the running total takes it only in
+    retire(), once it is known which map is kept (the saturation redo), in list order.  Its record hangs on the job
+    (job.scored), where the writer thread finds it.
+    device_output(map, scored) -> (what crosses to the host for a map, what is scored), enqueued behind the map on the
+    slot's stream and like the evaluation not inside the graph (a KITTI layout: the 16-bit code, half the bytes, and what
+    the file holds); None: the map itself."""
+
+    def __init__(self, matchers, streams, make_library_matcher, rank=0, log=print, scorer=None, device_output=None):
         import torch
+        import stereo_device
         self.torch = torch
         self.matchers, self.streams = matchers, streams
-        self.make_library_matcher = make_library_matcher
+        self.redo = stereo_device.SaturationRedo(matchers, make_library_matcher)
         self.device = torch.cuda.current_device()
         self.rank, self.log = rank, log
-        self._redo_left = 0
-        self._redo_matcher = None
-        # match.py --evaluate (evaluation.ListReport).  The evaluation is enqueued behind the graph replay on the slot's
-        # stream, NOT inside the captured graph: the thresholds stay call-time arguments, and the running total takes a
-        # pair only in retire(), once it is known which map is kept (the saturation redo) - in list order.
-        self.report = report
-        self.evaluator = report.evaluator if report is not None else None
-        # what crosses to the host for a map and what is scored: the map itself, or the pair device_output(map, scored)
-        # returns, enqueued behind the map on the slot's stream - like the evaluation NOT inside the captured graph (a
-        # KITTI layout: the 16-bit code, half the bytes, and what the file holds)
-        self.device_output = device_output
-        # match.py --confidence: the matchers return (map, planes); --evaluate besides: the planes are scored
-        # (evaluation.Sparsifier) behind the pair's evaluation, outside the graph like it
-        self.confidence = tuple(confidence)
-        self.sparsifier = sparsifier
-        # match.py --views both: the matchers return [2,H,W] maps (and [2,K,H,W] planes), which cross to the host whole;
-        # index 0 is scored as before, index 1 by the report's right evaluator against the right view's ground truth
-        self.both = views == "both"
-        self.right_evaluator = report.right_evaluator if (report is not None and self.both) else None
-
-    def _map_and_planes(self, result):
-        return result if self.confidence else (result, None)
+        self.scorer, self.device_output = scorer, device_output
 
     def thread_init(self):
         self.torch.cuda.set_device(self.device)      # the current device is a per-thread setting
@@ -343,11 +319,12 @@ class MatcherBackend(object):
         s = self.streams[slot]
         return self.torch.cuda.stream(s) if s is not None else contextlib.nullcontext()
 
-    def _to_host(self, disparity, planes=None):
+    def _to_host(self, result):
         torch = self.torch
+        disparity, planes = map_and_planes(result)
         crossing, scored = disparity, disparity
         if self.device_output is not None:
-            crossing, scored = self.device_output(disparity, self.evaluator is not None)
+            crossing, scored = self.device_output(disparity, self.scorer is not None)
         host = torch.empty(tuple(crossing.shape), dtype=crossing.dtype, pin_memory=True)
         host.copy_(crossing, non_blocking=True)
         host_planes = None
@@ -358,45 +335,25 @@ class MatcherBackend(object):
         done.record()
         return Ticket(host, done, scored, host_planes, planes)
 
-    def _score(self, slot, job, ticket, truth, truth_right=None):
-        """The evaluation of ticket.device_map behind it on the current stream; the writer finds it as job.score (and,
-        --views both with right-view ground truth, job.score_right)."""
-        ticket.truth, ticket.truth_right = truth, truth_right
-        maps, planes = ticket.device_map, ticket.device_planes
-        left, left_planes = (maps[0], planes[0] if planes is not None else None) if self.both else (maps, planes)
-        job.score = self.evaluator.score(left, truth[0], truth[1], slot)
-        if self.sparsifier is not None:
-            job.auc = self.sparsifier.score(left, left_planes, truth[0])
-        if truth_right is not None:
-            job.score_right = self.right_evaluator.score(maps[1], truth_right[0], truth_right[1], slot)
-            if self.sparsifier is not None:
-                job.auc_right = self.sparsifier.score(maps[1], planes[1], truth_right[0])
+    def _truth(self, gt, mask, dev):
+        """The reader's pinned ground truth on its way to the device, behind the pair on the slot's stream."""
+        if gt is None:
+            return None
+        return gt.to(dev, non_blocking=True), (mask.to(dev, non_blocking=True) if mask is not None else None)
 
     def submit(self, slot, job, mode):
         self.log("[{}] pair {}: {}  ({}x{}, ndisp {}, {} byte(s) per pixel, {})".format(
             self.rank, job.index, job.name, job.width, job.height, job.ndisp, job.key[3], mode))
         m = self.matchers[slot]
         with self._stream(slot):
-            if mode == "eager":
-                disparity, planes = self._map_and_planes(m.match_u8(job.left, job.right, job.ndisp))
-            else:
-                disparity, planes = self._map_and_planes(m.match_graph_u8(job.left, job.right, job.ndisp))
-            ticket = self._to_host(disparity, planes)
-            if self.evaluator is not None:
-                gt_right = getattr(job, "gt_right", None) if getattr(job, "gt", None) is not None else None
-                if self.both and gt_right is None:
-                    self.report.skip_right(job.index, job.name)
-                if getattr(job, "gt", None) is None:
-                    self.report.skip(job.index, job.name)
-                else:
-                    dev = m.device
-                    truth_right = None
-                    if self.both and gt_right is not None:
-                        truth_right = (gt_right.to(dev, non_blocking=True),
-                                       job.mask_right.to(dev, non_blocking=True) if job.mask_right is not None else None)
-                    self._score(slot, job, ticket, (job.gt.to(dev, non_blocking=True),
-                                                    job.mask.to(dev, non_blocking=True) if job.mask is not None else None),
-                                truth_right)
+            match = m.match_u8 if mode == "eager" else m.match_graph_u8
+            ticket = self._to_host(match(job.left, job.right, job.ndisp))
+            if self.scorer is not None:
+                # (the right view's truth crosses only where the pair is scored at all, and in front of the left's)
+                truth_right = self._truth(job.gt_right, job.mask_right, m.device) if job.gt is not None else None
+                job.scored = self.scorer.begin(job.index, job.name, self._truth(job.gt, job.mask, m.device), truth_right)
+                if job.scored is not None:
+                    self.scorer.score(job.scored, ticket.device_map, ticket.device_planes, slot)
             return ticket
 
     def wait(self, ticket):
@@ -407,35 +364,22 @@ class MatcherBackend(object):
 
     def retire(self, slot, job, ticket):
         ticket.done.synchronize()
-        # match.py's saturation redo: the hand-written feature kernels report an activation beyond the range of their
-        # records; that pair - and, with several in flight, the ones that shared the flag with it - is matched again
-        # with the float32 library convolutions before its slot is reused
-        m0 = self.matchers[0]
-        if m0.saturation_checked() and m0.features_saturated():
-            self._redo_left = len(self.matchers)
-        if self._redo_left <= 0:
-            self._commit(slot, ticket)
-            return None
-        self._redo_left -= 1
-        if self._redo_matcher is None:
-            self._redo_matcher = self.make_library_matcher()
-        self.log("[{}] ".format(self.rank) + m0.saturation_notice().format(job.paths["out"]))
-        disparity, planes = self._map_and_planes(self._redo_matcher.match_u8(job.left, job.right, job.ndisp))
-        again = self._to_host(disparity, planes)
-        self.torch.cuda.synchronize()
-        if ticket.truth is not None:
-            with self._stream(slot):     # the slot's result buffer and scratch belong to the slot's stream
-                self._score(slot, job, again, ticket.truth, ticket.truth_right)      # the redone map, not the discarded one
-            self._commit(slot, again)
-            self.torch.cuda.synchronize()    # the library matcher's output is overwritten by the next repeat
+        scored = job.scored if self.scorer is not None else None
+        again = None
+        if self.redo.due():              # before the slot is reused (stereo_device.SaturationRedo)
+            library = self.redo.matcher()
+            self.log("[{}] ".format(self.rank) + self.redo.notice(job.paths["out"]))
+            ticket = again = self._to_host(library.match_u8(job.left, job.right, job.ndisp))
+            self.torch.cuda.synchronize()
+        if scored is not None:
+            # on the slot's stream: its result buffer and scratch belong to it, and the commit runs in front of the
+            # slot's next pair, which overwrites a replayed graph's static output
+            with self._stream(slot):
+                if again is not None:
+                    self.scorer.score(scored, again.device_map, again.device_planes, slot)   # not the discarded map
+                self.scorer.commit(scored, ticket.device_map)
+            if again is not None:
+                self.torch.cuda.synchronize()    # the library matcher's output is overwritten by the next repeat
         return again
 
-    def _commit(self, slot, ticket):
-        """The kept map into the running total, on the slot's stream (in front of the slot's next pair, which overwrites
-        a replayed graph's static output)."""
-        if ticket.truth is not None:
-            with self._stream(slot):
-                self.evaluator.commit(ticket.device_map[0] if self.both else ticket.device_map, ticket.truth[0],
-                                      ticket.truth[1])
-                if ticket.truth_right is not None:
-                    self.right_evaluator.commit(ticket.device_map[1], ticket.truth_right[0], ticket.truth_right[1])
+

@@ -26,6 +26,7 @@ Multi-GPU: launch one process per GPU with different -g / -s / -e, as the refere
 or use `torchrun --nproc-per-node N match.py ...`: rank r then takes the pairs i = r (mod N) of the window.
 """
 import argparse
+import collections
 import contextlib
 import os
 import time
@@ -34,7 +35,10 @@ from datetime import datetime
 import numpy as np
 
 import datasets
+import evaluation          # (neither module touches torch or the GPU on import: util.pin_gpu comes first, in main)
+import list_matcher
 import util
+from list_matcher import map_and_planes
 
 # Flag names, types and defaults are the reference's command line (match.py:15-43) - that is the drop-in contract;
 # the help texts are this project's.
@@ -209,11 +213,140 @@ def hyper_parameters(args):
                 sgm_V=args.sgm_V, blur_sigma=args.blur_sigma, blur_threshold=args.blur_threshold)
 
 
+# a pair launched and not yet written: the matcher's map and planes, what crosses to the host and what is scored
+# (layout.device_output), the event behind all of it, the start of its time, its paths, the matcher's inputs (a repeat
+# needs them), its slot and its scoring record (evaluation.Scored, or None)
+Pending = collections.namedtuple("Pending", "maps planes crossing kept done started paths images slot scored")
+
+
+class ListLoop(object):
+    """The list loop without --pipeline: the host decodes and standardises a pair, launches it on its slot (one matcher
+    and, with --pairs_in_flight N > 1, one stream per slot) and writes its files when the slot comes round again.
+
+    layout: datasets.py; redo: stereo_device.SaturationRedo; scorer: evaluation.ListScorer or None (--evaluate);
+    save_maps(host map, paths), save_confidence(host planes, paths): the files of what crossed to the host."""
+
+    def __init__(self, layout, matchers, streams, redo, scorer, save_maps, save_confidence, rank):
+        import torch
+        self.torch = torch
+        self.layout, self.matchers, self.streams, self.redo, self.scorer = layout, matchers, streams, redo, scorer
+        self.save_maps, self.save_confidence, self.rank = save_maps, save_confidence, rank
+        self.pending = []            # oldest first
+
+    def _stream(self, slot):
+        return self.torch.cuda.stream(self.streams[slot]) if len(self.matchers) > 1 else contextlib.nullcontext()
+
+    def _to_device(self, truth):
+        """(ground truth, mask or None) of the host on the device, behind the pair on its stream."""
+        if truth is None:
+            return None
+        return (self.torch.from_numpy(truth[0]).cuda(),
+                self.torch.from_numpy(truth[1]).cuda() if truth[1] is not None else None)
+
+    def launch(self, slot, index, paths, left_image, right_image, ndisp, truth, truth_right):
+        """The timed region (match.py:129-179): host arrays in, host array out, device-synchronised - from here to
+        finish().  With several pairs in flight the pair runs on its slot's stream."""
+        torch = self.torch
+        started = time.time()
+        with self._stream(slot):
+            dev_l = torch.from_numpy(left_image).cuda()
+            dev_r = torch.from_numpy(right_image).cuda()
+            maps, planes = map_and_planes(self.matchers[slot].match(dev_l, dev_r, ndisp))
+            # what crosses to the host and what is scored: the map, or a KITTI layout's 16-bit code and what it holds,
+            # behind the map on this stream - and behind that the evaluation
+            crossing, kept = self.layout.device_output(maps, truth is not None)
+            scored = None
+            if self.scorer is not None:
+                scored = self.scorer.begin(index, paths["left"], self._to_device(truth), self._to_device(truth_right))
+            if scored is not None:
+                self.scorer.score(scored, kept, planes, slot)
+            done = torch.cuda.Event()
+            done.record()
+        self.pending.append(Pending(maps, planes, crossing, kept, done, started, paths, (dev_l, dev_r, ndisp), slot, scored))
+
+    def finish(self):
+        """Collects and writes the oldest pair."""
+        torch = self.torch
+        p = self.pending.pop(0)
+        p.done.synchronize()
+        planes, crossing, kept = p.planes, p.crossing, p.kept
+        redone = self.redo.due()
+        if redone:
+            library = self.redo.matcher()
+            print("[{}] ".format(self.rank) + self.redo.notice(p.paths["out"]))
+            maps, planes = map_and_planes(library.match(*p.images))
+            crossing, kept = self.layout.device_output(maps, p.scored is not None)
+            torch.cuda.synchronize()
+        if p.scored is not None:
+            # the total takes the map that is kept, once, in list order; a repeated pair is scored again
+            with self._stream(p.slot):
+                if redone:
+                    self.scorer.score(p.scored, kept, planes, p.slot)
+                self.scorer.commit(p.scored, kept)
+            if redone:
+                torch.cuda.synchronize()     # the library matcher's output is overwritten by the next repeat
+        host_map = crossing.cpu().numpy()            # the float32 map, or a KITTI layout's 16-bit plane
+        host_planes = planes.cpu().numpy() if planes is not None else None
+        seconds = time.time() - p.started
+        self.save_maps(host_map, p.paths)
+        if host_planes is not None:
+            self.save_confidence(host_planes, p.paths)
+        util.saveTimeFile(seconds, p.paths["out_time"])
+        print("[{}] {}: {:.3f} s -> {}".format(self.rank, datetime.now(), seconds, p.paths["out"]))
+        if p.scored is not None:
+            self.scorer.publish(p.scored, p.paths["out_eval"])
+
+    def run(self, indices, paths, shape, footprint):
+        """paths(index) -> the pair's inputs and outputs; shape(left path) -> (H, W, ndisp); footprint(H, W, ndisp) ->
+        the workspace's bytes, and refuses a shape outside what the kernels serve (ValueError naming the limit; each
+        matcher checks its own workspace against the free device memory before it allocates it)."""
+        layout, in_flight = self.layout, len(self.matchers)
+        last_shape = None
+        for launched, index in enumerate(indices):
+            p = paths(index)
+            left_path, right_path = p["left"], p["right"]
+            for d in p["dirs"]:
+                util.recurMk(os.path.abspath(d))
+            height, width, ndisp = shape(left_path)
+            print("[{}] pair {}: {} | {}  ({}x{}, ndisp {})".format(self.rank, index, left_path, right_path, width, height, ndisp))
+            nbytes = footprint(height, width, ndisp)
+            if (height, width, ndisp) != last_shape:
+                print("[{}] workspace {:.2f} GB ({} pair(s) in flight)".format(self.rank, nbytes / 1e9, in_flight))
+                last_shape = (height, width, ndisp)
+
+            # --views both: the right view is scored where the left one is and disp1GT.pfm exists (ListScorer.begin)
+            truth = layout.load_truth(left_path) if self.scorer is not None else None
+            truth_right = layout.load_truth_right(left_path) if (truth is not None and self.scorer.both) else None
+            for t in (truth, truth_right):
+                if t is not None:
+                    evaluation.check_shape(t[0], (height, width), left_path)
+
+            # decode + standardise (match.py:118-125): population std, no /255
+            views = []
+            for path in (left_path, right_path):
+                g = util.read_gray(path).astype(np.float32)
+                g = (g - np.mean(g, axis=(0, 1))) / np.std(g, axis=(0, 1))
+                views.append(np.expand_dims(g, axis=2))
+            left_image, right_image = views
+            if layout.kitti and right_image.shape != left_image.shape:
+                raise ValueError("%s is %dx%d, the left view %dx%d" % (right_path, right_image.shape[1], right_image.shape[0],
+                                                                       width, height))
+            assert left_image.shape == (height, width, 1)
+            assert right_image.shape == (height, width, 1)
+
+            if len(self.pending) == in_flight:
+                self.finish()                # the oldest pair is the one that used this slot
+            self.launch(launched % in_flight, index, p, left_image, right_image, ndisp, truth, truth_right)
+            if in_flight == 1:
+                self.finish()
+        while self.pending:
+            self.finish()
+
+
 def main(argv=None):
     args = parser.parse_args(argv)
     if args.fast and args.exact:
         parser.error("--fast and --exact exclude each other")
-    import evaluation as ev
     layout = datasets.get(args.dataset)
     try:
         eval_thresholds = layout.parse_thresholds(args.eval_thresholds if args.eval_thresholds is not None
@@ -242,7 +375,7 @@ def main(argv=None):
             parser.error("--eval_quantiles is not available with --dataset %s: the KITTI protocol has no error quantiles"
                          % args.dataset)
         try:
-            eval_quantiles = ev.parse_quantiles(args.eval_quantiles)
+            eval_quantiles = evaluation.parse_quantiles(args.eval_quantiles)
         except ValueError as e:
             parser.error("--eval_quantiles: %s" % e)
     both = args.views == "both"
@@ -263,10 +396,11 @@ def main(argv=None):
 
     with open(args.list_file, "r") as f:
         left_paths = [line.strip() for line in f.readlines()]
+    indices = shard_indices(args.start, args.end, len(left_paths), rank, world)
     if layout.kitti:
         # one --ndisp serves the whole list: a frame it does not fit (ndisp > W - 2) is refused here, from the image
         # headers, before the GPU is touched
-        for index in shard_indices(args.start, args.end, len(left_paths), rank, world):
+        for index in indices:
             sd.check_envelope(*layout.shape(left_paths[index], ndisp_flag))
 
     hip.require_device()
@@ -295,16 +429,12 @@ def main(argv=None):
             cv_mode=hip.MCCNN_CV_MFMA if args.fast else hip.MCCNN_CV_EXACT,
             cbca_order=hip.MCCNN_CBCA_SEPARABLE if (args.fast and args.separable_cbca) else hip.MCCNN_CBCA_REFERENCE_ORDER,
             features=features, decision=decision,
-            on_saturation="ignore",      # several pairs may be in flight: finish() polls the flag and repeats them
+            on_saturation="ignore",      # several pairs may be in flight: the loops poll the flag and repeat them
             extras=dict(both_view_support=args.paper_support_regions,
                         interpolation_directions=16 if args.paper_interpolation else 4,
                         occlusion_from_left=args.paper_interpolation, numpy1_promotion=args.numpy1_promotion,
                         sgm_independent_directions=args.paper_sgm),
             confidence=conf_names, views=args.views)
-
-    def map_and_planes(result):
-        """What a matcher returns, as (map, planes or None)."""
-        return result if conf_names else (result, None)
 
     def save_confidence(planes, out):
         """One PFM per measure from the host planes [K,H,W] (layout.confidence_path names the file); --views both:
@@ -322,200 +452,64 @@ def main(argv=None):
         layout.save(result[0], out)
         layout.save_right(result[1], out)
 
-    def left_of(t):
-        """The left view's part of a matcher's map or planes (None stays None)."""
-        return t[0] if (both and t is not None) else t
+    def paths(index):
+        # Middlebury: outputs mirror the input tree under the two roots (match.py:99-110): <root>/<dir of im0.png relative
+        # to data_dir>; a KITTI layout: the development kit's submission tree (src/datasets.py)
+        left_path = left_paths[index]
+        return dict(layout.outputs(left_path, args.data_dir, result_root, image_root), left=left_path,
+                    right=layout.right(left_path), calib=None if layout.kitti else layout.calib(left_path))
 
     matchers = [make_matcher("miopen" if args.features == "library" else "auto") for _ in range(in_flight)]
     footprint_kw = dict(pairs_in_flight=in_flight, arch=args.arch,
                         fc_units=net.num_fc_units if accurate else sd.DECISION_UNITS, confidence=len(conf_names),
                         views=args.views)
+
+    def footprint(height, width, ndisp):        # refuses a shape outside the envelope, with its message
+        return sd.workspace_bytes(height, width, ndisp, matchers[0].pixel_major(),
+                                  matchers[0].workspace_cbca_kernel(height, width, ndisp), **footprint_kw)
+
+    def make_library_matcher():                 # the saturation redo's
+        return make_matcher("miopen", "library")
+
     streams = [torch.cuda.Stream() for _ in range(in_flight)] if in_flight > 1 else [None]
     # --evaluate: one result buffer and scratch per slot, the list's running total on the device (src/evaluation.py)
     # (--views both: a second evaluator of the same kind, whose total pools the right maps against disp1GT.pfm)
     # (--eval_quantiles: both evaluators also select the error quantiles of every map and pool them over the list)
-    report = ev.ListReport(layout.evaluator(eval_thresholds, slots=in_flight, interpolate=args.eval_interpolate,
-                                            quantiles=eval_quantiles),
-                           layout.evaluator(eval_thresholds, slots=in_flight, quantiles=eval_quantiles) if both else None
-                           ) if args.evaluate else None
-    evaluator = report.evaluator if report is not None else None
-    evaluator_right = report.right_evaluator if report is not None else None
-    # --evaluate --confidence: the sparsification figures of every scored pair, behind its evaluation on its stream
-    sparsifier = ev.Sparsifier(conf_names, auc_threshold) if (report is not None and conf_names) else None
+    # (--confidence: the sparsification figures of every scored map, behind its evaluation on its stream)
+    scorer = None
+    if args.evaluate:
+        report = evaluation.ListReport(
+            layout.evaluator(eval_thresholds, slots=in_flight, interpolate=args.eval_interpolate, quantiles=eval_quantiles),
+            layout.evaluator(eval_thresholds, slots=in_flight, quantiles=eval_quantiles) if both else None)
+        scorer = evaluation.ListScorer(report, evaluation.Sparsifier(conf_names, auc_threshold) if conf_names else None,
+                                       args.views)
     eval_path = os.path.join(result_root, "eval.json" if world == 1 else "eval_rank{}.json".format(rank))
+    pipeline = None
     if args.pipeline:
-        import list_matcher as lm
-
-        def paths(index):
-            left_path = left_paths[index]
-            return dict(layout.outputs(left_path, args.data_dir, result_root, image_root), left=left_path,
-                        right=layout.right(left_path), calib=None if layout.kitti else layout.calib(left_path))
-
-        def check_shape(height, width, ndisp):      # the flagless loop's refusal, with its message
-            sd.workspace_bytes(height, width, ndisp, matchers[0].pixel_major(),
-                               matchers[0].workspace_cbca_kernel(height, width, ndisp), **footprint_kw)
-
-        backend = lm.MatcherBackend(matchers, streams, lambda: make_matcher("miopen", "library"), rank=rank,
-                                    report=report, device_output=layout.device_output if layout.kitti else None,
-                                    confidence=conf_names, sparsifier=sparsifier, views=args.views)
+        backend = list_matcher.MatcherBackend(matchers, streams, make_library_matcher, rank=rank, scorer=scorer,
+                                              device_output=layout.device_output if layout.kitti else None)
         # a KITTI frame's size is its decoded left image's: the capture policy sees every change through the job's key
-        reader = lm.make_reader(paths, check_shape, truth=layout.load_truth if args.evaluate else None,
-                                shape=(lambda left, image: layout.shape(left, ndisp_flag, image)) if layout.kitti else None,
-                                truth_right=layout.load_truth_right if (args.evaluate and both) else None)
-        pipeline = lm.ListPipeline(reader, backend,
-                                   lm.make_writer(rank, report=report, eval_file=out_eval_file, save=save_maps,
-                                                  save_confidence=save_confidence if conf_names else None),
-                                   slots=in_flight, readers=args.readers)
+        reader = list_matcher.make_reader(
+            paths, footprint, truth=layout.load_truth if args.evaluate else None,
+            shape=(lambda left, image: layout.shape(left, ndisp_flag, image)) if layout.kitti else None,
+            truth_right=layout.load_truth_right if (args.evaluate and both) else None)
+        writer = list_matcher.make_writer(rank, scorer=scorer, eval_file=out_eval_file, save=save_maps,
+                                          save_confidence=save_confidence if conf_names else None)
+        pipeline = list_matcher.ListPipeline(reader, backend, writer, slots=in_flight, readers=args.readers)
         try:
-            pipeline.run(shard_indices(args.start, args.end, len(left_paths), rank, world))
+            pipeline.run(indices)
         finally:
             print("[{}] {}".format(rank, pipeline.summary()))
-        if report is not None:
-            report.write(eval_path)
-        return pipeline
-
-    pending = []          # pairs launched and not yet written: (device map, done event, start time, output paths)
-    launched = 0
-    last_shape = None
-
-    redo = {"left": 0, "matcher": None}
-
-    def finish(entry):
-        disparity, planes, crossing, kept, done, stTime, out, images, scored, scored_right = entry
-        out_path, out_time_path = out["out"], out["out_time"]
-        done.synchronize()
-        redone = False
-        # the hand-written feature kernels report an activation beyond the range of their stored records (never seen
-        # on standardised images with the trained weights): that pair - and, with several in flight, the ones that
-        # shared the flag with it - is matched again with the float32 library convolutions
-        if matchers[0].saturation_checked() and matchers[0].features_saturated():
-            redo["left"] = in_flight
-        if redo["left"] > 0:
-            redo["left"] -= 1
-            if redo["matcher"] is None:
-                redo["matcher"] = make_matcher("miopen", "library")
-            print("[{}] ".format(rank) + matchers[0].saturation_notice().format(out_path))
-            disparity, planes = map_and_planes(redo["matcher"].match(images[0], images[1], images[2]))
-            crossing, kept = layout.device_output(disparity, scored is not None)
-            torch.cuda.synchronize()
-            redone = True
-        if scored is not None:
-            # the total takes the map that is kept, once, in list order; a repeated pair is scored again
-            index, name, score, auc, gt, mask, slot, json_path = scored
-            with torch.cuda.stream(streams[slot]) if in_flight > 1 else contextlib.nullcontext():
-                if redone:
-                    score = evaluator.score(left_of(kept), gt, mask, slot)
-                    if sparsifier is not None:
-                        auc = sparsifier.score(left_of(kept), left_of(planes), gt)
-                evaluator.commit(left_of(kept), gt, mask)
-                if scored_right is not None:
-                    score_r, auc_r, gt_r, mask_r = scored_right
-                    if redone:
-                        score_r = evaluator_right.score(kept[1], gt_r, mask_r, slot)
-                        if sparsifier is not None:
-                            auc_r = sparsifier.score(kept[1], planes[1], gt_r)
-                        scored_right = (score_r, auc_r, gt_r, mask_r)
-                    evaluator_right.commit(kept[1], gt_r, mask_r)
-            if redone:
-                torch.cuda.synchronize()     # the library matcher's output is overwritten by the next repeat
-        left_disparity_map = crossing.cpu().numpy()     # the float32 map, or a KITTI layout's 16-bit plane
-        host_planes = planes.cpu().numpy() if planes is not None else None
-        endTime = time.time()
-        save_maps(left_disparity_map, out)
-        if host_planes is not None:
-            save_confidence(host_planes, out)
-        util.saveTimeFile(endTime - stTime, out_time_path)
-        print("[{}] {}: {:.3f} s -> {}".format(rank, datetime.now(), endTime - stTime, out_path))
-        if scored is not None:
-            right = None
-            if scored_right is not None:
-                right = dict(metrics=scored_right[0].metrics(),
-                             sparsification=scored_right[1].figures() if scored_right[1] is not None else None)
-            report.pair(index, name, score.metrics(), json_path,
-                        sparsification=auc.figures() if auc is not None else None, right=right)
-
-    for index in shard_indices(args.start, args.end, len(left_paths), rank, world):
-        left_path = left_paths[index]
-        right_path = layout.right(left_path)
-        # Middlebury: outputs mirror the input tree under the two roots (match.py:99-110): <root>/<dir of im0.png relative
-        # to data_dir>; a KITTI layout: the development kit's submission tree (src/datasets.py)
-        out = layout.outputs(left_path, args.data_dir, result_root, image_root)
-        for d in out["dirs"]:
-            util.recurMk(os.path.abspath(d))
-
-        # Middlebury: calib.txt; a KITTI layout: the left image's header and --ndisp
-        height, width, ndisp = layout.shape(left_path, ndisp_flag)
-        print("[{}] pair {}: {} | {}  ({}x{}, ndisp {})".format(rank, index, left_path, right_path, width, height, ndisp))
-        # refuses a shape outside what the kernels serve (ValueError naming the limit); each matcher checks its own
-        # workspace against the free device memory before it allocates it
-        footprint = sd.workspace_bytes(height, width, ndisp, matchers[0].pixel_major(),
-                                       matchers[0].workspace_cbca_kernel(height, width, ndisp), **footprint_kw)
-        if (height, width, ndisp) != last_shape:
-            print("[{}] workspace {:.2f} GB ({} pair(s) in flight)".format(rank, footprint / 1e9, in_flight))
-            last_shape = (height, width, ndisp)
-
-        truth = layout.load_truth(left_path) if args.evaluate else None
-        if truth is not None:
-            ev.check_shape(truth[0], (height, width), left_path)
-        elif args.evaluate:
-            report.skip(index, left_path)
-        # --views both: the right view is scored where the left one is and disp1GT.pfm exists
-        truth_right = layout.load_truth_right(left_path) if (both and truth is not None) else None
-        if truth_right is not None:
-            ev.check_shape(truth_right[0], (height, width), left_path)
-        elif both and args.evaluate:
-            report.skip_right(index, left_path)
-
-        # decode + standardise (match.py:118-125): population std, no /255
-        views = []
-        for path in (left_path, right_path):
-            g = util.read_gray(path).astype(np.float32)
-            g = (g - np.mean(g, axis=(0, 1))) / np.std(g, axis=(0, 1))
-            views.append(np.expand_dims(g, axis=2))
-        left_image, right_image = views
-        if layout.kitti and right_image.shape != left_image.shape:
-            raise ValueError("%s is %dx%d, the left view %dx%d" % (right_path, right_image.shape[1], right_image.shape[0],
-                                                                   width, height))
-        assert left_image.shape == (height, width, 1)
-        assert right_image.shape == (height, width, 1)
-
-        # timed region (match.py:129-179): host arrays in, host array out, device-synchronised.  With several pairs
-        # in flight the pair is launched on its slot's stream and collected when the slot comes round again.
-        slot = launched % in_flight
-        launched += 1
-        if len(pending) == in_flight:
-            finish(pending.pop(0))        # the oldest pair is the one that used this slot
-        stTime = time.time()
-        ctx = torch.cuda.stream(streams[slot]) if in_flight > 1 else contextlib.nullcontext()
-        with ctx:
-            dev_l = torch.from_numpy(left_image).cuda()
-            dev_r = torch.from_numpy(right_image).cuda()
-            disparity, planes = map_and_planes(matchers[slot].match(dev_l, dev_r, ndisp))
-            scored = scored_right = None
-            # what crosses to the host and what is scored: the map, or a KITTI layout's 16-bit code and what it holds,
-            # behind the map on this stream
-            crossing, kept = layout.device_output(disparity, truth is not None)
-            if truth is not None:        # behind the map, on the pair's stream
-                gt = torch.from_numpy(truth[0]).cuda()
-                mask = torch.from_numpy(truth[1]).cuda() if truth[1] is not None else None
-                scored = (index, left_path, evaluator.score(left_of(kept), gt, mask, slot),
-                          sparsifier.score(left_of(kept), left_of(planes), gt) if sparsifier is not None else None, gt,
-                          mask, slot, out["out_eval"])
-            if truth_right is not None:
-                gt_r = torch.from_numpy(truth_right[0]).cuda()
-                mask_r = torch.from_numpy(truth_right[1]).cuda() if truth_right[1] is not None else None
-                scored_right = (evaluator_right.score(kept[1], gt_r, mask_r, slot),
-                                sparsifier.score(kept[1], planes[1], gt_r) if sparsifier is not None else None, gt_r, mask_r)
-            done = torch.cuda.Event()
-            done.record()
-        pending.append((disparity, planes, crossing, kept, done, stTime, out, (dev_l, dev_r, ndisp), scored, scored_right))
-        if in_flight == 1:
-            finish(pending.pop(0))
-    while pending:
-        finish(pending.pop(0))
-    if report is not None:
-        report.write(eval_path)
+    else:
+        loop = ListLoop(layout, matchers, streams, sd.SaturationRedo(matchers, make_library_matcher), scorer, save_maps,
+                        save_confidence, rank)
+        loop.run(indices, paths, lambda left_path: layout.shape(left_path, ndisp_flag), footprint)
+    if scorer is not None:
+        scorer.report.write(eval_path)
+    return pipeline
 
 
 if __name__ == "__main__":
     main()
+
+

@@ -2233,3 +2233,38 @@ class StereoMatcher(object):
         graph.replay()
         self._saturated_graph_pair(sl, sr, ndisp, out)
         return out
+
+
+class SaturationRedo(object):
+    """The repeat policy of a list loop whose matchers run with on_saturation="ignore" (several pairs in flight share
+    one flag).  The hand-written kernels report an activation beyond the range of their stored records (never seen on
+    standardised images with the trained weights): that pair - and, with several in flight, the ones that shared the
+    flag with it - is matched again by a library matcher, built when the first pair needs it.
+
+    matchers: one per pair in flight (they share the network, and with it the flag: the first is asked);
+    make_library_matcher(): the matcher that repeats a pair."""
+
+    def __init__(self, matchers, make_library_matcher):
+        self.matchers, self.make_library_matcher = matchers, make_library_matcher
+        self.left = 0                # pairs still to repeat: this one and the next len(matchers) - 1
+        self._matcher = None
+
+    def due(self):
+        """Asked once per pair, in list order, when the pair's map is complete: True when it is to be repeated.
+        Reads the flag (which blocks the host) only where the last pair ran a kernel that raises it."""
+        m0 = self.matchers[0]
+        if m0.saturation_checked() and m0.features_saturated():
+            self.left = len(self.matchers)
+        if self.left <= 0:
+            return False
+        self.left -= 1
+        return True
+
+    def matcher(self):
+        if self._matcher is None:
+            self._matcher = self.make_library_matcher()
+        return self._matcher
+
+    def notice(self, path):
+        """What a loop prints when it repeats the pair whose map is `path`."""
+        return self.matchers[0].saturation_notice().format(path)

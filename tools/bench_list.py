@@ -2,7 +2,7 @@
 """Times match.py over a LIST of pairs: the flagless list loop against --pipeline (each also with --pairs_in_flight 2).
 
     timeout -k 10 900 python tools/bench_list.py [--pairs 100] [--scenes 10] [--size 500 750 256] [--readers 4]
-                                                 [--baseline-src DIR] [--out FILE]
+                                                 [--baseline-src DIR | --compare-src DIR] [--out FILE]
 
 Writes a seeded list of synthetic PNG pairs (synthetic.make_scene_u8; `--scenes` different scenes, written over and over
 until there are `--pairs` entries - nothing in either loop caches a pair) into a temporary directory and runs the list,
@@ -14,6 +14,11 @@ tool under one `timeout`.  Prints one JSON object.
 --baseline-src DIR: the flagless variants run the match.py of another source tree (e.g. the parent commit's
 mc-cnn-python_amd/src, exported with `git archive`) against the same built library, so that the baseline is not a
 variant of the code under test.
+
+--compare-src DIR: another question - has the host code of the loops become slower?  Every loop (flagless, flagless with
+--pairs_in_flight 2, --pipeline) runs as three legs, alternating: DIR, DIR again, this tree.  The two identical legs are
+the yardstick: a loop passes when this tree's mean differs from the mean of DIR's two legs by no more than those two
+legs' means differ from each other.  Exit status 0 when every loop passes.
 """
 import argparse
 import contextlib
@@ -49,22 +54,26 @@ def source_tree(src, stash):
         sys.modules.update(outside)
 
 
-def write_list(root, pairs, scenes, H, W, D, seed):
+def write_list(root, pairs, scenes, H, W, D, seed, truth=False):
     from PIL import Image
     sys.path.insert(0, SRC)
     import synthetic
+    import util
     sys.path.remove(SRC)
     made = []
     for s in range(scenes):
-        left, right, _ = synthetic.make_scene_u8(H, W, D, seed=seed + s)
-        made.append((left, right))
+        left, right, disparity = synthetic.make_scene_u8(H, W, D, seed=seed + s)
+        made.append((left, right, np.asarray(disparity, np.float32)))
     lines = []
     for i in range(pairs):
         d = os.path.join(root, "data", "set", "pair%03d" % i)
         os.makedirs(d)
-        left, right = made[i % scenes]
+        left, right, disparity = made[i % scenes]
         Image.fromarray(left, mode="L").save(os.path.join(d, "im0.png"))
         Image.fromarray(right, mode="L").save(os.path.join(d, "im1.png"))
+        if truth:        # (what the figures say is not the point: the scoring path is inside the timing)
+            util.writePfm(disparity, os.path.join(d, "disp0GT.pfm"))
+            util.writePfm(disparity, os.path.join(d, "disp1GT.pfm"))
         with open(os.path.join(d, "calib.txt"), "w") as f:
             f.write("cam0=[1 0 0; 0 1 0; 0 0 1]\ncam1=[1 0 0; 0 1 0; 0 0 1]\ndoffs=0\nbaseline=100\n"
                     "width=%d\nheight=%d\nndisp=%d\nisint=0\nvmin=0\nvmax=%d\ndyavg=0\ndymax=0\n" % (W, H, D, D))
@@ -84,11 +93,15 @@ def main():
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--seed", type=int, default=1000)
     ap.add_argument("--baseline-src", default=None, help="source tree whose match.py runs the flagless variants")
+    ap.add_argument("--compare-src", default=None,
+                    help="source tree (the parent commit's) that every loop is compared with; see above")
+    ap.add_argument("--truth", action="store_true", help="the list carries disp0GT.pfm and disp1GT.pfm beside every pair")
+    ap.add_argument("--flags", default="", help="more match.py flags for every variant, e.g. '--evaluate --views both'")
     ap.add_argument("--weights", default=os.path.join(ROOT, "tests", "golden", "mccnn_fast_weights.npz"))
     ap.add_argument("--out", default=None, help="also write the JSON object to this file")
     args = ap.parse_args()
     H, W, D = args.size
-    if args.baseline_src:
+    if args.baseline_src or args.compare_src:
         # the other tree's binding looks for the library beside itself: point both at the one that was built here
         os.environ.setdefault("MCCNN_HIP_LIB", os.path.join(ROOT, "mc-cnn-python_amd", "lib", "libmccnn_hip.so"))
     base_src = os.path.abspath(args.baseline_src) if args.baseline_src else SRC
@@ -96,18 +109,23 @@ def main():
     variants = [("flagless", base_src, []), ("flagless_in_flight_2", base_src, ["--pairs_in_flight", "2"]),
                 ("pipeline", SRC, ["--pipeline", "--readers", str(args.readers)]),
                 ("pipeline_in_flight_2", SRC, ["--pipeline", "--readers", str(args.readers), "--pairs_in_flight", "2"])]
+    if args.compare_src:
+        other = os.path.abspath(args.compare_src)
+        stashes[other] = {}
+        variants = [("%s@%s" % (name, leg), src, extra) for name, _, extra in variants[:3]
+                    for leg, src in (("parent_a", other), ("parent_b", other), ("branch", SRC))]
     root = tempfile.mkdtemp(prefix="bench_list_")
     result = dict(tool="tools/bench_list.py", pairs=args.pairs, scenes=args.scenes, height=H, width=W, ndisp=D,
-                  readers=args.readers, baseline_src="parent export" if args.baseline_src else "this tree",
+                  readers=args.readers, truth=args.truth, flags=args.flags, baseline_src="parent export" if args.baseline_src else "this tree",
                   unit="ms per pair, wall, files written", passes={}, counters={}, stage_seconds_last_pass={}, steady_ms_per_pair_last_pass={})
     try:
         t = time.time()
-        lst = write_list(root, args.pairs, args.scenes, H, W, D, args.seed)
+        lst = write_list(root, args.pairs, args.scenes, H, W, D, args.seed, args.truth)
         result["list_written_s"] = round(time.time() - t, 2)
 
         def one_pass(name, src, extra, tag):
             argv = ["-g", "0", "--list_file", lst, "--resume", args.weights, "--data_dir", os.path.join(root, "data"),
-                    "--save_dir", os.path.join(root, "out_" + name), "-t", tag, "-s", "0", "-e", str(args.pairs - 1)] + extra
+                    "--save_dir", os.path.join(root, "out_" + name), "-t", tag, "-s", "0", "-e", str(args.pairs - 1)] + extra + args.flags.split()
             with source_tree(src, stashes[src]):
                 import match
                 log = io.StringIO()
@@ -138,17 +156,30 @@ def main():
     for name, ms in result["passes"].items():
         summary[name] = dict(mean=round(float(np.mean(ms)), 3), min=min(ms), max=max(ms), spread=round(max(ms) - min(ms), 3))
     result["summary"] = summary
+    if args.compare_src:
+        result["baseline_src"] = "parent export, every loop (--compare-src)"
+        result["compare"] = {}
+        for loop in sorted({name.split("@")[0] for name in summary}):
+            a, b, mine = (summary["%s@%s" % (loop, leg)]["mean"] for leg in ("parent_a", "parent_b", "branch"))
+            result["compare"][loop] = dict(parent=round((a + b) / 2, 3), branch=mine, difference=round(mine - (a + b) / 2, 3),
+                                           yardstick=round(abs(a - b), 3), within=bool(abs(mine - (a + b) / 2) <= abs(a - b)))
+        result["every_loop_within_the_yardstick"] = all(c["within"] for c in result["compare"].values())
+        return finish(args, result, result["every_loop_within_the_yardstick"])
     base, pipe = summary["flagless"], summary["pipeline"]
     result["pipeline_gain_ms_per_pair"] = round(base["mean"] - pipe["mean"], 3)
     result["baseline_spread_ms"] = base["spread"]
     result["pipeline_faster_by_more_than_baseline_spread"] = bool(base["mean"] - pipe["mean"] > base["spread"])
+    return finish(args, result, result["pipeline_faster_by_more_than_baseline_spread"])
+
+
+def finish(args, result, passed):
     line = json.dumps(result)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             f.write(line + "\n")
     print(line)
-    return 0 if result["pipeline_faster_by_more_than_baseline_spread"] else 1
+    return 0 if passed else 1
 
 
 if __name__ == "__main__":
