@@ -141,6 +141,18 @@ constexpr int CVP_TW = 63;   // new pixels per tile (lanes 1 .. 63)
 #endif
 // (an ablated part stays in the code, behind a condition no real call meets, so that registers and LDS do not change)
 __device__ __forceinline__ bool cvp_never(int D) { return D == 12345; }
+#ifndef CVP_NT
+#define CVP_NT 1             // A/B: the volumes' 16-byte stores carry the non-temporal hint (1) or not (0)
+#endif
+typedef float cv_f4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void cvp_store16(char *dst, cv_f4 v)
+{
+#if CVP_NT
+    __builtin_nontemporal_store(v, reinterpret_cast<cv_f4 *>(dst));
+#else
+    *reinterpret_cast<cv_f4 *>(dst) = v;
+#endif
+}
 __global__ __launch_bounds__(256, 3) void cost_volume_exact_pairs_kernel(const float *__restrict__ fl,
                                                                          const float *__restrict__ fr, int H, int W, int D,
                                                                          float *__restrict__ lcv, float *__restrict__ rcv,
@@ -156,18 +168,37 @@ __global__ __launch_bounds__(256, 3) void cost_volume_exact_pairs_kernel(const f
     const int w0 = (int)blockIdx.x * CVP_TW - 1, h = blockIdx.y;   // lane 0: pixel w0 (ghost)
     const int tid = threadIdx.x;
     const size_t rowbase = (size_t)h * W;
-    for (int i = tid; i < CV_TW * 16; i += 256) {
-        const int px = i >> 4, c4 = i & 15;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (w0 + px >= 0 && w0 + px < W) v = *reinterpret_cast<const float4 *>(fl + (rowbase + w0 + px) * CV_C + c4 * 4);
-        *reinterpret_cast<float4 *>(&sL[px * CV_LD + c4 * 4]) = v;
-    }
-    // the first tile's columns w0 - 63 .. w0 + 63
-    for (int i = tid; i < (CV_TW + CV_DT - 1) * 16; i += 256) {
-        const int x = w0 - (CV_DT - 1) + (i >> 4), c4 = i & 15;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (x >= 0 && x < W) v = *reinterpret_cast<const float4 *>(fr + (rowbase + x) * CV_C + c4 * 4);
-        *reinterpret_cast<float4 *>(&sR[(x & (RING - 1)) * CV_LD + c4 * 4]) = v;
+    // Staging: all of a thread's 4 + 8 loads are issued before the first is waited for (a[] is not live yet, so the
+    // twelve float4 fit), and every load is unconditional, so that the compiler's count of loads in flight stays exact.
+    // A column outside the image is fetched from the clamped address and kept as it comes: a score S(w, d) is stored
+    // only for 0 <= w - d and w < W, so neither a left pixel nor a right column outside the image ever reaches a
+    // stored score (the neighbour's row a lane multiplies for d + 1 is column w - d - 1, inside whenever w >= d + 1).
+    {
+        cv_f4 pl[4], pr[8];   // (the compiler's own vector type: an array of float4 structs copied from memory to memory
+                               // is kept in scratch)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int i = tid + q * 256, x = w0 + (i >> 4), c4 = i & 15;
+            pl[q] = *reinterpret_cast<const cv_f4 *>(fl + (rowbase + min(max(x, 0), W - 1)) * CV_C + c4 * 4);
+        }
+        // the first tile's columns w0 - 63 .. w0 + 63
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int i = tid + q * 256, x = w0 - (CV_DT - 1) + (i >> 4), c4 = i & 15;
+            pr[q] = *reinterpret_cast<const cv_f4 *>(fr + (rowbase + min(max(x, 0), W - 1)) * CV_C + c4 * 4);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int i = tid + q * 256, px = i >> 4, c4 = i & 15;
+            *reinterpret_cast<cv_f4 *>(&sL[px * CV_LD + c4 * 4]) = pl[q];
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int i = tid + q * 256, x = w0 - (CV_DT - 1) + (i >> 4), c4 = i & 15;
+            // (the last sixteen threads fill a 128th row, column w0 + 64: its ring slot is the one of column w0 - 64,
+            // which no product of the first tile reads and the first tile's prefetch overwrites)
+            *reinterpret_cast<cv_f4 *>(&sR[(x & (RING - 1)) * CV_LD + c4 * 4]) = pr[q];
+        }
     }
     __syncthreads();
 
@@ -181,17 +212,54 @@ __global__ __launch_bounds__(256, 3) void cost_volume_exact_pairs_kernel(const f
     }
     constexpr int TP = CV_LD;           // pitch of the score tile: a multiple of four, so a pixel's disparities leave as float4
     float *const sT = sL;               // every thread holds its left features in registers from here on
+    // Both volumes leave as 16-byte stores: 16 lanes x four disparities = one pixel's 64 disparities of a tile, four
+    // pixels per wave instruction (a quarter of the store instructions of the one-float-per-lane form: the store phase
+    // is bound by their count).  A thread owns 4 quads of the left and 8 of the right volume per tile, at the same
+    // places of the score tile in every tile, and classifies each once per tile: a FULL quad (all four entries exist)
+    // is one 16-byte store - per volume, all LDS reads first (unconditional, clamped row), then the stores back to
+    // back under their predicates; no load is in flight there that a store could be made to wait for, so a wave's
+    // stores of one tile retire under its products of the next.  A quad that straddles an edge (w = d, the last
+    // disparities when D is no multiple of 4, the image border, the ends of an anti-diagonal) is RAGGED and goes out
+    // float by float in a pass of its own behind the full ones.  What decides the class does not change from tile to
+    // tile except the quad's first disparity d, so it is one comparison of d with a limit worked out here:
+    //   left,  pixel ww = w0 + px:                  entry d exists iff d <= min(ww, D - 1)
+    //   right, pixel x = w0 + px - d (px: tile row of the quad's first entry; x >= 0 iff d <= w0 + px):
+    //          some entry may exist iff d <= min(w0 + px, D - 1) and px + 3 >= 1, px <= 63; all four exist iff besides
+    //          rows px .. px + 3 are rows 1 .. 63 of pixels inside the image (the same in every tile) and d + 3 <= D - 1
+    // and the byte offset of a quad within its image row (below 2^31: checked at the entry point) moves by a
+    // wave-uniform amount from quad to quad and tile to tile.
+    const int q4 = (tid & 15) * 4, sub = tid >> 4;
+    const int dlast = ((CVP_ABL & 2) && !cvp_never(D)) ? -1 : D - 1;      // the last disparity that is stored
+    int lim_l[4], lim_r[8];
+    unsigned whole_r = 0;                       // bit k: rows px .. px + 3 of right quad k are rows 1 .. 63, inside the image
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int px = 1 + sub + 16 * k, ww = w0 + px;
+        lim_l[k] = (px < CV_TW && ww < W) ? min(ww, dlast) : -1;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int px = sub + 16 * k - (CV_DT - 1) + q4;
+        lim_r[k] = (px + 3 >= 1 && px < CV_TW) ? min(w0 + px, dlast) : -1;
+        whole_r |= (px >= 1 && px + 3 < CV_TW && w0 + px + 3 < W) ? 1u << k : 0u;
+    }
+    const int Dp4 = Dp * 4;
+    // (modulo 2^32: a quad outside the image row, never stored, may lie beyond either end)
+    const unsigned vo_l = (unsigned)((w0 + 1 + sub) * Dp + q4) * 4u;            // quad 0 of tile 0: pixel w0 + 1 + sub, disparity q4
+    const unsigned vo_r = (unsigned)((w0 - (CV_DT - 1) + sub) * Dp + q4) * 4u; //                   pixel w0 - 63 + sub (tile d0: - d0)
+    char *const lrow = reinterpret_cast<char *>(lcv + rowbase * Dp), *const rrow = reinterpret_cast<char *>(rcv + rowbase * Dp);
     __syncthreads();
 #pragma unroll 1
     for (int d0 = 0; d0 < D && w0 + CV_TW - 1 >= d0; d0 += CV_DT) {   // beyond: every (w, d) has w < d (border fill)
-        // the next tile's 64 new columns w0 - d0 - 127 .. w0 - d0 - 64 on their way (4 x 16 bytes per thread)
-        const bool more = d0 + CV_DT < D && w0 + CV_TW - 1 >= d0 + CV_DT;
-        float4 nx[4];
+        // the next tile's 64 new columns w0 - d0 - 127 .. w0 - d0 - 64 on their way (4 x 16 bytes per thread; behind the
+        // last tile they are fetched for nothing, out of rows the cache holds)
+        cv_f4 nx[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int i = tid + q * 256, x = w0 - d0 - (2 * CV_DT - 1) + (i >> 4), c4 = i & 15;
-            nx[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (more && x >= 0 && x < W) nx[q] = *reinterpret_cast<const float4 *>(fr + (rowbase + x) * CV_C + c4 * 4);
+            // unconditional (clamped address): a load inside a condition makes the compiler's wait bookkeeping join
+            // conservatively, and every later reuse of a register then drains the queue
+            nx[q] = *reinterpret_cast<const cv_f4 *>(fr + (rowbase + min(max(x, 0), W - 1)) * CV_C + c4 * 4);
         }
 #pragma unroll 1
         for (int kk = 0; kk < (((CVP_ABL & 1) && !cvp_never(D)) ? 0 : 8); ++kk) {
@@ -255,51 +323,68 @@ __global__ __launch_bounds__(256, 3) void cost_volume_exact_pairs_kernel(const f
             }
         }
         __syncthreads();                             // products done: the score tile is complete, the oldest ring rows are free
+        // (without a next tile the rows written here are never read: the write stays unconditional like its loads)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int i = tid + q * 256, x = w0 - d0 - (2 * CV_DT - 1) + (i >> 4), c4 = i & 15;
-            if (more) *reinterpret_cast<float4 *>(&sR[(x & (RING - 1)) * CV_LD + c4 * 4]) = nx[q];
+            *reinterpret_cast<cv_f4 *>(&sR[(x & (RING - 1)) * CV_LD + c4 * 4]) = nx[q];
         }
-        const int nd = ((CVP_ABL & 2) && !cvp_never(D)) ? 0 : min(CV_DT, D - d0);   // disparities of this tile that exist
-        const int xr0 = w0 - d0 - (CV_DT - 1);
-        // Both volumes leave as 16-byte stores: 16 lanes x four disparities = one pixel's 64 disparities of this tile,
-        // four pixels per wave instruction (a quarter of the store instructions of the one-float-per-lane form: the
-        // store phase is bound by their count).  A group of four that straddles an edge (w = d, the last disparity, the
-        // image border) goes out float by float.
-        const int q4 = (tid & 15) * 4, sub = tid >> 4;
-        // left volume: pixel w0 + px (px >= 1), disparities d0 .. d0 + nd - 1 (those with d <= w)
-        for (int px = 1 + sub; px < CV_TW; px += 16) {
-            const int ww = w0 + px, d = d0 + q4;
-            if (ww >= W || q4 >= nd || ww < d) continue;
-            const float4 v = *reinterpret_cast<const float4 *>(&sT[px * TP + q4]);
-            float *dst = lcv + (rowbase + ww) * (size_t)Dp + d;
-            if (q4 + 3 < nd && ww >= d + 3) {
-                *reinterpret_cast<float4 *>(dst) = v;
-            } else {
-                const float e[4] = {v.x, v.y, v.z, v.w};
+        const int d = d0 + q4;                       // the first disparity of this thread's quads
+        unsigned rag = 0;                            // this thread's ragged quads: bits 0 .. 3 left, 4 .. 11 right
+        {   // left volume: pixel w0 + px (px >= 1), disparities d0 .. d0 + nd - 1 (those with d <= w)
+            cv_f4 v[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (q4 + j < nd && ww >= d + j) dst[j] = e[j];
+            for (int k = 0; k < 4; ++k)
+                v[k] = *reinterpret_cast<const cv_f4 *>(&sT[min(1 + sub + 16 * k, CV_TW - 1) * TP + q4]);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(v[k]));   // the reads stay ahead of the first store
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const bool full = d + 3 <= lim_l[k];
+                if (__builtin_expect(full, 1)) cvp_store16(lrow + (vo_l + (unsigned)(d0 * 4 + k * 16 * Dp4)), v[k]);
+                rag |= (d <= lim_l[k] && !full) ? 1u << k : 0u;
             }
         }
-        // right volume: pixel x = w - d; its entries of this tile are (w = x + d, d), d0 <= d < d0 + nd: the score tile's
-        // anti-diagonals (four LDS reads per 16-byte store)
-        for (int xi = sub; xi < CV_TW + CV_DT - 1; xi += 16) {
-            const int x = xr0 + xi, d = d0 + q4, px = x + d - w0;      // tile row of w = x + d (first of the four)
-            if (x < 0 || q4 >= nd || px + 3 < 1 || px >= CV_TW) continue;
-            float *dst = rcv + (rowbase + x) * (size_t)Dp + d;
-            if (q4 + 3 < nd && px >= 1 && px + 3 < CV_TW && w0 + px + 3 < W) {
-                float4 v;
-                v.x = sT[px * TP + q4];
-                v.y = sT[(px + 1) * TP + q4 + 1];
-                v.z = sT[(px + 2) * TP + q4 + 2];
-                v.w = sT[(px + 3) * TP + q4 + 3];
-                *reinterpret_cast<float4 *>(dst) = v;
-            } else {
+        {   // right volume: pixel x = w - d; its entries of this tile are (w = x + d, d), d0 <= d < d0 + nd: the score
+            // tile's anti-diagonals (four LDS reads per 16-byte store), in two groups of four quads: eight would not
+            // fit into the registers beside the left features
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (q4 + j < nd && px + j >= 1 && px + j < CV_TW && w0 + px + j < W) dst[j] = sT[(px + j) * TP + q4 + j];
+            for (int k0 = 0; k0 < 8; k0 += 4) {
+                cv_f4 v[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int pc = min(max(sub + 16 * (k0 + k) - (CV_DT - 1) + q4, 0), CV_TW - 4);
+                    v[k].x = sT[pc * TP + q4];
+                    v[k].y = sT[(pc + 1) * TP + q4 + 1];
+                    v[k].z = sT[(pc + 2) * TP + q4 + 2];
+                    v[k].w = sT[(pc + 3) * TP + q4 + 3];
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(v[k]));
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const bool some = d <= lim_r[k0 + k];
+                    const bool full = some && ((whole_r >> (k0 + k)) & 1) && d + 3 <= dlast;
+                    if (__builtin_expect(full, 1))
+                        cvp_store16(rrow + (vo_r + (unsigned)(d0 * 4 + ((k0 + k) * 16 - d0) * Dp4)), v[k]);
+                    rag |= (some && !full) ? 16u << (k0 + k) : 0u;
+                }
             }
+        }
+        // the ragged quads, one per turn (few threads have any, and hardly one has more than two)
+        for (unsigned m = rag & 15u; m; m &= m - 1) {
+            const int k = __builtin_ctz(m), px = 1 + sub + 16 * k, lim = min(w0 + px, dlast);
+            float *dst = reinterpret_cast<float *>(lrow + (vo_l + (unsigned)(d0 * 4 + k * 16 * Dp4)));
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (d + j <= lim) dst[j] = sT[px * TP + q4 + j];
+        }
+        for (unsigned m = rag >> 4; m; m &= m - 1) {
+            const int k = __builtin_ctz(m), px = sub + 16 * k - (CV_DT - 1) + q4;
+            float *dst = reinterpret_cast<float *>(rrow + (vo_r + (unsigned)(d0 * 4 + (k * 16 - d0) * Dp4)));
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (d + j <= dlast && px + j >= 1 && px + j < CV_TW && w0 + px + j < W) dst[j] = sT[(px + j) * TP + q4 + j];
         }
         __syncthreads();                             // the score tile has been read, the ring holds the next tile's rows
     }
