@@ -62,8 +62,12 @@ const char *mccnn_last_error_string(void);
  * recurrences, rcv[d,h,w] = lcv[d,h,w+d] (+ its own border recurrence).  Requires 1 <= D <= W-2.
  * mode MCCNN_CV_EXACT reproduces NumPy's pairwise float32 summation order bit for bit (C must be 64);
  * mode MCCNN_CV_MFMA contracts the 64 channels on the matrix cores (every float32 operand as two f16 numbers, three
- * v_mfma_f32_32x32x16_f16 products per K step, float32 accumulation): |diff| <= 2e-6 on unit-norm features - the
- * features must be unit vectors (|x| <= 1), as NET produces them. */
+ * v_mfma_f32_32x32x16_f16 products per K step, float32 accumulation): within 2e-6 of the float64 dot product, and of
+ * MCCNN_CV_EXACT, on unit-norm features - the features must be unit vectors (|x| <= 1), as NET produces them; within
+ * 8 x the error of NumPy's float32 pairwise sum + 2^-24 (measured: <= 3.6e-7, profiles/parity_cost_volume_mfma.json).
+ * Non-finite and large features in MCCNN_CV_MFMA: a NaN feature propagates - every score of its pixel, and every border
+ * entry filled from such a score, is NaN, the same set of entries as in MCCNN_CV_EXACT.  A finite feature with
+ * |x * 1024| > 65504 is clamped to +-65504 / 1024 (its scores are finite and wrong).  +-inf is outside the contract. */
 #define MCCNN_CV_EXACT 0
 #define MCCNN_CV_MFMA 1
 int mccnn_cost_volume(const float *fl, const float *fr, int H, int W, int C, int D, float *lcv, float *rcv, int mode,
@@ -162,9 +166,13 @@ int mccnn_cross_region_list(const mccnn_support_t *support, int H, int W, int L,
  * out[d,p] = (sum_{q in U(p)} in[d,q]) / count[p];  in != out (ping-pong; the reference does not mutate either).
  * L is the distance threshold the support plane was built with (arms < L; supported: L <= 32); a plane that this
  * library's mccnn_cross_arms built with a larger distance, or for another image size, is refused (MCCNN_E_INVALID).
- * order MCCNN_CBCA_SEPARABLE: horizontal-arm sums then vertical-arm sums evaluated through float64 prefix sums -
- * the correctly rounded region sum, within <= 1e-6 per iteration (O(1) costs) of the reference's sequential float32
- * sum, cost independent of the arm lengths; volumes must be finite (an inf/nan would poison its whole row).
+ * order MCCNN_CBCA_SEPARABLE: horizontal-arm sums then vertical-arm sums.  For L <= 14 they are evaluated through
+ * float64 prefix sums: the correctly rounded region mean - |out - exact mean| <= half a float32 spacing of the mean
+ * + 2^-34 max|in| - within <= 1e-6 per iteration (O(1) costs) of the reference's sequential float32 sum, cost
+ * independent of the arm lengths; volumes must be finite (an inf/nan would poison its whole row).  For 15 <= L <= 32
+ * the arms are summed in plain float32 (up to 63 + 63 sequential additions): NOT correctly rounded,
+ * |out - exact mean| <= (n_h + n_v + 2) 2^-24 (sum over the region of |in|) / count, n_h the longest horizontal span
+ * in the region and n_v its vertical span (measured: up to 8 spacings of the mean on costs of one sign).
  * MCCNN_CBCA_REFERENCE_ORDER: the reference's flat running sum (vertical arm self,up..,down.. x horizontal arm
  * self,left..,right..), bit-exact, slower. */
 #define MCCNN_CBCA_SEPARABLE 0

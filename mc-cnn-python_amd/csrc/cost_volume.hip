@@ -14,8 +14,10 @@
 //
 // MCCNN_CV_EXACT  : VALU kernel that reproduces NumPy's float32 pairwise summation of the 64 products
 //                   (8 running sums, fixed combine tree - numpy loops_utils pairwise_sum) bit for bit.
-// MCCNN_CV_MFMA   : the 64-channel contraction on the matrix cores, v_mfma_f32_32x32x2_f32 (exact-f32 fma chain in
-//                   channel order); differs from NumPy's order by <= 2e-6 on unit-norm features.
+// MCCNN_CV_MFMA   : the 64-channel contraction on the matrix cores: every operand as two f16 numbers (x * 2^10 = hi + lo),
+//                   three v_mfma_f32_32x32x16_f16 products per 16 channels, float32 accumulation; within 2e-6 of the
+//                   float64 dot product on unit-norm features (measured: 3.6e-7 at most, see the kernel); NaN features
+//                   propagate as they do in the exact mode.
 #include "common.h"
 
 namespace mccnn {
@@ -402,8 +404,11 @@ __global__ __launch_bounds__(256, 3) void cost_volume_exact_pairs_kernel(const f
 // to 384, or its stores were rearranged into whole 512-byte runs (a 128 x 64 output-stationary tiling, 1.5 x the
 // products, 121 KiB of LDS: 0.40 ms).  So this version is built for a small footprint instead:
 //   * operands as two f16 numbers each (x * 2^10 = hi + lo; unit vectors, 22 significand bits), three
-//     v_mfma_f32_32x32x16_f16 products per K step (hi*hi + hi*lo + lo*hi), float32 accumulation: <= 3e-7 from the exact
-//     dot product, 384 matrix-core cycles per block;
+//     v_mfma_f32_32x32x16_f16 products per K step (hi*hi + hi*lo + lo*hi), float32 accumulation, 384 matrix-core cycles
+//     per block.  Measured against the float64 dot product over every scored entry (tests/test_cost_volume_mfma_gpu.py,
+//     profiles/parity_cost_volume_mfma.json): <= 9.4e-8 on independent Gaussian unit vectors (scores near 0), <= 2.5e-7
+//     on true matches (fr = +-fl, scores near -+1), <= 3.6e-7 when all components are non-negative - 1.0 to 2.8 times
+//     the error NumPy's float32 pairwise sum makes on the same inputs; exact where the scores are exactly representable;
 //   * the 64 channels staged in two halves (18 KiB for both operand tiles; the second half waits in registers);
 //   * the product tile T diagonal-major but folded: diagonal dd >= 0 (columns dd..63) and diagonal dd - 64 (columns
 //     0..dd-1) share row dd of T[64][68] - 17 KiB instead of 34 - and the quads that straddle the fold are the ragged
@@ -415,13 +420,20 @@ typedef _Float16 cv_h4 __attribute__((ext_vector_type(4)));
 constexpr int CVM_SP = 144;  // LDS bytes per operand pixel and channel half: [K step][hi 32 B | lo 32 B] + 16 pad
 constexpr int CVM_TP = 68;   // LDS pitch of the folded product tile T[(w-x) & 63][w] (floats, 16-byte rows)
 
+// v_med3_f32 returns the minimum of the other two operands when one is NaN: the clamp alone would turn a NaN feature
+// (mccnn_l2norm_chw_to_hwc keeps one on purpose) into -65504 and its scores into finite numbers.  NaN passes instead,
+// through both halves and the matrix cores, and marks every score of its pixel as it does in the exact mode.
+__device__ __forceinline__ float cv_scale_clamp(float v)
+{
+    const float s = v * 1024.f;
+    const float c = __builtin_amdgcn_fmed3f(s, -65504.f, 65504.f);
+    return s != s ? s : c;
+}
+
 __device__ __forceinline__ void cv_split4(const float4 v, cv_h4 &hi, cv_h4 &lo)
 {
-    // unit vectors never get near the clamp (|x| <= 1 -> 1024); it keeps features that are not normalised finite
-    const float x[4] = {__builtin_amdgcn_fmed3f(v.x * 1024.f, -65504.f, 65504.f),
-                        __builtin_amdgcn_fmed3f(v.y * 1024.f, -65504.f, 65504.f),
-                        __builtin_amdgcn_fmed3f(v.z * 1024.f, -65504.f, 65504.f),
-                        __builtin_amdgcn_fmed3f(v.w * 1024.f, -65504.f, 65504.f)};
+    // unit vectors never get near the clamp (|x| <= 1 -> 1024); it keeps finite features that are not normalised finite
+    const float x[4] = {cv_scale_clamp(v.x), cv_scale_clamp(v.y), cv_scale_clamp(v.z), cv_scale_clamp(v.w)};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const _Float16 h = (_Float16)x[j];

@@ -12,7 +12,8 @@
 //                       wave-specialised stages stream 256-column strips of two disparity planes; 8 B/voxel/iteration
 //                       of HBM traffic.
 //   cbca_iter_kernel    LDS-tiled; REFERENCE_ORDER variant walks the region in the reference's list order and is
-//                       bit-exact; its separable variant serves distances > 14.
+//                       bit-exact; its separable variant serves distances > 14 with plain float32 arm sums (not the
+//                       correctly rounded mean of the streaming kernel: tests/test_cbca_separable_gpu.py has its bound).
 #include <math.h>
 
 #include <algorithm>

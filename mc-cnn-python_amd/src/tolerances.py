@@ -6,9 +6,14 @@ The bit-exact variants (the drop-in default) have no tolerance: every stage behi
 to the reference's NumPy, and the features are within FEATURES_ABS of a float64 evaluation of the network.
 
 Where the numbers come from.  The fast variants differ from the reference in three places: split-f16 products in the
-features (<= 2e-6 per unit-vector component), the matrix-core cost volume (<= 2e-6 per cost), and the separable
-float64-prefix aggregation, which returns the correctly rounded region mean where the reference returns its own flat
-float32 running sum (<= 8 float32 spacings of the largest cost per iteration, CBCA_SPACINGS).  WTA takes the argmin of
+features (<= 2e-6 per unit-vector component), the matrix-core cost volume (<= 2e-6 per cost, against the exact mode and
+against the float64 dot product; <= COST_VOLUME_MFMA_E32_FACTOR times the float32 pairwise sum's own error + 2^-24;
+NaN features propagate), and the separable aggregation.  At the default distance (<= 14) that is the float64-prefix
+kernel, which returns the correctly rounded region mean (half a float32 spacing of the mean + 2^-34 max|cost| from a
+float64 evaluation, tests/test_cbca_separable_gpu.py) where the reference returns its own flat float32 running sum
+(<= 8 float32 spacings of the largest cost per iteration, CBCA_SPACINGS).  At distances 15 .. 32 the separable order is
+a plain float32 sum of the arms, NOT correctly rounded: (n_h + n_v + 2) 2^-24 times the region's mean |cost|, n_h and
+n_v the region's horizontal and vertical spans.  WTA takes the argmin of
 the aggregated costs, so a pixel can flip only where two disparities tie to within that error (FAST_WTA_FLIP_FRACTION
 of the pixels; a flipped near-tie moves its pixel by many disparities, which is why no maximum is stated).  The
 sub-pixel parabola divides a cost difference by a second difference that is small on flat cost curves, which turns 1e-6
@@ -28,6 +33,11 @@ FEATURES_F32_CLASS_ABS = 5e-7       # EITHER feature path (library float32 / han
 FEATURES_FINAL_MAP_FRAC_1E3 = {"miopen": 0.999, "split_f16": 0.985}
 FEATURES_FINAL_MAP_FRAC_1E2 = 0.999
 COST_VOLUME_MFMA_ABS = 2e-6         # matrix-core cost volume vs the exact one
+# ... and against the float64 dot product, as a multiple of E32, the error NumPy's float32 pairwise sum (the oracle, the
+# exact mode) makes on the same inputs: E_mfma <= COST_VOLUME_MFMA_E32_FACTOR * E32 + 2^-24.  4 for the two significand
+# bits a split operand lacks (x * 2^10 = hi + lo carries 22), times 2 for an accumulation chain against a pairwise tree;
+# 2^-24 is half a spacing of a score near -1 (tests/test_cost_volume_mfma_gpu.py)
+COST_VOLUME_MFMA_E32_FACTOR = 8
 CBCA_SPACINGS = 8                   # separable aggregation, per iteration, in float32 spacings of max |cost|
 
 FAST_WTA_FLIP_FRACTION = 1e-4       # WTA indices that may differ from the bit-exact variant, per pixel and view
