@@ -489,6 +489,42 @@ int mccnn_confidence_right_hwd(const float *vol_right_hwd /* [H][W][Dp] */, cons
 int mccnn_confidence_right(const float *vol_right_dhw /* [D][H][W] */, const float *disp_left /* NULL unless LRC */, int D,
                            int H, int W, unsigned measures, float *out, mccnn_stream_t stream);
 
+/* ---- semi-dense maps: selection by validity, left-right status and confidence; speckle filter --------------------------
+ * Definitions (binding).
+ *   Valid: a disparity is valid when it is finite and >= 0 (mccnn_evaluate's rule): -0.0f is valid; -1, NaN, +-inf are not.
+ *   Dropped: a dropped pixel holds +inf (bits 0x7F800000, Middlebury's "unknown"); a kept pixel keeps its bits.  An output
+ *     holds nothing else: an input pixel that was already invalid comes out as +inf.
+ * mccnn_semi_dense_select, one launch.  A pixel is kept when all of these hold: it is valid; if require_match is set, its
+ *   status word is 0 (the plane mccnn_lr_status wrote for the left view, mccnn_lr_status_right for the right one); for
+ *   every bit b of `use`, plane_b[h][w] >= min_conf[b] - one float32 compare: a NaN plane value fails, -inf fails every
+ *   finite threshold.  planes is [K][H][W] in ascending bit order of plane_measures, exactly what mccnn_confidence* wrote;
+ *   `use` must be a subset of plane_measures; min_conf is a HOST array of four floats indexed by bit, read at call time
+ *   and passed by value (entries outside `use` are not read); a NaN threshold is refused.  out overlaps no input.
+ * Components and mccnn_speckle_filter.  Two 4-neighbours p and q are linked when both are valid and
+ *   fabsf(disp[p] - disp[q]) <= max_diff: one float32 subtraction, an inclusive compare.  A component is a class of the
+ *   transitive closure of the links (a chain a-b-c is one component even when |a - c| > max_diff); diagonal neighbours
+ *   never link; an invalid pixel belongs to no component and has size 0.  sizes[h][w]: the number of pixels of the
+ *   pixel's component, uint32.  out[h][w] = disp[h][w] when that size is >= min_size, +inf otherwise.
+ *   max_diff >= 0 and not NaN (+inf allowed); min_size >= 1 (1 drops nothing that is valid); out and sizes may each be
+ *   NULL, not both; H*W <= 2^31 - 1, beyond that MCCNN_E_UNSUPPORTED.  scratch: mccnn_speckle_scratch_bytes(H, W) bytes,
+ *   16-byte aligned, private to one call in flight; the call clears what it needs of it on the stream, so calls may follow
+ *   each other on one scratch.
+ *   Four launches whose number and sizes depend on H and W alone, no read-back, no allocation, no synchronisation, and no
+ *   wait on another workgroup: capturable, and the outputs are a function of the map alone (integer minima and sums).
+ *   Rows are not put on grid.y: neither wide rows nor H > 65535 take another path.
+ * The rule of a semi-dense map is sparse = speckle_filter(select(map)): components are taken over the pixels that
+ *   survived the selection.
+ * Refused before any HIP call (MCCNN_E_INVALID): null required pointers, non-positive sizes, `use` not a subset of
+ *   plane_measures or bits above 15, require_match with a null status, overlapping output, a scratch that overlaps a
+ *   map; a misaligned or short scratch is MCCNN_E_SCRATCH.  A refused call writes nothing. */
+int mccnn_semi_dense_select(const float *disp, const int32_t *status /* NULL unless require_match */,
+                            const float *planes /* [K][H][W]; NULL allowed when use == 0 */, int H, int W,
+                            unsigned plane_measures, unsigned use, const float *min_conf /* host [4] */, int require_match,
+                            float *out, mccnn_stream_t stream);
+size_t mccnn_speckle_scratch_bytes(int H, int W);   /* 0 for non-positive sizes and beyond the pixel limit */
+int mccnn_speckle_filter(const float *disp, int H, int W, float max_diff, unsigned min_size, float *out /* or NULL */,
+                         uint32_t *sizes /* or NULL */, void *scratch, size_t scratch_bytes, mccnn_stream_t stream);
+
 /* ---- a10 median_filter (pf:403-421): clipped fh x fw window (odd sizes, fh*fw <= 49), np.median -------------
  * np.median to the bit: NaN in the window gives NaN, and a median of -0.0 is +0.0 (np.mean's sum starts from +0).
  * Other window sizes and H > 65535 (rows go on grid.y): MCCNN_E_UNSUPPORTED. */

@@ -107,6 +107,11 @@ class Middlebury(object):
         """match.py --confidence: the plane of `measure` beside disp0MCCNN.pfm (view 1, --views both: conf1MCCNN_*)."""
         return os.path.join(paths["res_dir"], "conf%dMCCNN_%s.pfm" % (int(view), measure))
 
+    def sparse_path(self, paths, view=0):
+        """match.py --semi_dense: the sparse map beside disp0MCCNN.pfm, named as Middlebury's sparse track names it (view
+        1, --views both: disp1MCCNN_s.pfm)."""
+        return os.path.join(paths["res_dir"], "disp%dMCCNN_s.pfm" % int(view))
+
     def evaluator(self, thresholds, slots=1, interpolate=False, device=None, quantiles=None):
         import evaluation
         return evaluation.Evaluator(device, thresholds, slots, quantiles=quantiles)

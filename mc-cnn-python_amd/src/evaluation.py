@@ -524,6 +524,34 @@ def mean_sparsification(figures):
                 auc={n: mean(f["auc"][n] for f in figures) for n in names})
 
 
+def semi_dense_block(metrics, rule=None):
+    """The "semi_dense" block of a sparse map (match.py --semi_dense --evaluate) from the Metrics of mccnn_evaluate on it -
+    a dropped pixel (+inf) counts as invalid there: Metrics.to_dict(), `density` per region = 100 (n_valid - n_invalid) /
+    n_valid, `bad_of_scored` per region and threshold = 100 n_bad / (n_valid - n_invalid), None when nothing is scored;
+    and the rule's text where given."""
+    out = dict(metrics.to_dict())
+    out["density"], out["bad_of_scored"] = {}, {}
+    for r in REGIONS:
+        raw = metrics.raw[r]
+        n_valid, scored = raw["n_valid"], raw["n_valid"] - raw["n_invalid"]
+        out["density"][r] = 100.0 * scored / n_valid if n_valid > 0 else None
+        out["bad_of_scored"][r] = {threshold_tag(t): (100.0 * b / scored if scored > 0 else None)
+                                   for t, b in zip(metrics.thresholds, raw["n_bad"])}
+    if rule is not None:
+        out["rule"] = rule
+    return out
+
+
+def semi_dense_mean(metrics):
+    """mean_of() over the sparse maps of a list, with the unweighted means of `density` and `bad_of_scored` besides."""
+    out = mean_of(metrics)
+    blocks = [semi_dense_block(m) for m in metrics]
+    tags = list(blocks[0]["bad_of_scored"][REGIONS[0]]) if blocks else []
+    out["density"] = {r: mean(b["density"][r] for b in blocks) for r in REGIONS}
+    out["bad_of_scored"] = {r: {t: mean(b["bad_of_scored"][r][t] for b in blocks) for t in tags} for r in REGIONS}
+    return out
+
+
 def write_json(path, obj):
     with open(path, "w") as f:
         json.dump(obj, f, indent=1, sort_keys=True)
@@ -534,10 +562,13 @@ class _ViewBook(object):
     """One view's part of a ListReport: the scored maps by list index, the pairs skipped for this view, and the
     evaluator whose device total pools the view over the list."""
 
-    def __init__(self, evaluator):
+    def __init__(self, evaluator, semi_evaluator=None, rule=None):
         self.evaluator = evaluator
         self.scored = {}         # index -> (Metrics, the map's sparsification figures or None: match.py --confidence)
         self.skipped = {}        # index -> name
+        # match.py --semi_dense: the evaluator whose device total pools the view's SPARSE maps, the rule's text, and
+        # index -> Metrics of the pair's sparse map
+        self.semi_evaluator, self.rule, self.semi = semi_evaluator, rule, {}
 
     def block(self, index):
         """The view's fields in a pair's entry: the metrics, with --confidence also "sparsification" (without it no
@@ -545,7 +576,8 @@ class _ViewBook(object):
         if index not in self.scored:
             return None
         metrics, figures = self.scored[index]
-        return dict(metrics.to_dict(), **(dict(sparsification=figures) if figures is not None else {}))
+        semi = dict(semi_dense=semi_dense_block(self.semi[index], self.rule)) if index in self.semi else {}
+        return dict(metrics.to_dict(), **(dict(sparsification=figures) if figures is not None else {}), **semi)
 
     def totals(self):
         """The view's fields in the list's file: the device total, the means over the scored pairs, the skipped."""
@@ -554,8 +586,12 @@ class _ViewBook(object):
         figures = [self.scored[i][1] for i in order if self.scored[i][1] is not None]
         if figures:
             means["sparsification"] = mean_sparsification(figures)
+        semi = {}
+        if self.semi_evaluator is not None:
+            semi = dict(semi_dense=dict(rule=self.rule, pooled=semi_dense_block(self.semi_evaluator.report()),
+                                        mean=semi_dense_mean([self.semi[i] for i in order if i in self.semi])))
         return dict(pooled=self.evaluator.report().to_dict(), mean=means,
-                    skipped=[self.skipped[i] for i in sorted(self.skipped)])
+                    skipped=[self.skipped[i] for i in sorted(self.skipped)], **semi)
 
 
 class ListReport(object):
@@ -564,22 +600,32 @@ class ListReport(object):
 
     One book per view.  The right one (match.py --views both) has a second evaluator, whose total pools the RIGHT maps
     against disp1GT.pfm; a pair's right view is scored where its left view is and it has that file, and listed as skipped
-    for the right view otherwise.  Without a right evaluator no file has a "right" key."""
+    for the right view otherwise.  Without a right evaluator no file has a "right" key.
+    semi (match.py --semi_dense): (the rule's text, an evaluator for the left view's sparse maps, one for the right view's
+    or None); every view's block and totals then carry "semi_dense".  Without it no file has that key."""
 
-    def __init__(self, evaluator, right_evaluator=None):
+    def __init__(self, evaluator, right_evaluator=None, semi=None):
         self.evaluator, self.right_evaluator = evaluator, right_evaluator
         self.extra = evaluator.describe() if hasattr(evaluator, "describe") else {}     # more keys in every file
-        self.left, self.right = _ViewBook(evaluator), _ViewBook(right_evaluator)
+        rule, semi_left, semi_right = semi if semi is not None else (None, None, None)
+        self.semi_evaluators = (semi_left, semi_right) if semi is not None else None
+        self.left, self.right = _ViewBook(evaluator, semi_left, rule), _ViewBook(right_evaluator, semi_right, rule)
         self.names = {}          # index -> name, of the pairs whose left map was scored
 
     def _entry(self, index):
         right = self.right.block(index)
         return dict(self.left.block(index), pair=self.names[index], **(dict(right=right) if right is not None else {}))
 
-    def pair(self, index, name, metrics, path=None, sparsification=None, right=None):
-        """right: None or dict(metrics=Metrics, sparsification=figures or None).  A second call replaces the first."""
+    def pair(self, index, name, metrics, path=None, sparsification=None, right=None, semi_dense=None):
+        """right: None or dict(metrics=Metrics, sparsification=figures or None); semi_dense: None or the Metrics of the
+        sparse maps of the views that were scored, the left one first.  A second call replaces the first."""
         self.names[index] = name
         self.left.scored[index] = (metrics, sparsification)
+        for book, m in zip((self.left, self.right), tuple(semi_dense or ()) + (None, None)):
+            if m is not None:
+                book.semi[index] = m
+            else:
+                book.semi.pop(index, None)
         if right is not None:
             self.right.scored[index] = (right["metrics"], right.get("sparsification"))
         else:
@@ -605,6 +651,7 @@ class Scored(object):
 
     def __init__(self, index, name, truths):
         self.index, self.name, self.truths, self.scores = index, name, truths, None
+        self.semi = None         # --semi_dense: per view the PairScore of the sparse map kept so far
 
 
 class ListScorer(object):
@@ -644,20 +691,32 @@ class ListScorer(object):
             yield (self.evaluators[v], maps[v] if self.both else maps,
                    planes[v] if (self.both and planes is not None) else planes, gt, mask)
 
-    def score(self, scored, maps, planes, slot):
-        """Per view the evaluation, then (--confidence) the sparsification; replaces what the record holds."""
+    def _sparse_views(self, scored, sparse):
+        """(evaluator, sparse map, gt, mask) of every scored view (--semi_dense), the left one first."""
+        for v, (gt, mask) in enumerate(scored.truths):
+            yield self.report.semi_evaluators[v], sparse[v] if self.both else sparse, gt, mask
+
+    def score(self, scored, maps, planes, slot, sparse=None):
+        """Per view the evaluation, then (--confidence) the sparsification; replaces what the record holds.  sparse
+        (--semi_dense): the views' sparse maps, scored behind them by evaluators of their own."""
         scored.scores = [(e.score(m, gt, mask, slot), self.sparsifier.score(m, p, gt) if self.sparsifier is not None else None)
                          for e, m, p, gt, mask in self._views(scored, maps, planes)]
+        if sparse is not None:
+            scored.semi = [e.score(m, gt, mask, slot) for e, m, gt, mask in self._sparse_views(scored, sparse)]
 
-    def commit(self, scored, maps):
+    def commit(self, scored, maps, sparse=None):
         """The maps that are kept into the running totals (Evaluator.commit keeps the commits in call order)."""
         for e, m, _, gt, mask in self._views(scored, maps):
             e.commit(m, gt, mask)
+        if sparse is not None:
+            for e, m, gt, mask in self._sparse_views(scored, sparse):
+                e.commit(m, gt, mask)
 
     def publish(self, scored, json_path):
         """The pair's entry of the report and its evalMCCNN.json, from the scores the record holds now."""
         views = [dict(metrics=s.metrics(), sparsification=a.figures() if a is not None else None) for s, a in scored.scores]
+        semi = dict(semi_dense=[s.metrics() for s in scored.semi]) if scored.semi is not None else {}
         self.report.pair(scored.index, scored.name, views[0]["metrics"], json_path,
-                         sparsification=views[0]["sparsification"], right=views[1] if len(views) > 1 else None)
+                         sparsification=views[0]["sparsification"], right=views[1] if len(views) > 1 else None, **semi)
 
 

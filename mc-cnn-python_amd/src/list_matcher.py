@@ -261,20 +261,38 @@ def map_and_planes(result):
     return result if isinstance(result, tuple) else (result, None)
 
 
-def make_writer(rank=0, log=print, scorer=None, eval_file="evalMCCNN.json", save=_save_middlebury, save_confidence=None):
+def split_result(result):
+    """What a matcher returns, as (map, planes or None, sparse or None): the planes (--confidence) have one dimension
+    more than the map, the sparse map (--semi_dense) has the map's."""
+    if not isinstance(result, tuple):
+        return result, None, None
+    planes = sparse = None
+    for t in result[1:]:
+        if t.ndim == result[0].ndim:
+            sparse = t
+        else:
+            planes = t
+    return result[0], planes, sparse
+
+
+def make_writer(rank=0, log=print, scorer=None, eval_file="evalMCCNN.json", save=_save_middlebury, save_confidence=None,
+                save_sparse=None):
     """write(job, result, seconds) for ListPipeline: the three files of match.py, with the existing util functions; with a
     `scorer` (evaluation.ListScorer, match.py --evaluate) also the evaluation of a pair that was scored (job.scored: of
     the map these files hold, or of the repeat that replaces it), once its bytes are on the host.  `save(map, paths)`
     writes the map and its preview (datasets.py: a KITTI layout's is the 16-bit plane); a result (map, planes) also has
-    its planes written by `save_confidence(planes, paths)` - a repeated pair's files get the repeated pair's planes."""
+    its planes written by `save_confidence(planes, paths)` - a repeated pair's files get the repeated pair's planes -
+    and one with a sparse map (--semi_dense) has that written by `save_sparse(sparse, paths)`."""
     from datetime import datetime
 
     def write(job, result, seconds):
         p = job.paths
-        disparity, planes = map_and_planes(result)
+        disparity, planes, sparse = split_result(result)
         save(disparity, p)
         if planes is not None:
             save_confidence(planes, p)
+        if sparse is not None:
+            save_sparse(sparse, p)
         util.saveTimeFile(seconds, p["out_time"])
         log("[{}] {}: {:.3f} s -> {}".format(rank, datetime.now(), seconds, p["out"]))
         if scorer is not None and job.scored is not None:
@@ -283,11 +301,14 @@ def make_writer(rank=0, log=print, scorer=None, eval_file="evalMCCNN.json", save
 
 
 class Ticket(object):
-    def __init__(self, host, done, device_map=None, host_planes=None, device_planes=None):
+    def __init__(self, host, done, device_map=None, host_planes=None, device_planes=None, host_sparse=None,
+                 device_sparse=None):
         # device_map: what an evaluation scores (a KITTI layout: what the written PNG holds, not the matcher's map)
         self.host, self.done, self.device_map = host, done, device_map
         # with --confidence: the planes in a second pinned buffer, copied behind the map, and where they are on the device
         self.host_planes, self.device_planes = host_planes, device_planes
+        # with --semi_dense: the sparse map in a pinned buffer of its own, and where it is on the device
+        self.host_sparse, self.device_sparse = host_sparse, device_sparse
 
 
 class MatcherBackend(object):
@@ -321,7 +342,7 @@ class MatcherBackend(object):
 
     def _to_host(self, result):
         torch = self.torch
-        disparity, planes = map_and_planes(result)
+        disparity, planes, sparse = split_result(result)
         crossing, scored = disparity, disparity
         if self.device_output is not None:
             crossing, scored = self.device_output(disparity, self.scorer is not None)
@@ -331,9 +352,13 @@ class MatcherBackend(object):
         if planes is not None:
             host_planes = torch.empty(tuple(planes.shape), dtype=planes.dtype, pin_memory=True)
             host_planes.copy_(planes, non_blocking=True)
+        host_sparse = None
+        if sparse is not None:
+            host_sparse = torch.empty(tuple(sparse.shape), dtype=sparse.dtype, pin_memory=True)
+            host_sparse.copy_(sparse, non_blocking=True)
         done = torch.cuda.Event()
         done.record()
-        return Ticket(host, done, scored, host_planes, planes)
+        return Ticket(host, done, scored, host_planes, planes, host_sparse, sparse)
 
     def _truth(self, gt, mask, dev):
         """The reader's pinned ground truth on its way to the device, behind the pair on the slot's stream."""
@@ -353,14 +378,13 @@ class MatcherBackend(object):
                 truth_right = self._truth(job.gt_right, job.mask_right, m.device) if job.gt is not None else None
                 job.scored = self.scorer.begin(job.index, job.name, self._truth(job.gt, job.mask, m.device), truth_right)
                 if job.scored is not None:
-                    self.scorer.score(job.scored, ticket.device_map, ticket.device_planes, slot)
+                    self.scorer.score(job.scored, ticket.device_map, ticket.device_planes, slot, ticket.device_sparse)
             return ticket
 
     def wait(self, ticket):
         ticket.done.synchronize()
-        if ticket.host_planes is None:
-            return ticket.host.numpy()
-        return ticket.host.numpy(), ticket.host_planes.numpy()
+        extra = tuple(t.numpy() for t in (ticket.host_planes, ticket.host_sparse) if t is not None)
+        return (ticket.host.numpy(),) + extra if extra else ticket.host.numpy()
 
     def retire(self, slot, job, ticket):
         ticket.done.synchronize()
@@ -376,8 +400,8 @@ class MatcherBackend(object):
             # slot's next pair, which overwrites a replayed graph's static output
             with self._stream(slot):
                 if again is not None:
-                    self.scorer.score(scored, again.device_map, again.device_planes, slot)   # not the discarded map
-                self.scorer.commit(scored, ticket.device_map)
+                    self.scorer.score(scored, again.device_map, again.device_planes, slot, again.device_sparse)   # not the discarded map
+                self.scorer.commit(scored, ticket.device_map, ticket.device_sparse)
             if again is not None:
                 self.torch.cuda.synchronize()    # the library matcher's output is overwritten by the next repeat
         return again

@@ -38,7 +38,8 @@ import datasets
 import evaluation          # (neither module touches torch or the GPU on import: util.pin_gpu comes first, in main)
 import list_matcher
 import util
-from list_matcher import map_and_planes
+from list_matcher import split_result
+from semi_dense_rule import SemiDenseRule
 
 # Flag names, types and defaults are the reference's command line (match.py:15-43) - that is the drop-in contract;
 # the help texts are this project's.
@@ -178,6 +179,16 @@ parser.add_argument("--views", choices=("left", "both"), default="left",
                          "mask1nocc.png) beside im0.png: a \"right\" block in evalMCCNN.json and eval.json, a pair without "
                          "disp1GT.pfm listed as skipped for the right view.  timeMCCNN.txt stays the whole pair's time.  "
                          "Not with a KITTI --dataset.  Without it every file keeps its bytes")
+parser.add_argument("--semi_dense", type=str, default=None, metavar="RULE",
+                    help="a semi-dense map beside every map: comma-separated items lr (keep left-right matches), "
+                         "<msm|mmn|cur|lrc>:<min> (keep pixels whose confidence reaches min; the measure must be among "
+                         "--confidence) and speckle:<min_size>[:<max_diff>] (drop 4-connected blobs of similar disparity "
+                         "smaller than min_size; max_diff defaults to 1.0), e.g. lr,speckle:20:1 (include/mccnn.h defines "
+                         "them).  Written as disp0MCCNN_s.pfm beside disp0MCCNN.pfm (--views both: also disp1MCCNN_s.pfm), "
+                         "dropped pixels as inf; with --evaluate a \"semi_dense\" block (the sparse map's figures, its "
+                         "density and the bad share among the kept pixels) in evalMCCNN.json and eval.json; "
+                         "--eval_quantiles and the sparsification stay figures of the dense map.  Not with a KITTI "
+                         "--dataset.  Without it every file keeps its bytes")
 
 CONFIDENCE_MEASURES = ("msm", "mmn", "cur", "lrc")      # stereo_device.CONFIDENCE_MEASURES (not imported before the GPU is pinned)
 
@@ -216,7 +227,8 @@ def hyper_parameters(args):
 # a pair launched and not yet written: the matcher's map and planes, what crosses to the host and what is scored
 # (layout.device_output), the event behind all of it, the start of its time, its paths, the matcher's inputs (a repeat
 # needs them), its slot and its scoring record (evaluation.Scored, or None)
-Pending = collections.namedtuple("Pending", "maps planes crossing kept done started paths images slot scored")
+# (sparse: the semi-dense map of --semi_dense, or None)
+Pending = collections.namedtuple("Pending", "maps planes crossing kept done started paths images slot scored sparse")
 
 
 class ListLoop(object):
@@ -224,13 +236,14 @@ class ListLoop(object):
     and, with --pairs_in_flight N > 1, one stream per slot) and writes its files when the slot comes round again.
 
     layout: datasets.py; redo: stereo_device.SaturationRedo; scorer: evaluation.ListScorer or None (--evaluate);
-    save_maps(host map, paths), save_confidence(host planes, paths): the files of what crossed to the host."""
+    save_maps(host map, paths), save_confidence(host planes, paths), save_sparse(host sparse map, paths): the files of
+    what crossed to the host."""
 
-    def __init__(self, layout, matchers, streams, redo, scorer, save_maps, save_confidence, rank):
+    def __init__(self, layout, matchers, streams, redo, scorer, save_maps, save_confidence, rank, save_sparse=None):
         import torch
         self.torch = torch
         self.layout, self.matchers, self.streams, self.redo, self.scorer = layout, matchers, streams, redo, scorer
-        self.save_maps, self.save_confidence, self.rank = save_maps, save_confidence, rank
+        self.save_maps, self.save_confidence, self.save_sparse, self.rank = save_maps, save_confidence, save_sparse, rank
         self.pending = []            # oldest first
 
     def _stream(self, slot):
@@ -251,7 +264,7 @@ class ListLoop(object):
         with self._stream(slot):
             dev_l = torch.from_numpy(left_image).cuda()
             dev_r = torch.from_numpy(right_image).cuda()
-            maps, planes = map_and_planes(self.matchers[slot].match(dev_l, dev_r, ndisp))
+            maps, planes, sparse = split_result(self.matchers[slot].match(dev_l, dev_r, ndisp))
             # what crosses to the host and what is scored: the map, or a KITTI layout's 16-bit code and what it holds,
             # behind the map on this stream - and behind that the evaluation
             crossing, kept = self.layout.device_output(maps, truth is not None)
@@ -259,38 +272,42 @@ class ListLoop(object):
             if self.scorer is not None:
                 scored = self.scorer.begin(index, paths["left"], self._to_device(truth), self._to_device(truth_right))
             if scored is not None:
-                self.scorer.score(scored, kept, planes, slot)
+                self.scorer.score(scored, kept, planes, slot, sparse)
             done = torch.cuda.Event()
             done.record()
-        self.pending.append(Pending(maps, planes, crossing, kept, done, started, paths, (dev_l, dev_r, ndisp), slot, scored))
+        self.pending.append(Pending(maps, planes, crossing, kept, done, started, paths, (dev_l, dev_r, ndisp), slot, scored,
+                                    sparse))
 
     def finish(self):
         """Collects and writes the oldest pair."""
         torch = self.torch
         p = self.pending.pop(0)
         p.done.synchronize()
-        planes, crossing, kept = p.planes, p.crossing, p.kept
+        planes, crossing, kept, sparse = p.planes, p.crossing, p.kept, p.sparse
         redone = self.redo.due()
         if redone:
             library = self.redo.matcher()
             print("[{}] ".format(self.rank) + self.redo.notice(p.paths["out"]))
-            maps, planes = map_and_planes(library.match(*p.images))
+            maps, planes, sparse = split_result(library.match(*p.images))
             crossing, kept = self.layout.device_output(maps, p.scored is not None)
             torch.cuda.synchronize()
         if p.scored is not None:
             # the total takes the map that is kept, once, in list order; a repeated pair is scored again
             with self._stream(p.slot):
                 if redone:
-                    self.scorer.score(p.scored, kept, planes, p.slot)
-                self.scorer.commit(p.scored, kept)
+                    self.scorer.score(p.scored, kept, planes, p.slot, sparse)
+                self.scorer.commit(p.scored, kept, sparse)
             if redone:
                 torch.cuda.synchronize()     # the library matcher's output is overwritten by the next repeat
         host_map = crossing.cpu().numpy()            # the float32 map, or a KITTI layout's 16-bit plane
         host_planes = planes.cpu().numpy() if planes is not None else None
+        host_sparse = sparse.cpu().numpy() if sparse is not None else None
         seconds = time.time() - p.started
         self.save_maps(host_map, p.paths)
         if host_planes is not None:
             self.save_confidence(host_planes, p.paths)
+        if host_sparse is not None:
+            self.save_sparse(host_sparse, p.paths)
         util.saveTimeFile(seconds, p.paths["out_time"])
         print("[{}] {}: {:.3f} s -> {}".format(self.rank, datetime.now(), seconds, p.paths["out"]))
         if p.scored is not None:
@@ -378,6 +395,19 @@ def main(argv=None):
             eval_quantiles = evaluation.parse_quantiles(args.eval_quantiles)
         except ValueError as e:
             parser.error("--eval_quantiles: %s" % e)
+    semi_rule = None
+    if args.semi_dense is not None:
+        if layout.kitti:
+            parser.error("--semi_dense is not available with --dataset %s: the development kit's handling of sparse maps "
+                         "is --eval_interpolate's" % args.dataset)
+        try:
+            semi_rule = SemiDenseRule.parse(args.semi_dense)
+        except ValueError as e:
+            parser.error("--semi_dense: %s" % e)
+        missing = [n for n in semi_rule.measures if n not in conf_names]
+        if missing:
+            parser.error("--semi_dense reads the confidence measure %s, which --confidence does not name"
+                         % ", ".join(missing))
     both = args.views == "both"
     if both and layout.kitti:
         parser.error("--views both is not available with --dataset %s: the KITTI development kit has neither right-view "
@@ -434,7 +464,12 @@ def main(argv=None):
                         interpolation_directions=16 if args.paper_interpolation else 4,
                         occlusion_from_left=args.paper_interpolation, numpy1_promotion=args.numpy1_promotion,
                         sgm_independent_directions=args.paper_sgm),
-            confidence=conf_names, views=args.views)
+            confidence=conf_names, views=args.views, semi_dense=semi_rule)
+
+    def save_sparse(sparse, out):
+        """The sparse map's PFM from the host map [H,W] (--views both: [2,H,W], the right view's as disp1MCCNN_s.pfm)."""
+        for view, view_map in enumerate(sparse if both else (sparse,)):
+            util.writePfm(view_map, layout.sparse_path(out, view))
 
     def save_confidence(planes, out):
         """One PFM per measure from the host planes [K,H,W] (layout.confidence_path names the file); --views both:
@@ -462,7 +497,7 @@ def main(argv=None):
     matchers = [make_matcher("miopen" if args.features == "library" else "auto") for _ in range(in_flight)]
     footprint_kw = dict(pairs_in_flight=in_flight, arch=args.arch,
                         fc_units=net.num_fc_units if accurate else sd.DECISION_UNITS, confidence=len(conf_names),
-                        views=args.views)
+                        views=args.views, **(dict(semi_dense=True) if semi_rule is not None else {}))
 
     def footprint(height, width, ndisp):        # refuses a shape outside the envelope, with its message
         return sd.workspace_bytes(height, width, ndisp, matchers[0].pixel_major(),
@@ -480,7 +515,11 @@ def main(argv=None):
     if args.evaluate:
         report = evaluation.ListReport(
             layout.evaluator(eval_thresholds, slots=in_flight, interpolate=args.eval_interpolate, quantiles=eval_quantiles),
-            layout.evaluator(eval_thresholds, slots=in_flight, quantiles=eval_quantiles) if both else None)
+            layout.evaluator(eval_thresholds, slots=in_flight, quantiles=eval_quantiles) if both else None,
+            # (--semi_dense: one more evaluator per view, whose total pools the view's sparse maps; no quantiles)
+            **(dict(semi=(semi_rule.describe(), layout.evaluator(eval_thresholds, slots=in_flight),
+                          layout.evaluator(eval_thresholds, slots=in_flight) if both else None))
+               if semi_rule is not None else {}))
         scorer = evaluation.ListScorer(report, evaluation.Sparsifier(conf_names, auc_threshold) if conf_names else None,
                                        args.views)
     eval_path = os.path.join(result_root, "eval.json" if world == 1 else "eval_rank{}.json".format(rank))
@@ -494,7 +533,8 @@ def main(argv=None):
             shape=(lambda left, image: layout.shape(left, ndisp_flag, image)) if layout.kitti else None,
             truth_right=layout.load_truth_right if (args.evaluate and both) else None)
         writer = list_matcher.make_writer(rank, scorer=scorer, eval_file=out_eval_file, save=save_maps,
-                                          save_confidence=save_confidence if conf_names else None)
+                                          save_confidence=save_confidence if conf_names else None,
+                                          save_sparse=save_sparse if semi_rule is not None else None)
         pipeline = list_matcher.ListPipeline(reader, backend, writer, slots=in_flight, readers=args.readers)
         try:
             pipeline.run(indices)
@@ -502,7 +542,7 @@ def main(argv=None):
             print("[{}] {}".format(rank, pipeline.summary()))
     else:
         loop = ListLoop(layout, matchers, streams, sd.SaturationRedo(matchers, make_library_matcher), scorer, save_maps,
-                        save_confidence, rank)
+                        save_confidence, rank, save_sparse)
         loop.run(indices, paths, lambda left_path: layout.shape(left_path, ndisp_flag), footprint)
     if scorer is not None:
         scorer.report.write(eval_path)

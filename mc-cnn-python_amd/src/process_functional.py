@@ -56,7 +56,8 @@ _CBCA_ORDERS = {"separable": hip.MCCNN_CBCA_SEPARABLE, "reference": hip.MCCNN_CB
 
 __all__ = ["compute_features", "compute_cost_volume", "compute_cost_volume_accurate", "cost_volume_aggregation", "SGM_average",
            "disparity_prediction", "interpolation", "subpixel_enhance", "median_filter", "bilateral_filter",
-           "semi_global_matching", "compute_cross_region", "confidence_measures", "interpolation_right"]
+           "semi_global_matching", "compute_cross_region", "confidence_measures", "interpolation_right", "semi_dense",
+           "speckle_filter"]
 
 
 def _dev(x, dtype=torch.float32):
@@ -340,3 +341,33 @@ def confidence_measures(left_cost_volume, right_disparity_map=None, measures=CON
     names = sd.confidence_names(measures)
     planes = sd.confidence(v, dr, names, view=view)
     return dict((n, _ret(planes[i].clone(), was_np)) for i, n in enumerate(names))
+
+
+def semi_dense(disparity_map, rule, status=None, planes=None, measures=()):
+    """Not in the reference: the semi-dense map of `disparity_map` under `rule` (a stereo_device.SemiDenseRule or its text,
+    e.g. "lr,speckle:20:1"; include/mccnn.h has the definitions): kept pixels keep their bits, dropped ones hold +inf.
+    status: the int32 [H,W] left-right status of the map (0 = match), needed by `lr`; planes: the confidence planes the
+    rule reads - {measure: [H,W] map} as confidence_measures() returns them, or a [K,H,W] array in the order of
+    `measures`."""
+    rule = sd.SemiDenseRule.parse(rule)
+    d, was_np = _dev(disparity_map)
+    if isinstance(planes, dict):
+        measures = sd.confidence_names(tuple(planes))
+        planes = torch.stack([_dev(planes[n])[0] for n in measures])
+    elif planes is not None:
+        measures, planes = sd.confidence_names(measures), _dev(planes)[0]
+    if status is None or torch.is_tensor(status):
+        st = None if status is None else status.to(device=d.device, dtype=torch.int32).contiguous()
+    else:
+        st = torch.from_numpy(np.ascontiguousarray(status, dtype=np.int32)).to(d.device)
+    return _ret(sd.semi_dense(d, rule, st, planes, measures), was_np)
+
+
+def speckle_filter(disparity_map, min_size, max_diff=1.0, return_sizes=False):
+    """Not in the reference: drops (+inf) every pixel whose 4-connected component - neighbours both valid and no further
+    apart than max_diff - has fewer than min_size pixels.  return_sizes: -> (map, uint32 [H,W] component sizes)."""
+    d, was_np = _dev(disparity_map)
+    out, sizes = sd.speckle_filter(d, min_size, max_diff, want_sizes=return_sizes)
+    if not return_sizes:
+        return _ret(out, was_np)
+    return _ret(out, was_np), (sizes.cpu().numpy().view(np.uint32) if was_np else sizes)

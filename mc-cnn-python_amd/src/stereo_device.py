@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 import _hipabi as hip
+from semi_dense_rule import SemiDenseRule  # noqa: F401  (host-only: match.py parses it before the GPU is pinned)
 
 
 def _f32(x):
@@ -1395,6 +1396,94 @@ def median(dl, fh, fw, out=None):
     return out
 
 
+# ---- semi-dense maps: selection and speckle filter (include/mccnn.h has the definitions; csrc/semi_dense.hip) ----------
+DROPPED = float("inf")      # what a dropped pixel holds: Middlebury's "unknown"
+
+
+def _check_map(t, who, name="the map"):
+    if t.dim() != 2 or t.dtype != torch.float32:
+        raise ValueError("%s: %s must be a float32 [H,W] tensor, got %s %s" % (who, name, t.dtype, tuple(t.shape)))
+
+
+def semi_dense_select(disp, status=None, planes=None, plane_names=(), thresholds=None, require_match=False, out=None):
+    """mccnn_semi_dense_select: `disp` where it is valid, its `status` word (int32 [H,W]) is 0 if require_match, and every
+    plane named in `thresholds` ({measure: min}) reaches its value; +inf elsewhere.  planes: [K,H,W] in the order of
+    plane_names, as confidence*() wrote them."""
+    who = "semi_dense_select"
+    _check_map(disp, who)
+    H, W = disp.shape
+    thresholds = dict((n, _f32(v)) for n, v in dict(thresholds or {}).items())
+    if any(math.isnan(v) for v in thresholds.values()):
+        raise ValueError("%s: a NaN threshold" % who)
+    plane_names = (plane_names,) if isinstance(plane_names, str) else tuple(plane_names)
+    have = confidence_mask(plane_names) if plane_names else 0
+    use = confidence_mask(tuple(thresholds)) if thresholds else 0
+    missing = [n for n in confidence_names(use) if not _CONFIDENCE_BITS[n] & have] if use else []
+    if missing:
+        raise ValueError("%s: the rule reads %s, which the planes do not hold" % (who, ", ".join(missing)))
+    if use:
+        k = bin(have).count("1")
+        if planes is None or tuple(planes.shape) != (k, H, W) or planes.dtype != torch.float32:
+            raise ValueError("%s: `planes` must be a float32 [%d,%d,%d] tensor" % (who, k, H, W))
+    if require_match and (status is None or tuple(status.shape) != (H, W) or status.dtype != torch.int32):
+        raise ValueError("%s: require_match needs an int32 [%d,%d] status map" % (who, H, W))
+    if out is None:
+        out = torch.empty_like(disp)
+    elif tuple(out.shape) != (H, W) or out.dtype != torch.float32:
+        raise ValueError("%s: `out` must be a float32 [%d,%d] tensor" % (who, H, W))
+    mc = (ctypes.c_float * 4)(*[thresholds.get(n, 0.0) for n in CONFIDENCE_MEASURES])
+    hip.check(hip.load().mccnn_semi_dense_select(
+        hip.ptr(disp), hip.ptr(status) if require_match else None, hip.ptr(planes) if use else None, H, W, have, use, mc,
+        1 if require_match else 0, hip.ptr(out), hip.stream()), "mccnn_semi_dense_select")
+    return out
+
+
+def speckle_scratch(H, W, device):
+    """Scratch of one speckle_filter() in flight (labels and counts): mccnn_speckle_scratch_bytes(H, W) bytes."""
+    nbytes = int(hip.load().mccnn_speckle_scratch_bytes(H, W))
+    if not nbytes:
+        raise ValueError("speckle_scratch: %d x %d is not a size the labelling takes (H*W <= 2^31 - 1)" % (H, W))
+    return torch.empty((nbytes // 4,), dtype=torch.int32, device=device)
+
+
+def speckle_filter(disp, min_size, max_diff=1.0, out=None, sizes=None, want_out=True, want_sizes=False, scratch=None):
+    """mccnn_speckle_filter: -> (out, sizes), each None unless wanted or given.  out: `disp` where the pixel's component -
+    4-neighbours both valid and no further apart than max_diff, closed transitively - has at least min_size pixels, +inf
+    elsewhere; sizes: int32 [H,W] holding the uint32 component sizes (0 for invalid pixels).  `scratch`: a
+    speckle_scratch()."""
+    who = "speckle_filter"
+    _check_map(disp, who)
+    H, W = disp.shape
+    if out is None and want_out:
+        out = torch.empty_like(disp)
+    if sizes is None and want_sizes:
+        sizes = torch.empty((H, W), dtype=torch.int32, device=disp.device)
+    if out is not None and (tuple(out.shape) != (H, W) or out.dtype != torch.float32):
+        raise ValueError("%s: `out` must be a float32 [%d,%d] tensor" % (who, H, W))
+    if sizes is not None and (tuple(sizes.shape) != (H, W) or sizes.dtype != torch.int32):
+        raise ValueError("%s: `sizes` must be an int32 [%d,%d] tensor (the bits are uint32)" % (who, H, W))
+    if int(min_size) != min_size or not 0 <= int(min_size) <= 0xFFFFFFFF:
+        raise ValueError("%s: min_size=%r is not a uint32" % (who, min_size))
+    scratch = scratch if scratch is not None else speckle_scratch(H, W, disp.device)
+    hip.check(hip.load().mccnn_speckle_filter(
+        hip.ptr(disp), H, W, _f32(max_diff), int(min_size), hip.ptr(out) if out is not None else None,
+        hip.ptr(sizes) if sizes is not None else None, hip.ptr(scratch), scratch.numel() * scratch.element_size(),
+        hip.stream()), "mccnn_speckle_filter")
+    return out, sizes
+
+
+def semi_dense(disp, rule, status=None, planes=None, plane_names=(), out=None, selected=None, sizes=None, scratch=None):
+    """The semi-dense map of `disp` under `rule` (a SemiDenseRule or its text): speckle_filter(semi_dense_select(disp)).
+    `selected`: where the selection goes when a speckle part follows (a [H,W] float32 tensor; allocated if None); `sizes`:
+    an int32 [H,W] tensor that receives the component sizes of the selection, if given."""
+    rule = SemiDenseRule.parse(rule)
+    if rule.speckle is None:
+        return semi_dense_select(disp, status, planes, plane_names, rule.thresholds, rule.require_match, out=out)
+    # (a rule that is a speckle part alone still selects: the one launch that turns invalid pixels into +inf)
+    selected = semi_dense_select(disp, status, planes, plane_names, rule.thresholds, rule.require_match, out=selected)
+    return speckle_filter(selected, rule.speckle[0], rule.speckle[1], out=out, sizes=sizes, scratch=scratch)[0]
+
+
 def bilateral_table(filter_height, filter_width, mean, std_dev):
     """The reference's spatial kernel (pf:428-436, util.normal util.py:45-48): float64 evaluation, float32 storage."""
     constant1 = 1. / (np.sqrt(2 * np.pi) * std_dev)
@@ -1447,8 +1536,10 @@ VIEWS = ("left", "both")       # StereoMatcher(views=...): the left map alone, o
 # What StereoMatcher._post_view runs on for one view.  name / suffix: the wrappers' view= and what the view's keep= keys and
 # timer entries carry (VIEW_SUFFIX); image, own / other (the view's and the other view's WTA map), volume (the view's
 # result volume): the inputs; status (None: a fresh tensor), maps (three planes: interp, subpixel, median), dst (the final
-# map) and planes (the confidence planes; None without measures): where the results go; stream: where it runs.
-PostView = collections.namedtuple("PostView", "name suffix image own other volume status maps dst planes stream")
+# map) and planes (the confidence planes; None without measures): where the results go; stream: where it runs; semi (None
+# without a semi-dense rule): the sparse map, the selection, the size plane and the labelling scratch of the view.
+PostView = collections.namedtuple("PostView", "name suffix image own other volume status maps dst planes stream semi",
+                                  defaults=(None,))
 
 
 def check_envelope(H, W, D):
@@ -1464,7 +1555,7 @@ def check_envelope(H, W, D):
 
 
 def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flight=1, arch="fast",
-                    fc_units=DECISION_UNITS, confidence=0, views="left"):
+                    fc_units=DECISION_UNITS, confidence=0, views="left", semi_dense=False):
     """Device bytes StereoMatcher.workspace(H, W, D) allocates, times `pairs_in_flight` (match.py --pairs_in_flight:
     one matcher per pair in flight): four volumes of H*W*Dp*4 bytes (Dp = hwd_pitch(D)), the SGM scratch and the flag
     planes of the four directions, both support planes, the status and map planes, and - on pixel-major volumes with
@@ -1474,7 +1565,9 @@ def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flig
     confidence: the number K of confidence planes the matcher was asked for (StereoMatcher(confidence=...)): plus one
     [K,H,W] float32 buffer; 0 (default): none.
     views="both" (StereoMatcher(views="both")): plus the right view's status plane, its three intermediate maps, the
-    [2,H,W] result and a second set of confidence planes."""
+    [2,H,W] result and a second set of confidence planes.
+    semi_dense (StereoMatcher(semi_dense=...)): plus, per view, two [H,W] float32 maps (the selection and the sparse map),
+    the labelling scratch (mccnn_speckle_scratch_bytes) and a [H,W] size plane; False (default): none."""
     check_envelope(H, W, D)
     if views not in VIEWS:
         raise ValueError("views must be 'left' or 'both'")
@@ -1494,6 +1587,8 @@ def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flig
     n += int(confidence) * H * W * 4
     if views == "both":
         n += (1 + 3 + 2 + int(confidence)) * H * W * 4
+    if semi_dense:
+        n += (2 if views == "both" else 1) * (3 * H * W * 4 + int(lib.mccnn_speckle_scratch_bytes(H, W)))
     return n * max(1, int(pairs_in_flight))
 
 
@@ -1527,7 +1622,7 @@ class StereoMatcher(object):
     def __init__(self, net, hp=None, cv_mode=hip.MCCNN_CV_EXACT, cbca_order=hip.MCCNN_CBCA_REFERENCE_ORDER,
                  feature_tile_rows=None, extras=None, features="auto", layout="auto", cbca_kernel="auto",
                  on_saturation="fallback", skip_unit_regions=True, two_chains=True, free_chains=True, refresh_first=True,
-                 sgm_flags_once=True, decision="auto", confidence=(), views="left"):
+                 sgm_flags_once=True, decision="auto", confidence=(), views="left", semi_dense=None):
         self.device = hip.require_device()
         self.net = net
         self.hp = dict(DEFAULT_HP)
@@ -1614,6 +1709,16 @@ class StereoMatcher(object):
             raise ValueError("views must be 'left' or 'both'")
         self.views = views
         self.both = views == "both"
+        # a SemiDenseRule or its text: every match entry returns the sparse map ([H,W], or [2,H,W] with both views) as
+        # the last element of its result, behind the map and the planes: per view one more launch behind the confidence
+        # launch (the selection; a rule without a speckle part) or five (the selection and the labelling's four).  The measures the rule reads must be among `confidence`: none is added silently (that would
+        # change K).  None (default): nothing changes - no launch, no buffer, the results as they were.
+        self.semi_dense = SemiDenseRule.parse(semi_dense) if semi_dense is not None else None
+        if self.semi_dense is not None:
+            missing = [n for n in self.semi_dense.measures if n not in self.confidence]
+            if missing:
+                raise ValueError("semi_dense=%r reads the confidence measure %s, which confidence=%r does not produce"
+                                 % (self.semi_dense.describe(), ", ".join(missing), self.confidence))
         self._ws = {}
         self._graphs = {}
         self._side = None
@@ -1652,7 +1757,8 @@ class StereoMatcher(object):
             need = workspace_bytes(H, W, D, self.pixel_major(), self.workspace_cbca_kernel(H, W, D),
                                    arch="accurate" if self.accurate else "fast",
                                    fc_units=self.net.num_fc_units if self.accurate else DECISION_UNITS,
-                                   confidence=len(self.confidence), views=self.views)
+                                   confidence=len(self.confidence), views=self.views,
+                                   semi_dense=self.semi_dense is not None)
             self._ws, self._graphs = {}, {}          # one shape resident at a time: the previous one goes first
             _require_device_memory(need, "StereoMatcher: the workspace of a %dx%d pair with ndisp=%d" % (W, H, D))
             dp = hwd_pitch(D)
@@ -1676,6 +1782,12 @@ class StereoMatcher(object):
                 ws["status_right"] = torch.empty((H, W), dtype=torch.int32, device=dev)
                 ws["maps_right"] = torch.empty((3, H, W), dtype=torch.float32, device=dev)   # interp, subpixel, median
                 ws["both"] = torch.empty((2, H, W), dtype=torch.float32, device=dev)         # the result: left, right
+            if self.semi_dense is not None:
+                lead = (2,) if self.both else ()
+                ws["sparse"] = torch.empty(lead + (H, W), dtype=torch.float32, device=dev)      # the result
+                ws["semi_selected"] = torch.empty(lead + (H, W), dtype=torch.float32, device=dev)
+                ws["semi_sizes"] = torch.empty(lead + (H, W), dtype=torch.int32, device=dev)
+                ws["semi_scratch"] = [speckle_scratch(H, W, dev) for _ in range(2 if self.both else 1)]
             ws["progs"] = None
             # (distances above CBCA_HWD_MAX_DISTANCE: the aggregation programs do not encode such arms - the joined
             # two-volume path of mccnn_cbca_iter_hwd_long_pair runs, as for shapes the programs do not encode)
@@ -1705,7 +1817,7 @@ class StereoMatcher(object):
         return aggregation_route(self.hp["cbca_distance"], 1, 1, self.cbca_order, self.extras, self.layout,
                                  "hwd") != "plane_major"
 
-    def _saturated_pair(self, left_image, right_image, ndisp, out, keep=None, confidence_out=None):
+    def _saturated_pair(self, left_image, right_image, ndisp, out, keep=None, confidence_out=None, semi_out=None):
         """on_saturation for the pair that has just been launched: None when its features were fine (or nobody is to
         look), else the map of the same pair behind the float32 library convolutions (written to `out` if given) - with
         its confidence planes (written to `confidence_out` if given) where the matcher produces them.
@@ -1723,22 +1835,26 @@ class StereoMatcher(object):
             self._library_twin = StereoMatcher(self.net, hp=self.hp, cv_mode=self.cv_mode, cbca_order=self.cbca_order,
                                                extras=self.extras, features="miopen", layout=self.layout,
                                                cbca_kernel=self.cbca_kernel, on_saturation="ignore", decision="library",
-                                               confidence=self.confidence, views=self.views)
+                                               confidence=self.confidence, views=self.views,
+                                               semi_dense=self.semi_dense)
         if keep is not None:
             keep.clear()
-        return self._library_twin.match(left_image, right_image, ndisp, out=out, keep=keep, confidence_out=confidence_out)
+        return self._library_twin.match(left_image, right_image, ndisp, out=out, keep=keep, confidence_out=confidence_out,
+                                        semi_out=semi_out)
 
     def match(self, left_image, right_image, ndisp, timer=_NO_TIMER, keep=None, _static_out=False, out=None,
-              confidence_out=None):
+              confidence_out=None, semi_out=None):
         """_match() + the on_saturation policy (class docstring): a pair whose hand-written features were clamped is
         matched again with the library convolutions unless the caller asked to be left alone.  With `keep` the stages
         handed out are those of the map that is returned: the repeated pair's where the pair was repeated.
         A matcher with confidence measures returns (map, planes [K,H,W]); the planes follow the map's rules - a copy,
-        or `confidence_out` (a contiguous float32 [K,H,W] device tensor) where one is given, next to `out`."""
+        or `confidence_out` (a contiguous float32 [K,H,W] device tensor) where one is given, next to `out`.
+        A matcher with a semi-dense rule returns the sparse map as the last element - (map, sparse) or (map, planes,
+        sparse) - by the same rules, with `semi_out` (shaped like `out`) in the place of `confidence_out`."""
         res = self._match(left_image, right_image, ndisp, timer=timer, keep=keep, _static_out=_static_out, out=out,
-                          confidence_out=confidence_out)
+                          confidence_out=confidence_out, semi_out=semi_out)
         if not _static_out:
-            redo = self._saturated_pair(left_image, right_image, ndisp, out, keep, confidence_out)
+            redo = self._saturated_pair(left_image, right_image, ndisp, out, keep, confidence_out, semi_out)
             if redo is not None:
                 return redo
         return res
@@ -1988,6 +2104,15 @@ class StereoMatcher(object):
             stages["confidence"] = confidence_any(v.volume, D, pixel_major, v.other, self.confidence, out=v.planes,
                                                   view=v.name)
             timer.stop()
+        if self.semi_dense is not None:
+            # the rule on the view's final map: its own status plane and its own confidence planes
+            rule, (sparse, selected, sizes, scratch) = self.semi_dense, v.semi
+            timer.start("semi_dense" + v.suffix)
+            stages["semi_dense"] = semi_dense(db, rule, st, stages.get("confidence"), self.confidence, out=sparse,
+                                              selected=selected, sizes=sizes, scratch=scratch)
+            timer.stop()
+            if rule.speckle is not None:
+                stages["semi_dense_selected"], stages["component_sizes"] = selected, sizes
         if keep is not None:
             keep.update((name + v.suffix, t) for name, t in stages.items())
 
@@ -2005,13 +2130,13 @@ class StereoMatcher(object):
         return t if (handed or given is not None) else t.clone()
 
     def _match(self, left_image, right_image, ndisp, timer=_NO_TIMER, keep=None, _static_out=False, out=None,
-               confidence_out=None):
+               confidence_out=None, semi_out=None):
         """left/right: standardised float32 device tensors [H,W] (or [H,W,1]).  Returns the final left disparity
         map [H,W] on the device.  The matcher's workspace is reused by the next call, so the map is handed out as a
         copy - one [H,W] allocation + one copy per pair; pass `out` (a contiguous float32 [H,W] device tensor) and the
         last kernel writes there instead: nothing is allocated but the conv activations.  `keep`, if a dict, receives
         intermediate device tensors in the reference's [D,H,W] layout (tests).  A matcher with confidence measures
-        returns (map, planes) - see match()."""
+        returns (map, planes), one with a semi-dense rule the sparse map behind them - see match()."""
         L = left_image.reshape(left_image.shape[0], left_image.shape[1]).contiguous()
         R = right_image.reshape(right_image.shape[0], right_image.shape[1]).contiguous()
         H, W = L.shape
@@ -2080,6 +2205,17 @@ class StereoMatcher(object):
             return given if given is not None else (torch.empty_like(spare) if fresh else spare)
         res = dest(out, ws["both"] if both else ws["maps"][5])
         planes = dest(confidence_out, ws["confidence"]) if k else None
+        semi = self.semi_dense is not None
+        if semi:
+            self._check_given(semi_out, lead + (H, W), "semi_out", "H,W", L)
+            sparse = dest(semi_out, ws["sparse"])
+            selected, sizes = dest(None, ws["semi_selected"]), dest(None, ws["semi_sizes"])
+            scratch = [torch.empty_like(t) for t in ws["semi_scratch"]] if fresh else ws["semi_scratch"]
+
+        def semi_of(i):                 # view i's (sparse, selected, sizes, scratch)
+            if not semi:
+                return None
+            return (sparse[i], selected[i], sizes[i], scratch[i]) if both else (sparse, selected, sizes, scratch[0])
         main_s = torch.cuda.current_stream()
         fork = both and timer is _NO_TIMER
         if both:
@@ -2091,13 +2227,13 @@ class StereoMatcher(object):
                 right_s.wait_stream(main_s)
             view = PostView("right", "_right", R, dr, dl, right_volume, None if fresh else ws["status_right"],
                             torch.empty_like(ws["maps_right"]) if fresh else ws["maps_right"], res[1],
-                            planes[1] if k else None, right_s)
+                            planes[1] if k else None, right_s, semi_of(1))
             with torch.cuda.stream(view.stream):
                 self._post_view(view, D, pm, timer, keep)
             if fresh:
                 keep["cbca2_right"] = hwd_to_dhw(right_volume, D) if pm else right_volume.clone()
         view = PostView("left", "", L, dl, dr, left_volume, None if fresh else ws["status"], m[2:5],
-                        res[0] if both else res, planes[0] if k and both else planes, main_s)
+                        res[0] if both else res, planes[0] if k and both else planes, main_s, semi_of(0))
         self._post_view(view, D, pm, timer, keep)
         if fork:
             main_s.wait_stream(right_s)
@@ -2105,7 +2241,10 @@ class StereoMatcher(object):
             keep["wta"] = (dl, dr)
         handed = _static_out or fresh
         res = self._hand_out(res, out, handed)
-        return (res, self._hand_out(planes, confidence_out, handed)) if k else res
+        if not (k or semi):
+            return res
+        return ((res,) + ((self._hand_out(planes, confidence_out, handed),) if k else ())
+                + ((self._hand_out(sparse, semi_out, handed),) if semi else ()))
 
     def _ingest_buffers(self, H, W):
         """Static float32 inputs + ingest scratch of the eager byte path: kept per shape, so that a pair allocates
@@ -2118,7 +2257,7 @@ class StereoMatcher(object):
             self._ingest = b
         return b[1:]
 
-    def match_u8(self, left_u8, right_u8, ndisp, out=None, confidence_out=None):
+    def match_u8(self, left_u8, right_u8, ndisp, out=None, confidence_out=None, semi_out=None):
         """match() straight from the decoded bytes of the two PNGs: uint8 device tensors [H,W] or [H,W,C] (C = 1, 3, 4;
         see ingest_u8), or pinned host tensors, which are copied in stream order without blocking.  The standardisation runs on the device, bit-identical to match.py's on the host, so the map is
         what match() returns on the host-standardised images."""
@@ -2127,7 +2266,7 @@ class StereoMatcher(object):
         left_u8 = left_u8.to(self.device, non_blocking=True).contiguous()
         right_u8 = right_u8.to(self.device, non_blocking=True).contiguous()
         ingest_u8_pair(left_u8, right_u8, sl, sr, scratch)
-        return self.match(sl, sr, ndisp, out=out, confidence_out=confidence_out)
+        return self.match(sl, sr, ndisp, out=out, confidence_out=confidence_out, semi_out=semi_out)
 
     def _graph_key(self, key):
         """The key of a pair's captured graph.  An accurate network's graph holds the ADDRESS of the packed decision
@@ -2177,11 +2316,14 @@ class StereoMatcher(object):
 
     def _saturated_graph_pair(self, sl, sr, ndisp, out):
         """on_saturation behind a replay (one host synchronisation unless "ignore"): a repeated pair writes the static
-        map - and the static confidence planes, where the matcher produces them."""
+        map - and the static confidence planes and sparse map, where the matcher produces them."""
+        outs = out if isinstance(out, tuple) else (out,)
+        given = {}
         if self.confidence:
-            self._saturated_pair(sl, sr, ndisp, out[0], confidence_out=out[1])
-        else:
-            self._saturated_pair(sl, sr, ndisp, out)
+            given["confidence_out"] = outs[1]
+        if self.semi_dense is not None:
+            given["semi_out"] = outs[-1]
+        self._saturated_pair(sl, sr, ndisp, outs[0], **given)
 
     def _static_u8(self, left_u8, right_u8, H, W):
         """The static buffers of match_graph_u8: (float32 left, right, the byte images, the ingest scratch)."""
@@ -2198,7 +2340,8 @@ class StereoMatcher(object):
         """match_graph() from bytes: static uint8 inputs, and the ingest launches INSIDE the captured graph, writing the
         static float32 images the rest of the graph reads - per pair two byte copies (from the device or from pinned host
         memory, in stream order, non-blocking) and one replay.  One graph per (H, W, ndisp, C), captured by the rules of
-        _capture.  Returns the static output map (overwritten by the next call)."""
+        _capture.  Returns the static output map (overwritten by the next call) - what match_graph() returns: with
+        confidence measures and / or a semi-dense rule the tuple (map[, planes][, sparse]), every element static."""
         H, W, C = _u8_image(left_u8)
         if _u8_image(right_u8) != (H, W, C):
             raise ValueError("match_graph_u8: the two images must have the same shape")
@@ -2223,7 +2366,8 @@ class StereoMatcher(object):
     def match_graph(self, left_image, right_image, ndisp):
         """match() replayed as ONE hipGraph launch: the ~75 kernel launches of a pair are captured once per image
         shape (_capture) and replayed on static input/output buffers.  Returns the static output map [H,W] (overwritten
-        by the next call; with confidence measures (map, planes), both static).  The images are copied into the static inputs in stream order; nothing synchronises."""
+        by the next call; with confidence measures (map, planes), with a semi-dense rule the sparse map as the last element
+        besides - (map, sparse) or (map, planes, sparse) - all static).  The images are copied into the static inputs in stream order; nothing synchronises."""
         L = left_image.reshape(left_image.shape[0], left_image.shape[1])
         R = right_image.reshape(right_image.shape[0], right_image.shape[1])
         key = self._graph_key((L.shape[0], L.shape[1], int(ndisp)))
