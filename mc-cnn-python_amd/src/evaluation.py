@@ -659,14 +659,16 @@ class ListScorer(object):
     enqueued, what the running totals take and what the report is told.
 
         scored = scorer.begin(index, name, truth, truth_right)    None: no ground truth, the pair is listed as skipped
-        scorer.score(scored, maps, planes, slot)                  behind the maps on the pair's stream; again with the
-                                                                  maps of a repeated pair (the saturation redo)
-        scorer.commit(scored, maps)                               once, in list order, with the maps that are kept
+        scorer.score(scored, result, slot)                        behind the results on the pair's stream; again with the
+                                                                  result of a repeated pair (the saturation redo)
+        scorer.commit(scored, result)                             once, in list order, with the result that is kept
         scorer.publish(scored, json_path)                         by whoever writes the pair's files
 
-    score() and commit() enqueue on the current stream and never block the host; publish() waits for the scores' own
-    events.  views="both": maps are [2,H,W] and planes [2,K,H,W], and the report's right evaluator scores the right map
-    of a pair with right-view ground truth.  sparsifier (--confidence): scores a map's planes behind its evaluation."""
+    result: the pair's PairResult (pair_result.py) on the device - the map that is scored, the planes or None, the sparse
+    map (--semi_dense) or None.  score() and commit() enqueue on the current stream and never block the host; publish()
+    waits for the scores' own events.  views="both": maps are [2,H,W] and planes [2,K,H,W], and the report's right
+    evaluator scores the right map of a pair with right-view ground truth.  sparsifier (--confidence): scores a map's
+    planes behind its evaluation."""
 
     def __init__(self, report, sparsifier=None, views="left"):
         self.report, self.sparsifier, self.both = report, sparsifier, views == "both"
@@ -685,32 +687,28 @@ class ListScorer(object):
             return None
         return Scored(index, name, [truth] if truth_right is None else [truth, truth_right])
 
-    def _views(self, scored, maps, planes=None):
-        """(evaluator, map, planes, gt, mask) of every view of the pair that is scored, the left one first."""
+    def _views(self, scored, result):
+        """(view number, that view of the result, gt, mask) of every view of the pair that is scored, the left one first."""
         for v, (gt, mask) in enumerate(scored.truths):
-            yield (self.evaluators[v], maps[v] if self.both else maps,
-                   planes[v] if (self.both and planes is not None) else planes, gt, mask)
+            yield v, result.view(v, self.both), gt, mask
 
-    def _sparse_views(self, scored, sparse):
-        """(evaluator, sparse map, gt, mask) of every scored view (--semi_dense), the left one first."""
-        for v, (gt, mask) in enumerate(scored.truths):
-            yield self.report.semi_evaluators[v], sparse[v] if self.both else sparse, gt, mask
+    def score(self, scored, result, slot):
+        """Per view the evaluation, then (--confidence) the sparsification; replaces what the record holds.  The views'
+        sparse maps (--semi_dense) are scored behind them by evaluators of their own."""
+        scored.scores = [(self.evaluators[v].score(r.map, gt, mask, slot),
+                          self.sparsifier.score(r.map, r.planes, gt) if self.sparsifier is not None else None)
+                         for v, r, gt, mask in self._views(scored, result)]
+        if result.sparse is not None:
+            scored.semi = [self.report.semi_evaluators[v].score(r.sparse, gt, mask, slot)
+                           for v, r, gt, mask in self._views(scored, result)]
 
-    def score(self, scored, maps, planes, slot, sparse=None):
-        """Per view the evaluation, then (--confidence) the sparsification; replaces what the record holds.  sparse
-        (--semi_dense): the views' sparse maps, scored behind them by evaluators of their own."""
-        scored.scores = [(e.score(m, gt, mask, slot), self.sparsifier.score(m, p, gt) if self.sparsifier is not None else None)
-                         for e, m, p, gt, mask in self._views(scored, maps, planes)]
-        if sparse is not None:
-            scored.semi = [e.score(m, gt, mask, slot) for e, m, gt, mask in self._sparse_views(scored, sparse)]
-
-    def commit(self, scored, maps, sparse=None):
-        """The maps that are kept into the running totals (Evaluator.commit keeps the commits in call order)."""
-        for e, m, _, gt, mask in self._views(scored, maps):
-            e.commit(m, gt, mask)
-        if sparse is not None:
-            for e, m, gt, mask in self._sparse_views(scored, sparse):
-                e.commit(m, gt, mask)
+    def commit(self, scored, result):
+        """The result that is kept into the running totals (Evaluator.commit keeps the commits in call order)."""
+        for v, r, gt, mask in self._views(scored, result):
+            self.evaluators[v].commit(r.map, gt, mask)
+        if result.sparse is not None:
+            for v, r, gt, mask in self._views(scored, result):
+                self.report.semi_evaluators[v].commit(r.sparse, gt, mask)
 
     def publish(self, scored, json_path):
         """The pair's entry of the report and its evalMCCNN.json, from the scores the record holds now."""

@@ -21,6 +21,7 @@ The backend's interface:
     retire(slot, job, ticket)         the slot is about to be reused; returns None, or the ticket of a repeated pair
                                       (the saturation redo of match.py) whose result replaces the first one's files
 """
+import collections
 import os
 import queue
 import threading
@@ -250,49 +251,23 @@ def make_reader(paths, check_shape, to_host_buffer=pinned_u8, truth=None, shape=
     return read
 
 
-def _save_middlebury(disparity, p):
-    util.saveDisparity(disparity, p["out_img"])
-    util.writePfm(disparity, p["out"])
+def _save_middlebury(result, p):
+    util.saveDisparity(result.map, p["out_img"])
+    util.writePfm(result.map, p["out"])
 
 
-def map_and_planes(result):
-    """What a matcher returns, as (map, planes or None): one with confidence measures returns the pair (match.py
-    --confidence).  With --views both the map is [2,H,W] and the planes [2,K,H,W]."""
-    return result if isinstance(result, tuple) else (result, None)
-
-
-def split_result(result):
-    """What a matcher returns, as (map, planes or None, sparse or None): the planes (--confidence) have one dimension
-    more than the map, the sparse map (--semi_dense) has the map's."""
-    if not isinstance(result, tuple):
-        return result, None, None
-    planes = sparse = None
-    for t in result[1:]:
-        if t.ndim == result[0].ndim:
-            sparse = t
-        else:
-            planes = t
-    return result[0], planes, sparse
-
-
-def make_writer(rank=0, log=print, scorer=None, eval_file="evalMCCNN.json", save=_save_middlebury, save_confidence=None,
-                save_sparse=None):
-    """write(job, result, seconds) for ListPipeline: the three files of match.py, with the existing util functions; with a
+def make_writer(rank=0, log=print, scorer=None, eval_file="evalMCCNN.json", save=_save_middlebury):
+    """write(job, result, seconds) for ListPipeline: the files of match.py, with the existing util functions; with a
     `scorer` (evaluation.ListScorer, match.py --evaluate) also the evaluation of a pair that was scored (job.scored: of
-    the map these files hold, or of the repeat that replaces it), once its bytes are on the host.  `save(map, paths)`
-    writes the map and its preview (datasets.py: a KITTI layout's is the 16-bit plane); a result (map, planes) also has
-    its planes written by `save_confidence(planes, paths)` - a repeated pair's files get the repeated pair's planes -
-    and one with a sparse map (--semi_dense) has that written by `save_sparse(sparse, paths)`."""
+    the map these files hold, or of the repeat that replaces it), once its bytes are on the host.  `save(result, paths)`
+    writes what the PairResult of host arrays holds: the map and its preview (datasets.py: a KITTI layout's is the 16-bit
+    plane), the planes (--confidence) and the sparse map (--semi_dense) - a repeated pair's files get the repeated
+    pair's."""
     from datetime import datetime
 
     def write(job, result, seconds):
         p = job.paths
-        disparity, planes, sparse = split_result(result)
-        save(disparity, p)
-        if planes is not None:
-            save_confidence(planes, p)
-        if sparse is not None:
-            save_sparse(sparse, p)
+        save(result, p)
         util.saveTimeFile(seconds, p["out_time"])
         log("[{}] {}: {:.3f} s -> {}".format(rank, datetime.now(), seconds, p["out"]))
         if scorer is not None and job.scored is not None:
@@ -300,15 +275,33 @@ def make_writer(rank=0, log=print, scorer=None, eval_file="evalMCCNN.json", save
     return write
 
 
-class Ticket(object):
-    def __init__(self, host, done, device_map=None, host_planes=None, device_planes=None, host_sparse=None,
-                 device_sparse=None):
-        # device_map: what an evaluation scores (a KITTI layout: what the written PNG holds, not the matcher's map)
-        self.host, self.done, self.device_map = host, done, device_map
-        # with --confidence: the planes in a second pinned buffer, copied behind the map, and where they are on the device
-        self.host_planes, self.device_planes = host_planes, device_planes
-        # with --semi_dense: the sparse map in a pinned buffer of its own, and where it is on the device
-        self.host_sparse, self.device_sparse = host_sparse, device_sparse
+def slot_comes_round(redo, rematch, scorer, scored, result, slot, slot_stream, synchronize):
+    """What every list loop does with a pair (its results complete) when its slot is about to be reused.  The saturation
+    redo (stereo_device.SaturationRedo) is asked; a pair that is due is matched again by rematch() -> (anything, the
+    repeat's PairResult on the device), and the device is synchronised.  A pair that is scored (`scored` not None) is then
+    committed under slot_stream(): the slot's result buffer and scratch belong to that stream, and the commit runs in
+    front of the slot's next pair, which overwrites a replayed graph's static output; the total takes the result that
+    is kept, once, in list order, and a repeated pair is scored again first.  `result`: the PairResult of the first
+    match, its map what is scored.  Returns what rematch() returned, or None."""
+    again = None
+    if redo.due():
+        again = rematch()
+        result = again[1]
+        synchronize()
+    if scored is not None:
+        with slot_stream():
+            if again is not None:
+                scorer.score(scored, result, slot)       # not the discarded map
+            scorer.commit(scored, result)
+        if again is not None:
+            synchronize()                                # the library matcher's output is overwritten by the next repeat
+    return again
+
+
+# A pair enqueued by MatcherBackend.  host: the PairResult of pinned host tensors its results are copied to; done: the
+# event behind the copies; device: the PairResult on the device, its map what an evaluation scores (a KITTI layout: what
+# the written PNG holds, not the matcher's map).
+Ticket = collections.namedtuple("Ticket", "host done device")
 
 
 class MatcherBackend(object):
@@ -341,24 +334,19 @@ class MatcherBackend(object):
         return self.torch.cuda.stream(s) if s is not None else contextlib.nullcontext()
 
     def _to_host(self, result):
+        """The PairResult a matcher returned on its way to pinned host memory: map, planes, sparse map, then the event."""
         torch = self.torch
-        disparity, planes, sparse = split_result(result)
-        crossing, scored = disparity, disparity
+        crossing = scored = result.map
         if self.device_output is not None:
-            crossing, scored = self.device_output(disparity, self.scorer is not None)
-        host = torch.empty(tuple(crossing.shape), dtype=crossing.dtype, pin_memory=True)
-        host.copy_(crossing, non_blocking=True)
-        host_planes = None
-        if planes is not None:
-            host_planes = torch.empty(tuple(planes.shape), dtype=planes.dtype, pin_memory=True)
-            host_planes.copy_(planes, non_blocking=True)
-        host_sparse = None
-        if sparse is not None:
-            host_sparse = torch.empty(tuple(sparse.shape), dtype=sparse.dtype, pin_memory=True)
-            host_sparse.copy_(sparse, non_blocking=True)
+            crossing, scored = self.device_output(result.map, self.scorer is not None)
+
+        def pinned_copy(t):
+            host = torch.empty(tuple(t.shape), dtype=t.dtype, pin_memory=True)
+            return host.copy_(t, non_blocking=True)
+        host = result._replace(map=crossing).apply(pinned_copy)
         done = torch.cuda.Event()
         done.record()
-        return Ticket(host, done, scored, host_planes, planes, host_sparse, sparse)
+        return Ticket(host, done, result._replace(map=scored))
 
     def _truth(self, gt, mask, dev):
         """The reader's pinned ground truth on its way to the device, behind the pair on the slot's stream."""
@@ -372,38 +360,27 @@ class MatcherBackend(object):
         m = self.matchers[slot]
         with self._stream(slot):
             match = m.match_u8 if mode == "eager" else m.match_graph_u8
-            ticket = self._to_host(match(job.left, job.right, job.ndisp))
+            ticket = self._to_host(m.result_of(match(job.left, job.right, job.ndisp)))
             if self.scorer is not None:
                 # (the right view's truth crosses only where the pair is scored at all, and in front of the left's)
                 truth_right = self._truth(job.gt_right, job.mask_right, m.device) if job.gt is not None else None
                 job.scored = self.scorer.begin(job.index, job.name, self._truth(job.gt, job.mask, m.device), truth_right)
                 if job.scored is not None:
-                    self.scorer.score(job.scored, ticket.device_map, ticket.device_planes, slot, ticket.device_sparse)
+                    self.scorer.score(job.scored, ticket.device, slot)
             return ticket
 
     def wait(self, ticket):
         ticket.done.synchronize()
-        extra = tuple(t.numpy() for t in (ticket.host_planes, ticket.host_sparse) if t is not None)
-        return (ticket.host.numpy(),) + extra if extra else ticket.host.numpy()
+        return ticket.host.apply(lambda t: t.numpy())
 
     def retire(self, slot, job, ticket):
         ticket.done.synchronize()
-        scored = job.scored if self.scorer is not None else None
-        again = None
-        if self.redo.due():              # before the slot is reused (stereo_device.SaturationRedo)
+
+        def rematch():
             library = self.redo.matcher()
             self.log("[{}] ".format(self.rank) + self.redo.notice(job.paths["out"]))
-            ticket = again = self._to_host(library.match_u8(job.left, job.right, job.ndisp))
-            self.torch.cuda.synchronize()
-        if scored is not None:
-            # on the slot's stream: its result buffer and scratch belong to it, and the commit runs in front of the
-            # slot's next pair, which overwrites a replayed graph's static output
-            with self._stream(slot):
-                if again is not None:
-                    self.scorer.score(scored, again.device_map, again.device_planes, slot, again.device_sparse)   # not the discarded map
-                self.scorer.commit(scored, ticket.device_map, ticket.device_sparse)
-            if again is not None:
-                self.torch.cuda.synchronize()    # the library matcher's output is overwritten by the next repeat
-        return again
-
-
+            again = self._to_host(library.result_of(library.match_u8(job.left, job.right, job.ndisp)))
+            return again, again.device
+        again = slot_comes_round(self.redo, rematch, self.scorer, job.scored if self.scorer is not None else None,
+                                 ticket.device, slot, lambda: self._stream(slot), self.torch.cuda.synchronize)
+        return again[0] if again is not None else None

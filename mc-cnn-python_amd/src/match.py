@@ -38,7 +38,6 @@ import datasets
 import evaluation          # (neither module touches torch or the GPU on import: util.pin_gpu comes first, in main)
 import list_matcher
 import util
-from list_matcher import split_result
 from semi_dense_rule import SemiDenseRule
 
 # Flag names, types and defaults are the reference's command line (match.py:15-43) - that is the drop-in contract;
@@ -224,11 +223,10 @@ def hyper_parameters(args):
                 sgm_V=args.sgm_V, blur_sigma=args.blur_sigma, blur_threshold=args.blur_threshold)
 
 
-# a pair launched and not yet written: the matcher's map and planes, what crosses to the host and what is scored
-# (layout.device_output), the event behind all of it, the start of its time, its paths, the matcher's inputs (a repeat
-# needs them), its slot and its scoring record (evaluation.Scored, or None)
-# (sparse: the semi-dense map of --semi_dense, or None)
-Pending = collections.namedtuple("Pending", "maps planes crossing kept done started paths images slot scored sparse")
+# a pair launched and not yet written: what crosses to the host for its map, its PairResult on the device with the map
+# that is scored (layout.device_output states both), the event behind all of it, the start of its time, its paths, the
+# matcher's inputs (a repeat needs them), its slot and its scoring record (evaluation.Scored, or None)
+Pending = collections.namedtuple("Pending", "crossing result done started paths images slot scored")
 
 
 class ListLoop(object):
@@ -236,14 +234,13 @@ class ListLoop(object):
     and, with --pairs_in_flight N > 1, one stream per slot) and writes its files when the slot comes round again.
 
     layout: datasets.py; redo: stereo_device.SaturationRedo; scorer: evaluation.ListScorer or None (--evaluate);
-    save_maps(host map, paths), save_confidence(host planes, paths), save_sparse(host sparse map, paths): the files of
-    what crossed to the host."""
+    save(PairResult of host arrays, paths): the files of what crossed to the host."""
 
-    def __init__(self, layout, matchers, streams, redo, scorer, save_maps, save_confidence, rank, save_sparse=None):
+    def __init__(self, layout, matchers, streams, redo, scorer, save, rank):
         import torch
         self.torch = torch
         self.layout, self.matchers, self.streams, self.redo, self.scorer = layout, matchers, streams, redo, scorer
-        self.save_maps, self.save_confidence, self.save_sparse, self.rank = save_maps, save_confidence, save_sparse, rank
+        self.save, self.rank = save, rank
         self.pending = []            # oldest first
 
     def _stream(self, slot):
@@ -256,58 +253,46 @@ class ListLoop(object):
         return (self.torch.from_numpy(truth[0]).cuda(),
                 self.torch.from_numpy(truth[1]).cuda() if truth[1] is not None else None)
 
+    def _matched(self, matcher, images, scoring):
+        """One pair on `matcher`: (what crosses to the host for its map, its PairResult with the map that is scored) - the
+        map, or a KITTI layout's 16-bit code and what it holds, behind the map on the current stream."""
+        result = matcher.result_of(matcher.match(*images))
+        crossing, kept = self.layout.device_output(result.map, scoring)
+        return crossing, result._replace(map=kept)
+
     def launch(self, slot, index, paths, left_image, right_image, ndisp, truth, truth_right):
         """The timed region (match.py:129-179): host arrays in, host array out, device-synchronised - from here to
         finish().  With several pairs in flight the pair runs on its slot's stream."""
         torch = self.torch
         started = time.time()
         with self._stream(slot):
-            dev_l = torch.from_numpy(left_image).cuda()
-            dev_r = torch.from_numpy(right_image).cuda()
-            maps, planes, sparse = split_result(self.matchers[slot].match(dev_l, dev_r, ndisp))
-            # what crosses to the host and what is scored: the map, or a KITTI layout's 16-bit code and what it holds,
-            # behind the map on this stream - and behind that the evaluation
-            crossing, kept = self.layout.device_output(maps, truth is not None)
-            scored = None
+            images = (torch.from_numpy(left_image).cuda(), torch.from_numpy(right_image).cuda(), ndisp)
+            crossing, result = self._matched(self.matchers[slot], images, truth is not None)
+            scored = None                    # the evaluation: behind the map and what is scored, on this stream
             if self.scorer is not None:
                 scored = self.scorer.begin(index, paths["left"], self._to_device(truth), self._to_device(truth_right))
             if scored is not None:
-                self.scorer.score(scored, kept, planes, slot, sparse)
+                self.scorer.score(scored, result, slot)
             done = torch.cuda.Event()
             done.record()
-        self.pending.append(Pending(maps, planes, crossing, kept, done, started, paths, (dev_l, dev_r, ndisp), slot, scored,
-                                    sparse))
+        self.pending.append(Pending(crossing, result, done, started, paths, images, slot, scored))
 
     def finish(self):
         """Collects and writes the oldest pair."""
-        torch = self.torch
         p = self.pending.pop(0)
         p.done.synchronize()
-        planes, crossing, kept, sparse = p.planes, p.crossing, p.kept, p.sparse
-        redone = self.redo.due()
-        if redone:
+
+        def rematch():
             library = self.redo.matcher()
             print("[{}] ".format(self.rank) + self.redo.notice(p.paths["out"]))
-            maps, planes, sparse = split_result(library.match(*p.images))
-            crossing, kept = self.layout.device_output(maps, p.scored is not None)
-            torch.cuda.synchronize()
-        if p.scored is not None:
-            # the total takes the map that is kept, once, in list order; a repeated pair is scored again
-            with self._stream(p.slot):
-                if redone:
-                    self.scorer.score(p.scored, kept, planes, p.slot, sparse)
-                self.scorer.commit(p.scored, kept, sparse)
-            if redone:
-                torch.cuda.synchronize()     # the library matcher's output is overwritten by the next repeat
-        host_map = crossing.cpu().numpy()            # the float32 map, or a KITTI layout's 16-bit plane
-        host_planes = planes.cpu().numpy() if planes is not None else None
-        host_sparse = sparse.cpu().numpy() if sparse is not None else None
+            return self._matched(library, p.images, p.scored is not None)
+        crossing, result = list_matcher.slot_comes_round(self.redo, rematch, self.scorer, p.scored, p.result, p.slot,
+                                                         lambda: self._stream(p.slot),
+                                                         self.torch.cuda.synchronize) or (p.crossing, p.result)
+        # (the float32 map, or a KITTI layout's 16-bit plane)
+        host = result._replace(map=crossing).apply(lambda t: t.cpu().numpy())
         seconds = time.time() - p.started
-        self.save_maps(host_map, p.paths)
-        if host_planes is not None:
-            self.save_confidence(host_planes, p.paths)
-        if host_sparse is not None:
-            self.save_sparse(host_sparse, p.paths)
+        self.save(host, p.paths)
         util.saveTimeFile(seconds, p.paths["out_time"])
         print("[{}] {}: {:.3f} s -> {}".format(self.rank, datetime.now(), seconds, p.paths["out"]))
         if p.scored is not None:
@@ -466,26 +451,21 @@ def main(argv=None):
                         sgm_independent_directions=args.paper_sgm),
             confidence=conf_names, views=args.views, semi_dense=semi_rule)
 
-    def save_sparse(sparse, out):
-        """The sparse map's PFM from the host map [H,W] (--views both: [2,H,W], the right view's as disp1MCCNN_s.pfm)."""
-        for view, view_map in enumerate(sparse if both else (sparse,)):
-            util.writePfm(view_map, layout.sparse_path(out, view))
-
-    def save_confidence(planes, out):
-        """One PFM per measure from the host planes [K,H,W] (layout.confidence_path names the file); --views both:
-        [2,K,H,W], the right view's as conf1MCCNN_<measure>.pfm."""
-        for view, view_planes in enumerate(planes if both else (planes,)):
-            for k, name in enumerate(conf_names):
-                path = layout.confidence_path(out, name, view) if both else layout.confidence_path(out, name)
+    def save(result, out):
+        """The files of a pair from the PairResult of host arrays that crossed: the map's (--views both: [2,H,W], the right
+        map as disp1MCCNN.*), then one PFM per measure from the planes [K,H,W] (layout.confidence_path names the file;
+        the right view's as conf1MCCNN_<measure>.pfm), then the sparse map's PFM (the right view's as disp1MCCNN_s.pfm)."""
+        views = [(v, result.view(v, both)) for v in range(2 if both else 1)]
+        for v, r in views:
+            (layout.save_right if v else layout.save)(r.map, out)
+        for v, r in views:
+            for k, name in enumerate(conf_names if r.planes is not None else ()):
+                path = layout.confidence_path(out, name, v) if both else layout.confidence_path(out, name)
                 util.recurMk(os.path.abspath(os.path.dirname(path)))
-                util.writePfm(view_planes[k], path)
-
-    def save_maps(result, out):
-        """The map's files from what crossed to the host; --views both: [2,H,W], the right map as disp1MCCNN.*."""
-        if not both:
-            return layout.save(result, out)
-        layout.save(result[0], out)
-        layout.save_right(result[1], out)
+                util.writePfm(r.planes[k], path)
+        for v, r in views:
+            if r.sparse is not None:
+                util.writePfm(r.sparse, layout.sparse_path(out, v))
 
     def paths(index):
         # Middlebury: outputs mirror the input tree under the two roots (match.py:99-110): <root>/<dir of im0.png relative
@@ -532,17 +512,14 @@ def main(argv=None):
             paths, footprint, truth=layout.load_truth if args.evaluate else None,
             shape=(lambda left, image: layout.shape(left, ndisp_flag, image)) if layout.kitti else None,
             truth_right=layout.load_truth_right if (args.evaluate and both) else None)
-        writer = list_matcher.make_writer(rank, scorer=scorer, eval_file=out_eval_file, save=save_maps,
-                                          save_confidence=save_confidence if conf_names else None,
-                                          save_sparse=save_sparse if semi_rule is not None else None)
+        writer = list_matcher.make_writer(rank, scorer=scorer, eval_file=out_eval_file, save=save)
         pipeline = list_matcher.ListPipeline(reader, backend, writer, slots=in_flight, readers=args.readers)
         try:
             pipeline.run(indices)
         finally:
             print("[{}] {}".format(rank, pipeline.summary()))
     else:
-        loop = ListLoop(layout, matchers, streams, sd.SaturationRedo(matchers, make_library_matcher), scorer, save_maps,
-                        save_confidence, rank, save_sparse)
+        loop = ListLoop(layout, matchers, streams, sd.SaturationRedo(matchers, make_library_matcher), scorer, save, rank)
         loop.run(indices, paths, lambda left_path: layout.shape(left_path, ndisp_flag), footprint)
     if scorer is not None:
         scorer.report.write(eval_path)

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 import _hipabi as hip
+from pair_result import PairResult
 from semi_dense_rule import SemiDenseRule  # noqa: F401  (host-only: match.py parses it before the GPU is pinned)
 
 
@@ -1817,10 +1818,14 @@ class StereoMatcher(object):
         return aggregation_route(self.hp["cbca_distance"], 1, 1, self.cbca_order, self.extras, self.layout,
                                  "hwd") != "plane_major"
 
-    def _saturated_pair(self, left_image, right_image, ndisp, out, keep=None, confidence_out=None, semi_out=None):
+    def result_of(self, value):
+        """What a match entry of this matcher returned, as a PairResult: decoded by the matcher's own configuration."""
+        return PairResult.decode(value, bool(self.confidence), self.semi_dense is not None)
+
+    def _saturated_pair(self, left_image, right_image, ndisp, given, keep=None):
         """on_saturation for the pair that has just been launched: None when its features were fine (or nobody is to
-        look), else the map of the same pair behind the float32 library convolutions (written to `out` if given) - with
-        its confidence planes (written to `confidence_out` if given) where the matcher produces them.
+        look), else the PairResult of the same pair behind the float32 library convolutions, every field written to
+        the tensor `given` (a PairResult of the caller's tensors or None) holds for it.
         keep: the dict the pair's stages were handed out in; the repeated pair's stages replace them."""
         if not self.saturation_checked() or self.on_saturation == "ignore" or torch.cuda.is_current_stream_capturing():
             return None
@@ -1839,8 +1844,7 @@ class StereoMatcher(object):
                                                semi_dense=self.semi_dense)
         if keep is not None:
             keep.clear()
-        return self._library_twin.match(left_image, right_image, ndisp, out=out, keep=keep, confidence_out=confidence_out,
-                                        semi_out=semi_out)
+        return self._library_twin._match(left_image, right_image, ndisp, given, keep=keep)   # (it never repeats a pair)
 
     def match(self, left_image, right_image, ndisp, timer=_NO_TIMER, keep=None, _static_out=False, out=None,
               confidence_out=None, semi_out=None):
@@ -1850,14 +1854,12 @@ class StereoMatcher(object):
         A matcher with confidence measures returns (map, planes [K,H,W]); the planes follow the map's rules - a copy,
         or `confidence_out` (a contiguous float32 [K,H,W] device tensor) where one is given, next to `out`.
         A matcher with a semi-dense rule returns the sparse map as the last element - (map, sparse) or (map, planes,
-        sparse) - by the same rules, with `semi_out` (shaped like `out`) in the place of `confidence_out`."""
-        res = self._match(left_image, right_image, ndisp, timer=timer, keep=keep, _static_out=_static_out, out=out,
-                          confidence_out=confidence_out, semi_out=semi_out)
-        if not _static_out:
-            redo = self._saturated_pair(left_image, right_image, ndisp, out, keep, confidence_out, semi_out)
-            if redo is not None:
-                return redo
-        return res
+        sparse) - by the same rules, with `semi_out` (shaped like `out`) in the place of `confidence_out`.
+        (PairResult.public() is that shape; result_of() reads it back.)"""
+        given = PairResult(out, confidence_out, semi_out)
+        res = self._match(left_image, right_image, ndisp, given, timer=timer, keep=keep, _static_out=_static_out)
+        redo = None if _static_out else self._saturated_pair(left_image, right_image, ndisp, given, keep)
+        return (res if redo is None else redo).public()
 
     # ---- one pair, stage by stage (_match below is the schedule; INTEGRATION.md has the map) ----
     def _side_work(self, ws, L, R, D, want_flags):
@@ -2129,14 +2131,14 @@ class StereoMatcher(object):
         unless the tensor is its own (`given`) or `handed`: a fresh one (keep=) or the static buffer (match_graph)."""
         return t if (handed or given is not None) else t.clone()
 
-    def _match(self, left_image, right_image, ndisp, timer=_NO_TIMER, keep=None, _static_out=False, out=None,
-               confidence_out=None, semi_out=None):
-        """left/right: standardised float32 device tensors [H,W] (or [H,W,1]).  Returns the final left disparity
-        map [H,W] on the device.  The matcher's workspace is reused by the next call, so the map is handed out as a
-        copy - one [H,W] allocation + one copy per pair; pass `out` (a contiguous float32 [H,W] device tensor) and the
-        last kernel writes there instead: nothing is allocated but the conv activations.  `keep`, if a dict, receives
-        intermediate device tensors in the reference's [D,H,W] layout (tests).  A matcher with confidence measures
-        returns (map, planes), one with a semi-dense rule the sparse map behind them - see match()."""
+    def _match(self, left_image, right_image, ndisp, given=PairResult(None), timer=_NO_TIMER, keep=None, _static_out=False):
+        """left/right: standardised float32 device tensors [H,W] (or [H,W,1]).  Returns the PairResult of the pair: the
+        final left disparity map [H,W] on the device, the planes of a matcher with confidence measures and the sparse map
+        of one with a semi-dense rule.  The matcher's workspace is reused by the next call, so the map is handed out as a
+        copy - one [H,W] allocation + one copy per pair; with the caller's `out` in given.map (a contiguous float32 [H,W]
+        device tensor) the last kernel writes there instead: nothing is allocated but the conv activations; the other
+        fields follow the same rule.  `keep`, if a dict, receives intermediate device tensors in the reference's [D,H,W]
+        layout (tests)."""
         L = left_image.reshape(left_image.shape[0], left_image.shape[1]).contiguous()
         R = right_image.reshape(right_image.shape[0], right_image.shape[1]).contiguous()
         H, W = L.shape
@@ -2196,26 +2198,29 @@ class StereoMatcher(object):
         # the conv activations and never blocks the host.  views="both": one [2,H,W] tensor (and [2,K,H,W] planes) takes
         # the two views' results.
         both, k, fresh, pm = self.both, len(self.confidence), keep is not None, self.pixel_major()
-        lead = (2,) if both else ()
-        self._check_given(out, lead + (H, W), "out", "H,W", L)
-        if k or both:                              # (a left-only matcher without measures never looks at confidence_out)
-            self._check_given(confidence_out, lead + (k, H, W), "confidence_out", "K,H,W", L)
+        lead, semi = (2,) if both else (), self.semi_dense is not None
 
         def dest(given, spare):         # the caller's tensor, else the workspace's - under keep= a fresh one like it
             return given if given is not None else (torch.empty_like(spare) if fresh else spare)
-        res = dest(out, ws["both"] if both else ws["maps"][5])
-        planes = dest(confidence_out, ws["confidence"]) if k else None
-        semi = self.semi_dense is not None
+        # per result: the caller's keyword, the workspace's tensor (None: this matcher has no such result), the shape, and
+        # the shape as a refusal words it.  (A left-only matcher without measures never looks at confidence_out.)
+        rows = (("out", ws["both"] if both else ws["maps"][5], (H, W), "H,W"),
+                ("confidence_out", ws["confidence"] if k else None, (k, H, W), "K,H,W"),
+                ("semi_out", ws["sparse"] if semi else None, (H, W), "H,W"))
+        res = []
+        for t, (name, spare, shape, dims) in zip(given, rows):
+            if spare is not None or (both and name == "confidence_out"):
+                self._check_given(t, lead + shape, name, dims, L)
+            res.append(dest(t, spare) if spare is not None else None)
+        res = PairResult(*res)
         if semi:
-            self._check_given(semi_out, lead + (H, W), "semi_out", "H,W", L)
-            sparse = dest(semi_out, ws["sparse"])
-            selected, sizes = dest(None, ws["semi_selected"]), dest(None, ws["semi_sizes"])
+            # the selection and the size plane, one [H,W] per view, and each view's labelling scratch
+            selected, sizes = (dest(None, ws[key]).view(-1, H, W) for key in ("semi_selected", "semi_sizes"))
             scratch = [torch.empty_like(t) for t in ws["semi_scratch"]] if fresh else ws["semi_scratch"]
 
-        def semi_of(i):                 # view i's (sparse, selected, sizes, scratch)
-            if not semi:
-                return None
-            return (sparse[i], selected[i], sizes[i], scratch[i]) if both else (sparse, selected, sizes, scratch[0])
+        def results_of(i):              # where view i's results go (PostView's dst, planes and semi)
+            r = res.view(i, both)
+            return dict(dst=r.map, planes=r.planes, semi=(r.sparse, selected[i], sizes[i], scratch[i]) if semi else None)
         main_s = torch.cuda.current_stream()
         fork = both and timer is _NO_TIMER
         if both:
@@ -2226,25 +2231,21 @@ class StereoMatcher(object):
             if fork:
                 right_s.wait_stream(main_s)
             view = PostView("right", "_right", R, dr, dl, right_volume, None if fresh else ws["status_right"],
-                            torch.empty_like(ws["maps_right"]) if fresh else ws["maps_right"], res[1],
-                            planes[1] if k else None, right_s, semi_of(1))
+                            torch.empty_like(ws["maps_right"]) if fresh else ws["maps_right"], stream=right_s,
+                            **results_of(1))
             with torch.cuda.stream(view.stream):
                 self._post_view(view, D, pm, timer, keep)
             if fresh:
                 keep["cbca2_right"] = hwd_to_dhw(right_volume, D) if pm else right_volume.clone()
-        view = PostView("left", "", L, dl, dr, left_volume, None if fresh else ws["status"], m[2:5],
-                        res[0] if both else res, planes[0] if k and both else planes, main_s, semi_of(0))
+        view = PostView("left", "", L, dl, dr, left_volume, None if fresh else ws["status"], m[2:5], stream=main_s,
+                        **results_of(0))
         self._post_view(view, D, pm, timer, keep)
         if fork:
             main_s.wait_stream(right_s)
         if fresh:
             keep["wta"] = (dl, dr)
         handed = _static_out or fresh
-        res = self._hand_out(res, out, handed)
-        if not (k or semi):
-            return res
-        return ((res,) + ((self._hand_out(planes, confidence_out, handed),) if k else ())
-                + ((self._hand_out(sparse, semi_out, handed),) if semi else ()))
+        return PairResult(*(self._hand_out(t, g, handed) if t is not None else None for t, g in zip(res, given)))
 
     def _ingest_buffers(self, H, W):
         """Static float32 inputs + ingest scratch of the eager byte path: kept per shape, so that a pair allocates
@@ -2310,20 +2311,14 @@ class StereoMatcher(object):
         with torch.cuda.graph(graph):
             if prologue is not None:
                 prologue(*static)
-            out = self._match(static[0], static[1], D, _static_out=True)
+            out = self._match(static[0], static[1], D, _static_out=True).public()
         self._graphs[key] = (graph, static, out)
         return self._graphs[key]
 
     def _saturated_graph_pair(self, sl, sr, ndisp, out):
         """on_saturation behind a replay (one host synchronisation unless "ignore"): a repeated pair writes the static
         map - and the static confidence planes and sparse map, where the matcher produces them."""
-        outs = out if isinstance(out, tuple) else (out,)
-        given = {}
-        if self.confidence:
-            given["confidence_out"] = outs[1]
-        if self.semi_dense is not None:
-            given["semi_out"] = outs[-1]
-        self._saturated_pair(sl, sr, ndisp, outs[0], **given)
+        self._saturated_pair(sl, sr, ndisp, self.result_of(out))
 
     def _static_u8(self, left_u8, right_u8, H, W):
         """The static buffers of match_graph_u8: (float32 left, right, the byte images, the ingest scratch)."""

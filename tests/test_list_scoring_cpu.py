@@ -9,6 +9,7 @@ import os
 import pytest
 
 import evaluation as ev
+from pair_result import PairResult
 from conftest import GOLDEN_DIR
 
 _spec = importlib.util.spec_from_file_location("gen_list_report_golden", os.path.join(GOLDEN_DIR, "gen_list_report_golden.py"))
@@ -93,8 +94,8 @@ def test_left_only_one_pair(tmp_path):
     m = Map()
     scored = scorer.begin(3, "pair3", TRUTH, TRUTH_RIGHT)        # not --views both: the right truth is ignored
     assert scored.truths == [TRUTH]
-    scorer.score(scored, m, None, 0)
-    scorer.commit(scored, m)
+    scorer.score(scored, PairResult(m), 0)
+    scorer.commit(scored, PairResult(m))
     assert log == [("left", "score", id(m), 0), ("left", "commit", id(m), None)]
     path = tmp_path / "evalMCCNN.json"
     scorer.publish(scored, str(path))
@@ -109,10 +110,10 @@ def test_both_views_order_and_commits(tmp_path):
     scorer, report, log = _scorer("both", sparsifier=True)
     maps, planes = [Map(), Map()], [Map(), Map()]
     scored = scorer.begin(0, "pair0", TRUTH, TRUTH_RIGHT)
-    scorer.score(scored, maps, planes, 1)
+    scorer.score(scored, PairResult(maps, planes), 1)
     assert log == [("left", "score", id(maps[0]), 1), ("auc", "score", id(maps[0]), None),
                    ("right", "score", id(maps[1]), 1), ("auc", "score", id(maps[1]), None)]
-    scorer.commit(scored, maps)
+    scorer.commit(scored, PairResult(maps))
     assert log[4:] == [("left", "commit", id(maps[0]), None), ("right", "commit", id(maps[1]), None)]
     scorer.publish(scored, str(tmp_path / "e.json"))
     assert report.calls[-1][4] == gen.figures(2)
@@ -128,8 +129,8 @@ def test_both_views_without_right_truth(tmp_path):
     maps, planes = [Map(), Map()], [Map(), Map()]
     scored = scorer.begin(2, "pair2", TRUTH, None)
     assert report.calls == [("skip_right", 2, "pair2")]
-    scorer.score(scored, maps, planes, 0)
-    scorer.commit(scored, maps)
+    scorer.score(scored, PairResult(maps, planes), 0)
+    scorer.commit(scored, PairResult(maps))
     scorer.publish(scored, str(tmp_path / "e.json"))
     assert all(which != "right" for which, _, _, _ in log)
     assert [e[2] for e in log] == [id(maps[0])] * 3
@@ -155,9 +156,9 @@ def test_redo_commits_and_publishes_the_second_score_only(views, tmp_path):
     both = views == "both"
     first, redone = ([Map(), Map()], [Map(), Map()]) if both else (Map(), Map())
     scored = scorer.begin(0, "pair0", TRUTH, TRUTH_RIGHT)
-    scorer.score(scored, first, None, 0)
-    scorer.score(scored, redone, None, 0)
-    scorer.commit(scored, redone)
+    scorer.score(scored, PairResult(first), 0)
+    scorer.score(scored, PairResult(redone), 0)
+    scorer.commit(scored, PairResult(redone))
     scorer.publish(scored, str(tmp_path / "e.json"))
     ids = lambda maps: [id(m) for m in maps] if both else [id(maps)]      # noqa: E731
     assert [e[1:3] for e in log] == ([("score", i) for i in ids(first)] + [("score", i) for i in ids(redone)]
@@ -179,8 +180,8 @@ def test_two_slots_five_pairs_commit_in_list_order():
         if len(pending) == 2:
             scorer.commit(*pending.pop(0))
         scored = scorer.begin(n, "pair%d" % n, TRUTH, None)
-        scorer.score(scored, maps[n], None, n % 2)
-        pending.append((scored, maps[n]))
+        scorer.score(scored, PairResult(maps[n]), n % 2)
+        pending.append((scored, PairResult(maps[n])))
     while pending:
         scorer.commit(*pending.pop(0))
     assert [e[2] for e in log if e[1] == "commit"] == [id(m) for m in maps]

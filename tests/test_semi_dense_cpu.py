@@ -376,12 +376,41 @@ def test_list_reports_keep_the_bytes_on_record_without_and_under_the_flag(tmp_pa
 
 
 def test_split_result():
-    import list_matcher
-    m, p, s = np.zeros((3, 4)), np.zeros((2, 3, 4)), np.ones((3, 4))
-    assert list_matcher.split_result(m) == (m, None, None)
-    for res, want in (((m, p), (m, p, None)), ((m, s), (m, None, s)), ((m, p, s), (m, p, s))):
-        got = list_matcher.split_result(res)
-        assert all(a is b for a, b in zip(got, want))
+    """pair_result.PairResult: the public shape of every combination, and its inverse by configuration."""
+    from pair_result import PairResult
+    for both in (False, True):
+        lead = (2,) if both else ()
+        m, p, s = np.zeros(lead + (3, 4)), np.zeros(lead + (2, 3, 4)), np.ones(lead + (3, 4))
+        for has_p in (False, True):
+            for has_s in (False, True):
+                record = PairResult(m, p if has_p else None, s if has_s else None)
+                public = record.public()
+                if not (has_p or has_s):
+                    assert public is m
+                else:
+                    want = (m,) + ((p,) if has_p else ()) + ((s,) if has_s else ())
+                    assert isinstance(public, tuple) and len(public) == len(want)
+                    assert all(a is b for a, b in zip(public, want))
+                got = PairResult.decode(public, has_p, has_s)
+                assert all(a is b for a, b in zip(got, record)) and (got.planes is None) == (not has_p)
+                # one view: index v of every present field under views="both", the record itself otherwise
+                for v in range(2 if both else 1):
+                    view = record.view(v, both)
+                    if not both:
+                        assert view is record
+                    else:
+                        assert np.shares_memory(view.map, m[v]) and view.map.shape == (3, 4)
+                        assert (view.planes is None) == (not has_p) and (view.sparse is None) == (not has_s)
+                        assert not has_p or view.planes.shape == (2, 3, 4)
+                applied = record.apply(lambda t: t + 1)
+                assert [t is None for t in applied] == [t is None for t in record] and (applied.map == 1).all()
     both = np.zeros((2, 3, 4))
-    assert list_matcher.split_result((both, np.zeros((2, 2, 3, 4)), both))[2] is both
-    assert list_matcher.map_and_planes((m, p)) == (m, p) and list_matcher.map_and_planes(m) == (m, None)
+    assert PairResult.decode((both, np.zeros((2, 2, 3, 4)), both), True, True).sparse is both
+    # what no rule on dimensions can tell: a planes tensor and a sparse tensor of equal ndim (and of the map's)
+    planes, sparse = np.zeros((2, 3, 4)), np.ones((2, 3, 4))
+    got = PairResult.decode((both, planes, sparse), True, True)
+    assert got.map is both and got.planes is planes and got.sparse is sparse
+    got = PairResult.decode((both, planes), True, False)
+    assert got.planes is planes and got.sparse is None
+    got = PairResult.decode((both, sparse), False, True)
+    assert got.planes is None and got.sparse is sparse
