@@ -79,6 +79,26 @@ int mccnn_cost_volume(const float *fl, const float *fr, int H, int W, int C, int
 int mccnn_cost_volume_hwd(const float *fl, const float *fr, int H, int W, int C, int D, float *lcv_hwd, float *rcv_hwd,
                           int mode, mccnn_stream_t stream);
 
+/* The pixel-major MCCNN_CV_EXACT volumes with a VERTICAL SEARCH of +-vertical_range rows, for pairs whose rectification
+ * leaves a residual vertical disparity (not in the reference).  fl, fr: [H][W][64] float32; r = vertical_range, 0 <= r <= 4.
+ *   P(k; d,h,w) = the float32 score of left pixel (h,w) against right pixel (h+k, w-d): the 64 rounded products summed
+ *                 in NumPy's pairwise order (pf:89), exactly the arithmetic of MCCNN_CV_EXACT; defined for 0 <= w-d,
+ *                 w < W and 0 <= h+k < H.
+ *   S_L(d,h,w) = max over k = -r..r with 0 <= h+k < H of P(k; d,h,w)                 for w >= d       (left scores)
+ *   S_R(d,h,w) = max over k = -r..r with 0 <= h-k < H of P(k; d,h-k,w+d)             for w+d < W      (right scores)
+ * S_R matches right pixel (h,w) against left pixel (h-k, w+d): the same pairing seen from the other view.  For r > 0 it
+ * is NOT a copy of S_L; for r = 0 it is the reference's copy (pf:104).  Rows outside the image are skipped, not clamped.
+ * The maximum: candidates in ascending k; best = the first candidate; then best = s if (s > best or isnan(s)) else best.
+ * So a NaN candidate makes the score NaN and it stays NaN, and among equal values (+-0 included) the first one seen is
+ * kept.  Then the reference's border recurrences on S_L and S_R (pf:94-95, 105-106) and the negation (pf:111-112): the
+ * fill launch of mccnn_cost_volume_hwd, unchanged.  vertical_range = 0 is bit-identical to mccnn_cost_volume_hwd with
+ * MCCNN_CV_EXACT (the Dp - D pad entries of a pixel are not written either way).
+ * MCCNN_E_INVALID: null pointers, vertical_range outside [0, 4].  MCCNN_E_UNSUPPORTED: outside 2 <= D <= 1024,
+ * D <= W - 2, C = 64, one volume row below 2 GiB.  No allocation, no synchronisation: capturable. */
+#define MCCNN_VERTICAL_RANGE_MAX 4
+int mccnn_cost_volume_vertical_hwd(const float *fl, const float *fr, int H, int W, int C, int D, int vertical_range,
+                                   float *lcv_hwd, float *rcv_hwd, mccnn_stream_t stream);
+
 /* ---- a2 for the "accurate" network (Zbontar & LeCun 2016, sec. 3.2): the decision MLP on the matrix cores -----------
  * s(h,w,d) = sigmoid(wf . relu(W_n ... relu(W_2 . relu(aL[h,w] + aR[h,w-d]) + b_2) ... + b_n) + bf) for w >= d;
  * lcv = -s at (h,w,d), rcv = -s at (h,w-d,d); the border columns are filled by the same recurrences, the same kernels,

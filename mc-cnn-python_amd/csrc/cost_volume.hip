@@ -392,6 +392,225 @@ __global__ __launch_bounds__(256, 3) void cost_volume_exact_pairs_kernel(const f
     }
 }
 
+// ---- vertical search (include/mccnn.h: mccnn_cost_volume_vertical_hwd) ------------------------------------------------
+// S_L(d,h,w) = max_k P(k; d,h,w) pairs left pixel (h,w) with right pixels (h+k, w-d); S_R(d,h,w) pairs right pixel (h,w)
+// with left pixels (h-k, w+d).  Seen from its own pixel, either view is the same job: the pixel's features stay in
+// registers, the OTHER view's rows h +- k are searched, and only the pixel's OWN volume is written - for k != 0 an
+// entry of the other volume takes its maximum over other products, so nothing but k = 0 is shared and the scatter
+// along the score tile's anti-diagonals, half of cost_volume_exact_pairs_kernel's store phase, has nothing to carry.
+// Hence ONE kernel launched for both views (blockIdx.z): the right view is the left view's code on the horizontally
+// mirrored pair with the roles of the images swapped - "search column" c is image column c on the left and W - 1 - c on
+// the right, where the match of search column c at disparity d lies at search column c - d in both - and with the
+// candidate rows walked the other way (row h - k for ascending k).  Products commute, so the 64 rounded products and
+// their summation order per score are those of the pairs kernel: the same ghost lane, the same DPP operand, the same
+// ring indexed by (search column & 127).
+// What the vertical search costs in LDS: the ring would have to exist once per candidate row for a tile's 63 reusable
+// columns to survive until the next tile, 34 KiB each - beside the 17 KiB left tile that is one workgroup per CU at
+// r = 2.  So the ring is re-staged for every (tile, candidate): all 128 rows (8 x 16 bytes per thread, out of rows the
+// L2 holds: a workgroup reads each of its 2r + 1 rows once per tile) instead of the 64 new ones, fetched into
+// registers under the products of the candidate before and written behind them.  The running maximum lives in the
+// score tile: entry (wl, d) is read, compared and written by the one thread that computes it, so the candidates need
+// no synchronisation beyond the ring's, and every voxel is stored once, behind the last candidate, negated there.
+// Both launches together do 2 (2r + 1) = 4r + 2 product sets; the k = 0 set is computed once per view.
+__device__ __forceinline__ void cvv_pair_scores(const float (&a)[CV_C], const float *b, float &s_out, float &sn_out)
+{
+    float acc[8], acn[8];                                // this lane's score for d_even; for d_even + 1 (neighbour's row)
+    // numpy pairwise_sum, n = 64, as in cost_volume_exact_pairs_kernel: the same instruction blocks
+    float4 n0 = *reinterpret_cast<const float4 *>(b), n1 = *reinterpret_cast<const float4 *>(b + 4);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float bv[8] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w};
+        if (i < 7) {
+            n0 = *reinterpret_cast<const float4 *>(b + (i + 1) * 8);
+            n1 = *reinterpret_cast<const float4 *>(b + (i + 1) * 8 + 4);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; j += 4) {
+            if (i == 0) {
+                asm volatile("v_mul_f32 %0, %8, %12\n\tv_mul_f32 %1, %9, %13\n\tv_mul_f32 %2, %10, %14\n\tv_mul_f32 %3, %11, %15\n\t"
+                             "v_mul_f32_dpp %4, %12, %8 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                             "v_mul_f32_dpp %5, %13, %9 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                             "v_mul_f32_dpp %6, %14, %10 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                             "v_mul_f32_dpp %7, %15, %11 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+                             : "=&v"(acc[j]), "=&v"(acc[j + 1]), "=&v"(acc[j + 2]), "=&v"(acc[j + 3]),
+                               "=&v"(acn[j]), "=&v"(acn[j + 1]), "=&v"(acn[j + 2]), "=&v"(acn[j + 3])
+                             : "v"(a[j]), "v"(a[j + 1]), "v"(a[j + 2]), "v"(a[j + 3]),
+                               "v"(bv[j]), "v"(bv[j + 1]), "v"(bv[j + 2]), "v"(bv[j + 3]));
+            } else {
+                float t0, t1, t2, t3;
+                asm volatile("v_mul_f32 %8, %12, %16\n\tv_mul_f32 %9, %13, %17\n\tv_mul_f32 %10, %14, %18\n\tv_mul_f32 %11, %15, %19\n\t"
+                             "v_add_f32 %0, %0, %8\n\tv_add_f32 %1, %1, %9\n\tv_add_f32 %2, %2, %10\n\tv_add_f32 %3, %3, %11\n\t"
+                             "v_mul_f32_dpp %8, %16, %12 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                             "v_mul_f32_dpp %9, %17, %13 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                             "v_mul_f32_dpp %10, %18, %14 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                             "v_mul_f32_dpp %11, %19, %15 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                             "v_add_f32 %4, %4, %8\n\tv_add_f32 %5, %5, %9\n\tv_add_f32 %6, %6, %10\n\tv_add_f32 %7, %7, %11"
+                             : "+v"(acc[j]), "+v"(acc[j + 1]), "+v"(acc[j + 2]), "+v"(acc[j + 3]),
+                               "+v"(acn[j]), "+v"(acn[j + 1]), "+v"(acn[j + 2]), "+v"(acn[j + 3]),
+                               "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3)
+                             : "v"(a[i * 8 + j]), "v"(a[i * 8 + j + 1]), "v"(a[i * 8 + j + 2]), "v"(a[i * 8 + j + 3]),
+                               "v"(bv[j]), "v"(bv[j + 1]), "v"(bv[j + 2]), "v"(bv[j + 3]));
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    const float s = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+    const float sn = ((acn[0] + acn[1]) + (acn[2] + acn[3])) + ((acn[4] + acn[5]) + (acn[6] + acn[7]));
+    s_out = 0.f + s;  // np.sum adds the pairwise result to the identity
+    sn_out = 0.f + sn;
+}
+
+// the definition's maximum: a candidate replaces the best so far when it is larger or NaN (NaN then stays: nothing is
+// larger than it, and a later NaN is NaN again); among equal values the first one seen is kept
+__device__ __forceinline__ void cvv_take(float *best, float s, bool first)
+{
+    const float b = first ? s : *best;
+    *best = (s > b || s != s) ? s : b;
+}
+
+__global__ __launch_bounds__(256, 3) void cost_volume_vertical_kernel(const float *__restrict__ fl,
+                                                                      const float *__restrict__ fr, int H, int W, int D,
+                                                                      int vrange, float *__restrict__ lcv,
+                                                                      float *__restrict__ rcv, int Dp)
+{
+    constexpr int RING = 128;
+    __shared__ __attribute__((aligned(16))) float sR[RING * CV_LD];
+    __shared__ __attribute__((aligned(16))) float sL[CV_TW * CV_LD];
+    const bool right = blockIdx.z != 0;                 // the view whose volume this workgroup writes
+    const float *const fa = right ? fr : fl;            // its own features (registers) ...
+    const float *const fb = right ? fl : fr;            // ... and the other view's (ring)
+    const int mir = right ? W - 1 : 0, sgn = right ? -1 : 1;   // image column of search column c: mir + sgn * c
+    const int w0 = (int)blockIdx.x * CVP_TW - 1, h = blockIdx.y;   // lane 0: search column w0 (ghost)
+    const int tid = threadIdx.x;
+    // the candidates k = klo .. khi, ascending: the other view's row h + sgn * k lies inside the image (k = 0 always does)
+    const int klo = right ? max(-vrange, h - (H - 1)) : max(-vrange, -h);
+    const int khi = right ? min(vrange, h) : min(vrange, H - 1 - h);
+    // the 16 bytes at channels 4 c4 .. of search column c (clamped: kept as it comes, never part of a stored score)
+    auto at = [&](const float *f, int row, int c, int c4) {
+        return reinterpret_cast<const cv_f4 *>(f + ((size_t)row * W + (mir + sgn * min(max(c, 0), W - 1))) * CV_C + c4 * 4);
+    };
+    {
+        cv_f4 pl[4], pr[8];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int i = tid + q * 256;
+            pl[q] = *at(fa, h, w0 + (i >> 4), i & 15);
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {     // the first tile's search columns w0 - 63 .. w0 + 64 of the first candidate's row
+            const int i = tid + q * 256;
+            pr[q] = *at(fb, h + sgn * klo, w0 - (CV_DT - 1) + (i >> 4), i & 15);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int i = tid + q * 256;
+            *reinterpret_cast<cv_f4 *>(&sL[(i >> 4) * CV_LD + (i & 15) * 4]) = pl[q];
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int i = tid + q * 256, x = w0 - (CV_DT - 1) + (i >> 4);
+            *reinterpret_cast<cv_f4 *>(&sR[(x & (RING - 1)) * CV_LD + (i & 15) * 4]) = pr[q];
+        }
+    }
+    __syncthreads();
+
+    const int wl = tid & 63, dq = tid >> 6;  // dq is wave-uniform: each wave owns 16 disparities = 8 pairs of a tile
+    const int w = w0 + wl;
+    float a[CV_C];
+#pragma unroll
+    for (int c4 = 0; c4 < 16; ++c4) {
+        const float4 v = *reinterpret_cast<const float4 *>(&sL[wl * CV_LD + c4 * 4]);
+        a[c4 * 4 + 0] = v.x; a[c4 * 4 + 1] = v.y; a[c4 * 4 + 2] = v.z; a[c4 * 4 + 3] = v.w;
+    }
+    constexpr int TP = CV_LD;
+    float *const sT = sL;               // every thread holds its own features in registers from here on
+    // The store phase is the pairs kernel's for its left volume: 16 lanes x four disparities = one pixel's 64
+    // disparities of a tile, a thread owns 4 quads per tile; FULL quads leave as one 16-byte store, a quad that
+    // straddles w = d or the last disparity goes out float by float.  Entry d of search column ww exists iff
+    // d <= min(ww, D - 1), in either view.
+    const int q4 = (tid & 15) * 4, sub = tid >> 4;
+    const int dlast = D - 1;
+    const int Dp4 = Dp * 4;
+    // byte offset of quad 0 of tile 0 within the image row (below 2^31: checked at the entry point; modulo 2^32 for a
+    // quad outside the row, which is never stored); the next quad is 16 search columns on: 16 pixels up or down
+    const unsigned vo = (unsigned)((mir + sgn * (w0 + 1 + sub)) * Dp + q4) * 4u;
+    char *const vrow = reinterpret_cast<char *>((right ? rcv : lcv) + (size_t)h * W * Dp);
+    __syncthreads();
+#pragma unroll 1
+    for (int d0 = 0; d0 < D && w0 + CV_TW - 1 >= d0; d0 += CV_DT) {   // beyond: every (w, d) has w < d (border fill)
+#pragma unroll 1
+        for (int k = klo; k <= khi; ++k) {
+            const bool first = k == klo, last = k == khi;
+            // the rows of the next (tile, candidate) on their way; behind the last one they are fetched for nothing
+            const int nd0 = last ? d0 + CV_DT : d0, nrow = h + sgn * (last ? klo : k + 1);
+            // (their first half under the products, like the pairs kernel's four; all eight beside the own features do
+            // not fit into the registers of three workgroups per CU - 40 bytes of scratch - so the second half is
+            // fetched behind the products and lands under the tile's stores)
+            cv_f4 nx[4], ny[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int i = tid + q * 256;
+                nx[q] = *at(fb, nrow, w0 - nd0 - (CV_DT - 1) + (i >> 4), i & 15);
+            }
+#pragma unroll 1
+            for (int kk = 0; kk < 8; ++kk) {
+                const int dloc = dq * 16 + 2 * kk;                   // the even disparity of the pair (tile-relative)
+                const int r = (w - d0 - dloc) & (RING - 1);          // ring row of search column w - d_even
+                float s, sn;
+                cvv_pair_scores(a, &sR[r * CV_LD], s, sn);
+                const int d = d0 + dloc;
+                if (wl >= 1 && w < W) {
+                    if (d < D && w >= d) cvv_take(&sT[wl * TP + dloc], s, first);
+                    if (d + 1 < D && w >= d + 1) cvv_take(&sT[wl * TP + dloc + 1], sn, first);
+                }
+            }
+            __syncthreads();                         // this candidate's products are done: the ring is free
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int i = tid + (q + 4) * 256;
+                ny[q] = *at(fb, nrow, w0 - nd0 - (CV_DT - 1) + (i >> 4), i & 15);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int i = tid + q * 256, x = w0 - nd0 - (CV_DT - 1) + (i >> 4);
+                *reinterpret_cast<cv_f4 *>(&sR[(x & (RING - 1)) * CV_LD + (i & 15) * 4]) = nx[q];
+            }
+            if (last) {                            // the score tile holds the maxima: negate (pf:111-112) and store
+                const int d = d0 + q4;               // the first disparity of this thread's quads
+                unsigned rag = 0;
+                cv_f4 v[4];
+                int lim[4];                          // (worked out per tile: four registers less across the products)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int px = 1 + sub + 16 * j, ww = w0 + px;
+                    lim[j] = (px < CV_TW && ww < W) ? min(ww, dlast) : -1;
+                    v[j] = *reinterpret_cast<const cv_f4 *>(&sT[min(px, CV_TW - 1) * TP + q4]);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool full = d + 3 <= lim[j];
+                    if (__builtin_expect(full, 1))
+                        cvp_store16(vrow + (vo + (unsigned)(d0 * 4 + sgn * j * 16 * Dp4)), -1.f * v[j]);
+                    rag |= (d <= lim[j] && !full) ? 1u << j : 0u;
+                }
+                for (unsigned m = rag; m; m &= m - 1) {
+                    const int j = __builtin_ctz(m), px = 1 + sub + 16 * j;
+                    float *dst = reinterpret_cast<float *>(vrow + (vo + (unsigned)(d0 * 4 + sgn * j * 16 * Dp4)));
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (d + e <= lim[j]) dst[e] = -1.f * sT[px * TP + q4 + e];
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int i = tid + (q + 4) * 256, x = w0 - nd0 - (CV_DT - 1) + (i >> 4);
+                *reinterpret_cast<cv_f4 *>(&sR[(x & (RING - 1)) * CV_LD + (i & 15) * 4]) = ny[q];
+            }
+            __syncthreads();                        // the ring holds the next candidate's rows, the score tile has been read
+        }
+    }
+}
+
 // ---- MFMA variant ---------------------------------------------------------------------------------------------
 // One wave computes a 32(w) x 32(w') block of S = <fl[w], fr[w']>; a workgroup of 4 waves covers 64 w x 64 w' and
 // keeps only the band 0 <= w-w' < D.  A/B operands: lane l holds pixel l&31, channels 8 (l>>5) .. +7 of a 16-channel
@@ -908,6 +1127,36 @@ extern "C" int mccnn_cost_volume_hwd(const float *fl, const float *fr, int H, in
     int rc = check_launch("mccnn_cost_volume_hwd");
     if (rc) return rc;
     return launch_cost_volume_fill_hwd(lcv_hwd, rcv_hwd, D, Dp, H, W, s, "mccnn_cost_volume_hwd(fill)");
+}
+
+extern "C" int mccnn_cost_volume_vertical_hwd(const float *fl, const float *fr, int H, int W, int C, int D,
+                                              int vertical_range, float *lcv_hwd, float *rcv_hwd, mccnn_stream_t stream)
+{
+    using namespace mccnn;
+    MCCNN_REQUIRE(fl && fr && lcv_hwd && rcv_hwd, MCCNN_E_INVALID, "mccnn_cost_volume_vertical_hwd: null pointer");
+    MCCNN_REQUIRE(vertical_range >= 0 && vertical_range <= MCCNN_VERTICAL_RANGE_MAX, MCCNN_E_INVALID,
+                  "mccnn_cost_volume_vertical_hwd: vertical_range=%d outside [0, %d]", vertical_range,
+                  MCCNN_VERTICAL_RANGE_MAX);
+    MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "mccnn_cost_volume_vertical_hwd: non-positive size");
+    MCCNN_REQUIRE(C == CV_C, MCCNN_E_UNSUPPORTED, "mccnn_cost_volume_vertical_hwd: C=%d, kernels are built for 64 channels", C);
+    MCCNN_REQUIRE(D >= 2 && D <= 1024, MCCNN_E_UNSUPPORTED, "mccnn_cost_volume_vertical_hwd: D=%d outside [2, 1024]", D);
+    MCCNN_REQUIRE(D <= W - 2, MCCNN_E_UNSUPPORTED,
+                  "mccnn_cost_volume_vertical_hwd: D=%d needs W >= D+2 (the reference's border recurrence pf:106 is "
+                  "degenerate beyond that), W=%d", D, W);
+    MCCNN_REQUIRE(H <= 65535, MCCNN_E_UNSUPPORTED, "mccnn_cost_volume_vertical_hwd: H=%d > 65535 rows exceed the grid", H);
+    const int Dp = mccnn_hwd_pitch(D);
+    MCCNN_REQUIRE((size_t)W * Dp * 4 < ((size_t)1 << 31), MCCNN_E_UNSUPPORTED,
+                  "mccnn_cost_volume_vertical_hwd: a %d x %d row exceeds a buffer descriptor's reach", W, D);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(cdiv(W, CVP_TW), H, 1);
+    if (vertical_range == 0)      // one candidate: both volumes out of the same products (pf:104), the pairs kernel as it is
+        hipLaunchKernelGGL(cost_volume_exact_pairs_kernel, grid, dim3(256), 0, s, fl, fr, H, W, D, lcv_hwd, rcv_hwd, Dp);
+    else
+        hipLaunchKernelGGL(cost_volume_vertical_kernel, dim3(grid.x, grid.y, 2), dim3(256), 0, s, fl, fr, H, W, D,
+                           vertical_range, lcv_hwd, rcv_hwd, Dp);
+    int rc = check_launch("mccnn_cost_volume_vertical_hwd");
+    if (rc) return rc;
+    return launch_cost_volume_fill_hwd(lcv_hwd, rcv_hwd, D, Dp, H, W, s, "mccnn_cost_volume_vertical_hwd(fill)");
 }
 
 extern "C" int mccnn_cost_volume_fill(float *lcv, float *rcv, int D, int H, int W, int pixel_major, mccnn_stream_t stream)

@@ -45,6 +45,7 @@ SIGNATURES = {
     "mccnn_last_error_string": (ctypes.c_char_p, []),
     "mccnn_cost_volume": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "mccnn_cost_volume_hwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "mccnn_cost_volume_vertical_hwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mccnn_cost_volume_fill": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "mccnn_decision_pack_bytes": (_sz, [_i, _i, _i]),
     "mccnn_decision_pack": (_i, [_vp, _i, _i, _f, _i, _vp, _vp]),

@@ -125,6 +125,13 @@ parser.add_argument("--paper_sgm", action="store_true",
                     help="semiglobal matching as the paper defines it: the four directions each computed from the same "
                          "volume and averaged (the reference composes them one after the other on one array, "
                          "process_functional.py:195-210, and its average is the identity)")
+parser.add_argument("--vertical_range", type=int, default=0,
+                    help="for imperfectly rectified pairs: every pixel is also compared with the other view's pixels up to "
+                         "this many rows above and below (0 .. 4) and keeps its best score per disparity "
+                         "(include/mccnn.h: mccnn_cost_volume_vertical_hwd); everything behind the cost volume is "
+                         "unchanged.  0 (default): the reference's row-to-row comparison.  Costs a point or two on "
+                         "well-rectified pairs and 4 x range + 2 times the cost volume's products; bit-exact fast "
+                         "network only: not with --fast, --separable_cbca, --paper_support_regions or --arch accurate")
 parser.add_argument("--numpy1_promotion", action="store_true",
                     help="evaluate the sub-pixel formula as NumPy < 2 promotes its scalars (float64, rounded once), "
                          "i.e. as the reference's own Python 2.7 environment does; differs by <= 2.5e-5 px")
@@ -349,6 +356,17 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.fast and args.exact:
         parser.error("--fast and --exact exclude each other")
+    if not 0 <= args.vertical_range <= 4:
+        parser.error("--vertical_range: %d outside [0, 4]" % args.vertical_range)
+    if args.vertical_range:
+        for flag, on, why in (("--fast", args.fast, "the matrix-core cost volume has no vertical search"),
+                              ("--separable_cbca", args.separable_cbca, "the vertical search writes pixel-major volumes, "
+                               "the separable aggregation starts plane-major"),
+                              ("--paper_support_regions", args.paper_support_regions, "the vertical search writes "
+                               "pixel-major volumes, the two-view support regions start plane-major"),
+                              ("--arch accurate", args.arch == "accurate", "the decision network has no vertical search")):
+            if on:
+                parser.error("--vertical_range is not available with %s: %s" % (flag, why))
     layout = datasets.get(args.dataset)
     try:
         eval_thresholds = layout.parse_thresholds(args.eval_thresholds if args.eval_thresholds is not None
@@ -448,7 +466,7 @@ def main(argv=None):
             extras=dict(both_view_support=args.paper_support_regions,
                         interpolation_directions=16 if args.paper_interpolation else 4,
                         occlusion_from_left=args.paper_interpolation, numpy1_promotion=args.numpy1_promotion,
-                        sgm_independent_directions=args.paper_sgm),
+                        sgm_independent_directions=args.paper_sgm, vertical_range=args.vertical_range),
             confidence=conf_names, views=args.views, semi_dense=semi_rule)
 
     def save(result, out):

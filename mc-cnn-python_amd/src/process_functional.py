@@ -27,6 +27,9 @@ Opt-in departures from the reference's results (defaults reproduce it):
                                              the four passes on one aliased array (semi_global_matching returns its
                                              argument) and its average is the identity; that stays the default.  With
                                              the switch on SGM_average leaves its arguments unmodified.
+    VERTICAL_RANGE           0 | 1 .. 4    - compute_cost_volume for imperfectly rectified pairs: every pixel keeps, per
+                                             disparity, its best score over the other view's rows h - R .. h + R
+                                             (include/mccnn.h: mccnn_cost_volume_vertical_hwd; "exact" mode, ndisp <= 1024)
     NUMPY1_PROMOTION         False | True  - sub-pixel formula evaluated as NumPy < 2 promotes its scalars (float64,
                                              rounded once): what the reference's own Python 2.7 + NumPy 1.14 computes;
                                              the default is NumPy >= 2's float32 chain, which the golden vectors pin
@@ -49,6 +52,7 @@ INTERPOLATION_DIRECTIONS = 4
 OCCLUSION_FROM_LEFT = False
 NUMPY1_PROMOTION = False
 SGM_INDEPENDENT_DIRECTIONS = False
+VERTICAL_RANGE = 0
 
 _CV_MODES = {"exact": hip.MCCNN_CV_EXACT, "mfma": hip.MCCNN_CV_MFMA}
 _CBCA_ORDERS = {"separable": hip.MCCNN_CBCA_SEPARABLE, "reference": hip.MCCNN_CBCA_REFERENCE_ORDER,
@@ -115,6 +119,11 @@ def compute_cost_volume(featuresl, featuresr, ndisp):
     """pf:78-113."""
     fl, was_np = _dev(featuresl)
     fr, _ = _dev(featuresr)
+    if VERTICAL_RANGE:
+        if COST_VOLUME_MODE != "exact":
+            raise ValueError("VERTICAL_RANGE=%r: the vertical search exists for COST_VOLUME_MODE 'exact' only" % VERTICAL_RANGE)
+        hl, hr = sd.cost_volume_vertical_hwd(fl, fr, int(ndisp), VERTICAL_RANGE)
+        return _ret(sd.hwd_to_dhw(hl, int(ndisp)), was_np), _ret(sd.hwd_to_dhw(hr, int(ndisp)), was_np)
     lcv, rcv = sd.cost_volume(fl, fr, int(ndisp), _CV_MODES[COST_VOLUME_MODE])
     return _ret(lcv, was_np), _ret(rcv, was_np)
 

@@ -185,6 +185,26 @@ def cost_volume_hwd(fl, fr, ndisp, out=None, mode=hip.MCCNN_CV_EXACT):
     return lcv, rcv
 
 
+VERTICAL_RANGE_MAX = 4         # mccnn_cost_volume_vertical_hwd
+
+
+def cost_volume_vertical_hwd(fl, fr, ndisp, vertical_range, out=None):
+    """The bit-exact pixel-major volumes [H,W,Dp] with a vertical search of +-vertical_range rows (0 .. 4) for imperfectly
+    rectified pairs (include/mccnn.h: mccnn_cost_volume_vertical_hwd has the definition): each view's pixel keeps, per
+    disparity, its best score over the other view's rows h - r .. h + r.  0: the bits of cost_volume_hwd."""
+    H, W, C = fl.shape
+    dp = hwd_pitch(ndisp)
+    if out is None:
+        lcv = torch.zeros((H, W, dp), dtype=torch.float32, device=fl.device)
+        rcv = torch.zeros((H, W, dp), dtype=torch.float32, device=fl.device)
+    else:
+        lcv, rcv = out
+    hip.check(hip.load().mccnn_cost_volume_vertical_hwd(hip.ptr(fl), hip.ptr(fr), H, W, C, int(ndisp), int(vertical_range),
+                                                        hip.ptr(lcv), hip.ptr(rcv), hip.stream()),
+              "mccnn_cost_volume_vertical_hwd")
+    return lcv, rcv
+
+
 # ---- a2 for the accurate network: the decision MLP per (pixel, disparity) ------------------------------------------
 DECISION_UNITS = 384                     # csrc/decision_mfma.hip
 DECISION_MAPS = (64, 112)
@@ -1692,12 +1712,16 @@ class StereoMatcher(object):
         # sgm_independent_directions: the paper's SGM - the four directions each from the same volume, averaged
         # (sgm_average_independent_hwd) - instead of the reference's four passes composed on one array
         self.extras = dict(both_view_support=False, interpolation_directions=4, occlusion_from_left=False,
-                           numpy1_promotion=False, sgm_independent_directions=False)
+                           numpy1_promotion=False, sgm_independent_directions=False, vertical_range=0)
         if extras:
             unknown = set(extras) - set(self.extras)
             if unknown:
                 raise ValueError("unknown extras: %s" % sorted(unknown))
             self.extras.update(extras)
+        # vertical_range: the cost volume's vertical search for imperfectly rectified pairs (cost_volume_vertical_hwd)
+        # in the place of cost_volume_hwd; every later stage is the same.  0 (default): nothing changes - the same
+        # launches, workspace and graphs.  Only where the bit-exact dot-product volume is written pixel-major.
+        self._check_vertical_range()
         # confidence measures of the returned map (CONFIDENCE_MEASURES; names in any order, planes in that order): one
         # more launch per pair behind the post-processing, and every match entry returns (map, planes [K,H,W]).
         # Empty (default): nothing changes - no launch, no buffer, the map alone is returned.
@@ -1725,6 +1749,21 @@ class StereoMatcher(object):
         self._side = None
         self._right = None
         self._ingest = None
+
+    def _check_vertical_range(self):
+        r = self.extras["vertical_range"]
+        if isinstance(r, bool) or not isinstance(r, int) or not 0 <= r <= VERTICAL_RANGE_MAX:
+            raise ValueError("vertical_range must be an integer in [0, %d], not %r" % (VERTICAL_RANGE_MAX, r))
+        if r == 0:
+            return
+        if self.accurate:
+            raise ValueError("vertical_range=%d: the accurate network's decision stage has no vertical search" % r)
+        if self.cv_mode != hip.MCCNN_CV_EXACT:
+            raise ValueError("vertical_range=%d: the matrix-core cost volume (MCCNN_CV_MFMA) has no vertical search" % r)
+        if not self.pixel_major():
+            raise ValueError("vertical_range=%d: the vertical search writes pixel-major volumes, and this configuration's "
+                             "cost volume starts plane-major (layout='plane_major', the separable aggregation order or "
+                             "both_view_support)" % r)
 
     def _right_stream(self):
         """The stream of the right volume's chain of aggregation launches: this matcher's own (like its side stream), so
@@ -1926,8 +1965,14 @@ class StereoMatcher(object):
         if self.accurate:
             return self._cost_volumes_accurate(ws, fl, fr, D, dhw, hwd, timer)
         direct = self.pixel_major() and D <= COST_VOLUME_HWD_MAX_D
+        vertical = self.extras["vertical_range"]
+        if vertical and not direct:
+            raise ValueError("vertical_range=%d: the vertical search writes pixel-major volumes of at most %d disparities, "
+                             "not %d" % (vertical, COST_VOLUME_HWD_MAX_D, D))
         timer.start("cost_volume")
-        if direct:
+        if vertical:
+            left, right = cost_volume_vertical_hwd(fl, fr, D, vertical, out=(hwd[2], hwd[3]))
+        elif direct:
             left, right = cost_volume_hwd(fl, fr, D, out=(hwd[2], hwd[3]), mode=self.cv_mode)
         else:
             left, right = cost_volume(fl, fr, D, self.cv_mode, out=(dhw[0], dhw[1]))
