@@ -32,6 +32,33 @@
  *   support   mccnn_support_bytes(H,W) bytes: plane 0 [H][W] uint32 words (four 5-bit cross-arm lengths + 12-bit
  *             region size, mccnn_support_t), then four derived planes private to the aggregation kernels
  *   maps      [H][W]        float32 disparity maps, int32 status / region counts
+ *
+ * Memory contract (tests/test_memory_contract_gpu.py pins every sentence; "families" below note where one differs)
+ *   Alignment.  On the pixel-major path - mccnn_cross_arms(_pair), mccnn_cost_volume_hwd (MCCNN_CV_EXACT),
+ *     mccnn_cost_volume_vertical_hwd, mccnn_cost_volume_fill, mccnn_cbca_iter_hwd*, mccnn_cbca_iter_hwd_long*,
+ *     mccnn_cbca_iter_prog*, the mccnn_sgm_* entry points, mccnn_wta_hwd, mccnn_subpixel_hwd, mccnn_dhw_to_hwd and
+ *     mccnn_hwd_to_dhw - volumes, images, feature tensors and maps need only the alignment of their element, 4 bytes:
+ *     the kernels reach them through vector loads and stores of 4 to 16 bytes per lane, which the hardware serves at
+ *     any 4-byte-aligned address (the layout changes pick their 16-byte transposes only between two 16-byte-aligned
+ *     bases).  A caller may carve all of those out of one arena.  The other entry points (plane-major aggregation,
+ *     matrix-core cost volume, features, post-processing) have only ever been run on 16-byte-aligned pointers: keep
+ *     theirs so.  Buffers whose layout is
+ *     PRIVATE to the library must start on a 16-byte boundary: the support buffer (mccnn_support_bytes), the program
+ *     buffers (mccnn_cbca_prog_bytes) and the SGM flag / scratch buffer (mccnn_sgm_scratch_bytes) - their planes are laid
+ *     out in 16-byte steps from the base and read by scalar and packed loads.  A pointer that is not is refused on the
+ *     host before anything is launched: MCCNN_E_INVALID for support and program buffers, MCCNN_E_SCRATCH for the SGM
+ *     buffer (as mccnn_speckle_filter answers for its scratch).  The evaluation, ingest, KITTI and semi-dense entry
+ *     points state the alignment of their own scratch and result buffers where they are declared.
+ *   Pads.  A pixel-major volume has Dp - D pad entries per pixel (D % 4 != 0).  The pad entries of an INPUT never
+ *     influence an entry d < D of any output, whatever they hold (stale costs, +-inf, NaN): every minimum, sum and
+ *     neighbour lookup across d is masked to d < D.  The pad entries of an OUTPUT are left untouched by
+ *     mccnn_cost_volume_hwd, mccnn_cost_volume_vertical_hwd and mccnn_cost_volume_fill(pixel_major != 0); after every
+ *     other call that writes a pixel-major volume (the aggregation families, the SGM passes, mccnn_sgm_first_pass,
+ *     mccnn_dhw_to_hwd, ...) they are unspecified.
+ *   Bounds.  No call writes a byte outside the buffers documented for it, and no call reads one in a way that changes a
+ *     result.  (Some kernels do read a few elements past a row or a plane inside the SAME buffer - a prefetch that is
+ *     never used - and steer lanes without work to an offset their buffer descriptor drops.)  Buffers sized by a query
+ *     (mccnn_support_bytes, mccnn_cbca_prog_bytes, mccnn_sgm_scratch_bytes) need exactly that many bytes.
  */
 #ifndef MCCNN_H
 #define MCCNN_H
@@ -45,7 +72,7 @@ extern "C" {
 
 typedef void *mccnn_stream_t; /* hipStream_t */
 
-#define MCCNN_ABI_VERSION 7 /* 2: window-mask plane, *_hwd entry points; 3: saturation flags; 4: program-driven CBCA; 5: skip programs; 6: one-volume launches; 7: refresh launches, SGM flag planes as a call of their own; still 7 with the mccnn_ingest_* and the mccnn_decision_* / mccnn_cost_volume_accurate* entry points and mccnn_sample_patches, and with mccnn_evaluate, and with the mccnn_kitti_* entry points and mccnn_evaluate_kitti, and with mccnn_confidence / mccnn_confidence_hwd: purely additive, nothing that existed changed */
+#define MCCNN_ABI_VERSION 7 /* 2: window-mask plane, *_hwd entry points; 3: saturation flags; 4: program-driven CBCA; 5: skip programs; 6: one-volume launches; 7: refresh launches, SGM flag planes as a call of their own; still 7 with the mccnn_ingest_* and the mccnn_decision_* / mccnn_cost_volume_accurate* entry points and mccnn_sample_patches, and with mccnn_evaluate, and with the mccnn_kitti_* entry points and mccnn_evaluate_kitti, and with mccnn_confidence / mccnn_confidence_hwd: purely additive, nothing that existed changed; still 7 with the memory contract below: no signature changed, and the only new refusals are support, program and SGM flag / scratch buffers that do not start on a 16-byte boundary (no allocator hands such a buffer out) */
 
 #define MCCNN_E_INVALID (-1)     /* bad argument (null pointer, non-positive size, unsupported shape) */
 #define MCCNN_E_UNSUPPORTED (-2) /* shape outside what the kernels were built for (e.g. D > 1024 for SGM) */
@@ -161,7 +188,8 @@ int mccnn_cost_volume_fill(float *lcv, float *rcv, int D, int H, int W, int pixe
  * falling region size (uint16 tile-local indices): the order in which the plane-major reference-order kernel deals
  * pixels to lanes, so that a wave's lanes walk regions of similar size.  The fourth, [H][W] uint32 "window masks", is
  * what the pixel-major reference-order kernel (mccnn_cbca_iter_hwd) walks: one bit per column of its register window
- * that the pixel's horizontal arm covers.  Allocate mccnn_support_bytes(H, W) bytes (22 per pixel + alignment);
+ * that the pixel's horizontal arm covers.  Allocate mccnn_support_bytes(H, W) bytes (22 per pixel + alignment) on a
+ * 16-byte boundary (memory contract: MCCNN_E_INVALID otherwise, here and in every entry point that takes the buffer);
  * mccnn_cross_arms fills all planes, and consumers that only want the arms / counts read the first H*W words. */
 typedef uint32_t mccnn_support_t; /* plane 0 layout [H][W] */
 size_t mccnn_support_bytes(int H, int W); /* whole buffer: all planes (0 for non-positive sizes) */
@@ -268,7 +296,8 @@ int mccnn_cbca_iter_hwd_long_pair(const float *in_left, float *out_left, const m
  * compiled once per image into a linear program per patch (mccnn_cbca_prog_build_pair, after mccnn_cross_arms), and the
  * iteration is an interpreter of those programs written in gfx950 assembly (csrc/asm/cbca_prog_gen.py).  The programs
  * depend on the image, on D (disparities per lane) and on nothing else: one build serves all 18 iterations of a pair.
- *   mccnn_cbca_prog_bytes: size of ONE image's program buffer (room for two program sets: the full programs and the
+ *   mccnn_cbca_prog_bytes: size of ONE image's program buffer, which must be 16-byte aligned (memory contract:
+ *     MCCNN_E_INVALID otherwise, in the builders and in every launch) (room for two program sets: the full programs and the
  *     ones mccnn_cbca_iter_prog_pair_skip runs); 0 when the shape is outside what the programs encode
  *     (W > 2180 columns, or volumes beyond a buffer descriptor's reach) - callers then stay with mccnn_cbca_iter_hwd_pair.
  *   support_*: the whole buffers mccnn_cross_arms wrote (plane 0 is read).  L <= 14; outputs must not alias inputs.
@@ -342,7 +371,9 @@ int mccnn_cbca_iter_prog_pair_refresh(float *in_left, float *out_left, const mcc
                                       const mccnn_support_t *support_right, const void *prog_right, int D, int H, int W,
                                       int L, mccnn_stream_t stream);
 
-/* ---- layout changes between DHW and HWD ------------------------------------------------------------------- */
+/* ---- layout changes between DHW and HWD -------------------------------------------------------------------
+ * Any 4-byte-aligned bases (the 16-byte transposes run only between two 16-byte-aligned ones, same bits).  mccnn_dhw_to_hwd
+ * leaves the pad entries of hwd unspecified; mccnn_hwd_to_dhw never copies one. */
 int mccnn_hwd_pitch(int D); /* Dp: D rounded up to a multiple of 4 (16-byte rows) */
 int mccnn_dhw_to_hwd(const float *dhw, float *hwd, int D, int H, int W, mccnn_stream_t stream);
 int mccnn_hwd_to_dhw(const float *hwd, float *dhw, int D, int H, int W, mccnn_stream_t stream);
@@ -355,6 +386,8 @@ int mccnn_hwd_to_dhw(const float *hwd, float *dhw, int D, int H, int W, mccnn_st
  * as p1 for the vertical directions, pf:204).  float32 add/min/sub only, un-fused: bit-exact vs the reference.
  * Up to two volumes (e.g. left + right) are advanced by one launch so the chip sees 2x the scanlines:
  * n_jobs in {1,2}; job j updates vol_hwd[j] as side[j].  scratch >= mccnn_sgm_scratch_bytes(H,W,D). 2<=D<=1024.
+ * scratch / flags of every SGM entry point: 16-byte aligned (memory contract: MCCNN_E_SCRATCH otherwise).  The pad entries
+ * of vol_hwd are read, masked to +inf, and overwritten with unspecified values; they never reach an entry d < D.
  * No limit on the volume's size: vertical scanlines of volumes of 4 GiB or more run a variant that rebases its buffer
  * descriptor every few steps (same bits). */
 size_t mccnn_sgm_scratch_bytes(int H, int W, int D);

@@ -321,6 +321,8 @@ static int prog_build(const char *who, int mode, const mccnn_support_t *support_
 {
     using namespace mccnn;
     MCCNN_REQUIRE(support_left && support_right && prog_left && prog_right, MCCNN_E_INVALID, "%s: null pointer", who);
+    MCCNN_REQUIRE(aligned16(prog_left) && aligned16(prog_right), MCCNN_E_INVALID,
+                  "%s: the program buffers must be 16-byte aligned", who);
     MCCNN_REQUIRE(L >= 1 && L <= 14, MCCNN_E_UNSUPPORTED, "%s: L=%d outside [1,14]", who, L);
     prog::Shape s;
     int rc = prog::shape_of(D, H, W, &s, who);
@@ -396,6 +398,8 @@ static int prog_iter(const char *who, const float *in_left, float *out_left, con
                   MCCNN_E_INVALID, "%s: null pointer", who);
     MCCNN_REQUIRE(single || out_right || (wta && !store_right), MCCNN_E_INVALID, "%s: out_right is null", who);
     MCCNN_REQUIRE(!wta || (disp_left && disp_right), MCCNN_E_INVALID, "%s: null disparity map", who);
+    MCCNN_REQUIRE(aligned16(prog_left) && aligned16(prog_right), MCCNN_E_INVALID,
+                  "%s: the program buffers must be 16-byte aligned", who);
     if (!out_right || single) out_right = out_left;     // never dereferenced: an empty descriptor / no second job
     MCCNN_REQUIRE(in_left != out_left && (single || (in_right != out_right && (out_left != out_right || !store_right) &&
                                                      in_left != out_right && in_right != out_left)),

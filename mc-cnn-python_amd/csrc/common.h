@@ -19,6 +19,11 @@ int check_launch(const char *what);
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// The buffers whose layout is private to the library - support planes, aggregation programs, SGM flag planes - must
+// start on a 16-byte boundary (include/mccnn.h, memory contract): their derived planes are laid out in 16-byte steps
+// from the base and read with scalar and packed loads.  Checked on the host in front of every launch.
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
 // Compute units of the CURRENT device, rounded down to whole groups of 8 (one CU of every XCD), never below 8;
 // looked up per device (a process may drive several) and remembered.
 int device_cus8();

@@ -917,6 +917,7 @@ unsigned long long mccnn::support_generation(const mccnn_support_t *support)
 
 int mccnn::check_support_record(const mccnn_support_t *support, int H, int W, int L, const char *who, bool must_be_known)
 {
+    MCCNN_REQUIRE(aligned16(support), MCCNN_E_INVALID, "%s: the support buffer must be 16-byte aligned", who);
     std::lock_guard<std::mutex> lock(g_support_mu);
     const auto it = g_support.find(support);
     if (it != g_support.end()) it->second.used = ++g_support_tick;
@@ -977,6 +978,7 @@ extern "C" int mccnn_cross_arms(const float *image, int H, int W, float tau, int
 {
     using namespace mccnn;
     MCCNN_REQUIRE(image && support, MCCNN_E_INVALID, "mccnn_cross_arms: null pointer");
+    MCCNN_REQUIRE(aligned16(support), MCCNN_E_INVALID, "mccnn_cross_arms: the support buffer must be 16-byte aligned");
     MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "mccnn_cross_arms: non-positive size");
     MCCNN_REQUIRE(L >= 1 && L <= 32, MCCNN_E_UNSUPPORTED,
                   "mccnn_cross_arms: L=%d outside [1,32] (5-bit arms, 12-bit region size)", L);
@@ -991,6 +993,8 @@ extern "C" int mccnn_cross_arms_pair(const float *image_left, const float *image
     MCCNN_REQUIRE(image_left && image_right && support_left && support_right, MCCNN_E_INVALID,
                   "mccnn_cross_arms_pair: null pointer");
     MCCNN_REQUIRE(support_left != support_right, MCCNN_E_INVALID, "mccnn_cross_arms_pair: the two buffers must differ");
+    MCCNN_REQUIRE(aligned16(support_left) && aligned16(support_right), MCCNN_E_INVALID,
+                  "mccnn_cross_arms_pair: the support buffers must be 16-byte aligned");
     MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "mccnn_cross_arms_pair: non-positive size");
     MCCNN_REQUIRE(L >= 1 && L <= 32, MCCNN_E_UNSUPPORTED,
                   "mccnn_cross_arms_pair: L=%d outside [1,32] (5-bit arms, 12-bit region size)", L);

@@ -721,6 +721,7 @@ static int sgm_validate(const char *who, bool pointers, int n_jobs, sgm_vols vol
                   "%s: r=(%d,%d) is not an axis-aligned unit step (pf:484)", who, rh, rw);
     MCCNN_REQUIRE(flags_bytes >= mccnn_sgm_scratch_bytes(H, W, D), MCCNN_E_SCRATCH, "%s: scratch %zu < %zu bytes", who,
                   flags_bytes, mccnn_sgm_scratch_bytes(H, W, D));
+    MCCNN_REQUIRE(aligned16(flags), MCCNN_E_SCRATCH, "%s: the flag / scratch buffer must be 16-byte aligned", who);
     for (int j = 0; side && j < n_jobs; ++j) {
         MCCNN_REQUIRE(vol_a[j] != nullptr && (!vol_b || vol_b[j] != nullptr), MCCNN_E_INVALID, "%s: null volume", who);
         MCCNN_REQUIRE(side[j] == MCCNN_SIDE_LEFT || side[j] == MCCNN_SIDE_RIGHT, MCCNN_E_INVALID,

@@ -64,6 +64,28 @@ def test_argument_validation_without_gpu(lib_path):
     assert lib.mccnn_sgm_scratch_bytes(500, 750, 256) >= 2 * 500 * (750 + 2 * 256)
 
 
+def test_misaligned_private_buffers_are_refused_without_gpu(lib_path):
+    """include/mccnn.h, memory contract: support, program and SGM flag / scratch buffers that do not start on a 16-byte
+    boundary are refused on the host, before any HIP call - so the refusal needs no device (the addresses below are
+    never dereferenced)."""
+    import _hipabi
+    lib = _hipabi.load()
+    p = ctypes.c_void_p
+    ok, odd = 0x10000, 0x10004
+    assert lib.mccnn_cross_arms(p(ok), 8, 8, 0.02, 14, p(odd), None) == _hipabi.MCCNN_E_INVALID
+    assert b"16-byte aligned" in lib.mccnn_last_error_string()
+    assert lib.mccnn_cross_arms_pair(p(ok), p(ok), 8, 8, 0.02, 14, p(ok), p(ok + 8), None) == _hipabi.MCCNN_E_INVALID
+    assert lib.mccnn_cbca_iter_hwd(p(ok), p(ok + 4096), p(odd), 6, 8, 8, 14, None) == _hipabi.MCCNN_E_INVALID
+    assert b"16-byte aligned" in lib.mccnn_last_error_string()
+    assert lib.mccnn_cbca_iter(p(ok), p(ok + 4096), p(ok + 12), 6, 8, 8, 14, 1, None) == _hipabi.MCCNN_E_INVALID
+    assert lib.mccnn_cbca_prog_build_pair(p(ok), p(ok), 6, 8, 8, 14, p(ok), p(odd), None) == _hipabi.MCCNN_E_INVALID
+    assert b"program buffers must be 16-byte aligned" in lib.mccnn_last_error_string()
+    assert lib.mccnn_cbca_iter_prog(p(ok), p(ok + 4096), p(ok), p(odd), 6, 8, 8, 14, None) == _hipabi.MCCNN_E_INVALID
+    need = lib.mccnn_sgm_scratch_bytes(8, 8, 6)
+    assert lib.mccnn_sgm_flags(p(ok), p(ok), 6, 8, 8, 0, 1, 0.08, p(odd), need, None) == _hipabi.MCCNN_E_SCRATCH
+    assert b"16-byte aligned" in lib.mccnn_last_error_string()
+
+
 def test_product_path_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():

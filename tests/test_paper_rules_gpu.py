@@ -87,11 +87,12 @@ def test_both_view_aggregation(case):
 
 
 def _unregistered_copy(support):
-    """The arms of a plane at an address mccnn_cross_arms has never written (one word into a fresh allocation: no
-    support buffer starts there)."""
+    """The arms of a plane at an address mccnn_cross_arms has never written (16 bytes into a fresh allocation: no
+    support buffer starts there, and the plane keeps the 16-byte alignment every support pointer must have)."""
     H, W = support.shape
-    room = torch.empty((H * W + 1,), dtype=torch.int32, device="cuda")
-    copy = room[1:].view(H, W)
+    room = torch.empty((H * W + 4,), dtype=torch.int32, device="cuda")
+    copy = room[4:].view(H, W)
+    assert copy.data_ptr() % 16 == 0 and copy.data_ptr() != room.data_ptr()
     copy.copy_(support)
     return copy
 
