@@ -126,6 +126,46 @@ int mccnn_cost_volume_hwd(const float *fl, const float *fr, int H, int W, int C,
 int mccnn_cost_volume_vertical_hwd(const float *fl, const float *fr, int H, int W, int C, int D, int vertical_range,
                                    float *lcv_hwd, float *rcv_hwd, mccnn_stream_t stream);
 
+/* ---- a pair's ROW OFFSET: measured on the device, and the cost volume taken along it (not in the reference) ----------
+ * A pair whose right image sits k0 rows low needs no search: it needs the volume taken against row h + k0.  P(k; d,h,w)
+ * and the maximum rule (ascending order, NaN sticky, the first of equal values kept) are those of
+ * mccnn_cost_volume_vertical_hwd above; so are the envelope and the refusals of the two calls that read features.
+ *
+ * mccnn_vertical_profile: the measurement, for the left view.  R = max_offset, 0 <= R <= 8; row_step >= 1.
+ *   profiled rows   h_i = row_step / 2 + i * row_step < H, i = 0 .. n_rows - 1; n_rows = mccnn_vertical_profile_rows(H,
+ *                   row_step) (0 where row_step / 2 >= H)
+ *   b(k)            for a profiled row h, a pixel w and every k in -R..R with 0 <= h + k < H: the maximum over
+ *                   d = 0 .. min(D - 1, w), d ascending, of P(k; d,h,w)
+ *   vote            a pixel votes unless one of its b(k) is NaN.  Its winner: best = b(0); then the candidates -1, +1, -2,
+ *                   +2, ... in this order, each replacing the best only when strictly greater - ties go to the smaller
+ *                   |k|, a flat image votes 0
+ *   votes           uint32 [n_rows][ceil(W / 64)][2R + 1]: votes[i][w / 64][winner + R] counts the pixels.  The call
+ *                   overwrites all of it (a memset node and one kernel); integer atomics only: deterministic
+ * MCCNN_E_INVALID: also max_offset outside [0, 8], row_step < 1.  MCCNN_E_SCRATCH: votes_bytes below the array's size.
+ *
+ * mccnn_vertical_offset_select: totals[k + R] (uint64 [2R + 1]) = the votes for k over all rows and blocks; *offset
+ * (int32) = the k of the largest total, candidates and replacement as for the vote; no votes at all give 0.  votes,
+ * offset and totals are device buffers; one small launch.
+ *
+ * mccnn_cost_volume_offset_hwd: the pixel-major volumes along the offset.  row_offset: a DEVICE int32, read by the
+ * kernel (so a measured offset needs no host round trip); k0 = min(max(*row_offset, -8), 8), whatever is stored; a null
+ * pointer means 0.  r = vertical_range, 0 <= r <= 4:
+ *   S_L(d,h,w) = max over k = k0-r .. k0+r with 0 <= h+k < H of P(k; d,h,w); where no such k exists,
+ *                P(kc; d,h,w) with kc = clamp(k0, -h, H-1-h): the nearest image row
+ *   S_R(d,h,w) = max over the same k with 0 <= h-k < H of P(k; d,h-k,w+d); where none exists, kc = clamp(k0, h-(H-1), h)
+ * then the border recurrences and the negation: the unchanged fill launch.  Pads are not written.  *row_offset = 0 (and
+ * a null pointer) give the bits of mccnn_cost_volume_vertical_hwd at the same range.  With a pointer the search kernel
+ * runs at every range: 2 (2r + 1) product sets.
+ * All three: no allocation, no synchronisation: capturable. */
+#define MCCNN_VERTICAL_OFFSET_MAX 8
+int mccnn_vertical_profile_rows(int H, int row_step);
+int mccnn_vertical_profile(const float *fl, const float *fr, int H, int W, int C, int D, int max_offset, int row_step,
+                           uint32_t *votes, size_t votes_bytes, mccnn_stream_t stream);
+int mccnn_vertical_offset_select(const uint32_t *votes, int n_rows, int n_blocks, int max_offset, int32_t *offset,
+                                 uint64_t *totals, mccnn_stream_t stream);
+int mccnn_cost_volume_offset_hwd(const float *fl, const float *fr, int H, int W, int C, int D, const int32_t *row_offset,
+                                 int vertical_range, float *lcv_hwd, float *rcv_hwd, mccnn_stream_t stream);
+
 /* ---- a2 for the "accurate" network (Zbontar & LeCun 2016, sec. 3.2): the decision MLP on the matrix cores -----------
  * s(h,w,d) = sigmoid(wf . relu(W_n ... relu(W_2 . relu(aL[h,w] + aR[h,w-d]) + b_2) ... + b_n) + bf) for w >= d;
  * lcv = -s at (h,w,d), rcv = -s at (h,w-d,d); the border columns are filled by the same recurrences, the same kernels,

@@ -468,10 +468,15 @@ __device__ __forceinline__ void cvv_take(float *best, float s, bool first)
     *best = (s > b || s != s) ? s : b;
 }
 
+// OFFSET (include/mccnn.h: mccnn_cost_volume_offset_hwd): the candidates lie around k0 = *row_offset clamped to +-8
+// instead of around 0 - only klo / khi differ; a row none of whose candidates lies inside the image takes the one
+// candidate nearest to k0 that does.  The search itself (OFFSET = false) is the kernel as it was.
+template <bool OFFSET>
 __global__ __launch_bounds__(256, 3) void cost_volume_vertical_kernel(const float *__restrict__ fl,
                                                                       const float *__restrict__ fr, int H, int W, int D,
                                                                       int vrange, float *__restrict__ lcv,
-                                                                      float *__restrict__ rcv, int Dp)
+                                                                      float *__restrict__ rcv, int Dp,
+                                                                      const int *__restrict__ row_offset)
 {
     constexpr int RING = 128;
     __shared__ __attribute__((aligned(16))) float sR[RING * CV_LD];
@@ -483,8 +488,15 @@ __global__ __launch_bounds__(256, 3) void cost_volume_vertical_kernel(const floa
     const int w0 = (int)blockIdx.x * CVP_TW - 1, h = blockIdx.y;   // lane 0: search column w0 (ghost)
     const int tid = threadIdx.x;
     // the candidates k = klo .. khi, ascending: the other view's row h + sgn * k lies inside the image (k = 0 always does)
-    const int klo = right ? max(-vrange, h - (H - 1)) : max(-vrange, -h);
-    const int khi = right ? min(vrange, h) : min(vrange, H - 1 - h);
+    int klo = right ? max(-vrange, h - (H - 1)) : max(-vrange, -h);
+    int khi = right ? min(vrange, h) : min(vrange, H - 1 - h);
+    if (OFFSET) {
+        const int k0 = min(max(*row_offset, -MCCNN_VERTICAL_OFFSET_MAX), MCCNN_VERTICAL_OFFSET_MAX);   // any stored value is safe
+        const int kmin = right ? h - (H - 1) : -h, kmax = right ? h : H - 1 - h;     // the k whose row is an image row
+        klo = max(k0 - vrange, kmin);
+        khi = min(k0 + vrange, kmax);
+        if (klo > khi) klo = khi = min(max(k0, kmin), kmax);
+    }
     // the 16 bytes at channels 4 c4 .. of search column c (clamped: kept as it comes, never part of a stored score)
     auto at = [&](const float *f, int row, int c, int c4) {
         return reinterpret_cast<const cv_f4 *>(f + ((size_t)row * W + (mir + sgn * min(max(c, 0), W - 1))) * CV_C + c4 * 4);
@@ -609,6 +621,185 @@ __global__ __launch_bounds__(256, 3) void cost_volume_vertical_kernel(const floa
             __syncthreads();                        // the ring holds the next candidate's rows, the score tile has been read
         }
     }
+}
+
+// ---- the row offset of a pair, measured (include/mccnn.h: mccnn_vertical_profile, mccnn_vertical_offset_select) --------
+// One workgroup per (63-pixel tile, profiled row) of the LEFT view: the tile, ring and product block of the search
+// above, and no volume.  Candidates outermost, in the order of the vote (0, -1, +1, ...): for one candidate a thread
+// keeps the maximum over its wave's 16 disparities of every disparity tile in a register; the four waves' maxima of a
+// pixel meet in the score tile's LDS (free once the own features are in registers) and wave 0 keeps (best value, best k,
+// NaN seen) per pixel.  The maximum's rule makes NaN sticky, so b(k) is NaN iff one of its scores is; which of several
+// equal scores is kept is invisible to the comparisons that follow.  The ring is re-staged per (candidate, disparity
+// tile) exactly as above.  The votes of a tile (it touches at most two 64-pixel blocks) are counted in LDS and leave as
+// at most 2 (2R + 1) integer atomics per workgroup: the result does not depend on any order.
+__device__ __forceinline__ int cvp_candidate(int c) { return c == 0 ? 0 : ((c & 1) ? -((c + 1) >> 1) : (c >> 1)); }
+
+__global__ __launch_bounds__(256, 3) void vertical_profile_kernel(const float *__restrict__ fl, const float *__restrict__ fr,
+                                                                  int H, int W, int D, int R, int row_step,
+                                                                  unsigned *__restrict__ votes, int n_blocks)
+{
+    constexpr int RING = 128, NK = 2 * MCCNN_VERTICAL_OFFSET_MAX + 1;
+    __shared__ __attribute__((aligned(16))) float sR[RING * CV_LD];
+    __shared__ __attribute__((aligned(16))) float sL[CV_TW * CV_LD];
+    __shared__ unsigned sH[2 * NK];
+    const int w0 = (int)blockIdx.x * CVP_TW - 1, h = row_step / 2 + (int)blockIdx.y * row_step;   // h < H: the grid's rows
+    const int tid = threadIdx.x;
+    const int nk = 2 * R + 1;
+    auto at = [&](const float *f, int row, int c, int c4) {
+        return reinterpret_cast<const cv_f4 *>(f + ((size_t)row * W + min(max(c, 0), W - 1)) * CV_C + c4 * 4);
+    };
+    // the candidate behind candidate c whose row lies inside the image; 2R + 1: none
+    auto next_candidate = [&](int c) {
+        for (++c; c < nk; ++c) {
+            const int row = h + cvp_candidate(c);
+            if (row >= 0 && row < H) break;
+        }
+        return c;
+    };
+    if (tid < 2 * NK) sH[tid] = 0u;
+    {
+        cv_f4 pl[4], pr[8];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int i = tid + q * 256;
+            pl[q] = *at(fl, h, w0 + (i >> 4), i & 15);
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {     // the first tile's columns w0 - 63 .. w0 + 64 of the first candidate's row (k = 0)
+            const int i = tid + q * 256;
+            pr[q] = *at(fr, h, w0 - (CV_DT - 1) + (i >> 4), i & 15);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int i = tid + q * 256;
+            *reinterpret_cast<cv_f4 *>(&sL[(i >> 4) * CV_LD + (i & 15) * 4]) = pl[q];
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int i = tid + q * 256, x = w0 - (CV_DT - 1) + (i >> 4);
+            *reinterpret_cast<cv_f4 *>(&sR[(x & (RING - 1)) * CV_LD + (i & 15) * 4]) = pr[q];
+        }
+    }
+    __syncthreads();
+
+    const int wl = tid & 63, dq = tid >> 6;  // dq is wave-uniform: each wave owns 16 disparities = 8 pairs of a tile
+    const int w = w0 + wl;
+    const bool pixel = wl >= 1 && w < W;     // lane 0 is the ghost
+    float a[CV_C];
+#pragma unroll
+    for (int c4 = 0; c4 < 16; ++c4) {
+        const float4 v = *reinterpret_cast<const float4 *>(&sL[wl * CV_LD + c4 * 4]);
+        a[c4 * 4 + 0] = v.x; a[c4 * 4 + 1] = v.y; a[c4 * 4 + 2] = v.z; a[c4 * 4 + 3] = v.w;
+    }
+    float *const sM = sL;               // [4][64]: the four waves' maxima of the current candidate
+    __syncthreads();
+    float best = 0.f;
+    int bestk = 0;
+    bool nan_seen = false;
+#pragma unroll 1
+    for (int c = 0; c < nk;) {
+        const int k = cvp_candidate(c), nc = next_candidate(c);
+        float m = -__builtin_inff();         // below every score; d = 0 exists for every pixel
+#pragma unroll 1
+        for (int d0 = 0; d0 < D && w0 + CV_TW - 1 >= d0; d0 += CV_DT) {
+            const bool lastd = !(d0 + CV_DT < D && w0 + CV_TW - 1 >= d0 + CV_DT);
+            // the rows of the next (candidate, tile) on their way; behind the last one they are fetched for nothing
+            const int nd0 = lastd ? 0 : d0 + CV_DT, nrow = h + (lastd ? (nc < nk ? cvp_candidate(nc) : 0) : k);
+            cv_f4 nx[4], ny[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int i = tid + q * 256;
+                nx[q] = *at(fr, nrow, w0 - nd0 - (CV_DT - 1) + (i >> 4), i & 15);
+            }
+#pragma unroll 1
+            for (int kk = 0; kk < 8; ++kk) {
+                const int dloc = dq * 16 + 2 * kk;
+                const int r = (w - d0 - dloc) & (RING - 1);
+                float s, sn;
+                cvv_pair_scores(a, &sR[r * CV_LD], s, sn);
+                const int d = d0 + dloc;
+                if (pixel && d < D && w >= d) m = (s > m || s != s) ? s : m;
+                if (pixel && d + 1 < D && w >= d + 1) m = (sn > m || sn != sn) ? sn : m;
+            }
+            __syncthreads();                         // this tile's products are done: the ring is free
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int i = tid + (q + 4) * 256;
+                ny[q] = *at(fr, nrow, w0 - nd0 - (CV_DT - 1) + (i >> 4), i & 15);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int i = tid + q * 256, x = w0 - nd0 - (CV_DT - 1) + (i >> 4);
+                *reinterpret_cast<cv_f4 *>(&sR[(x & (RING - 1)) * CV_LD + (i & 15) * 4]) = nx[q];
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int i = tid + (q + 4) * 256, x = w0 - nd0 - (CV_DT - 1) + (i >> 4);
+                *reinterpret_cast<cv_f4 *>(&sR[(x & (RING - 1)) * CV_LD + (i & 15) * 4]) = ny[q];
+            }
+            __syncthreads();                        // the ring holds the next tile's rows
+        }
+        sM[dq * 64 + wl] = m;       // (last read two barriers ago: every candidate runs at least the tile d0 = 0)
+        __syncthreads();
+        if (dq == 0) {
+            float b = sM[wl];       // waves in ascending order: d ascending
+#pragma unroll
+            for (int q = 1; q < 4; ++q) {
+                const float s = sM[q * 64 + wl];
+                b = (s > b || s != s) ? s : b;
+            }
+            nan_seen = nan_seen || b != b;
+            if (c == 0 || b > best) {
+                best = b;
+                bestk = k;
+            }
+        }
+        c = nc;
+    }
+    if (dq == 0 && pixel && !nan_seen) atomicAdd(&sH[((w >> 6) - ((w0 + 1) >> 6)) * NK + bestk + R], 1u);
+    __syncthreads();
+    if (tid < 2 * NK) {
+        const int blk = ((w0 + 1) >> 6) + tid / NK, kk = tid % NK;
+        const unsigned n = sH[tid];
+        if (n != 0u && blk < n_blocks && kk < nk) atomicAdd(&votes[((size_t)blockIdx.y * n_blocks + blk) * nk + kk], n);
+    }
+}
+
+// totals[k + R] = the votes for k over all rows and blocks; *offset = the k of the largest total (candidates 0, -1, +1,
+// ..., replaced only by a strictly greater total: no votes at all give 0).  One workgroup; integer sums only.
+__global__ __launch_bounds__(256) void vertical_offset_select_kernel(const unsigned *__restrict__ votes, int n_cells, int R,
+                                                                     int *__restrict__ offset,
+                                                                     unsigned long long *__restrict__ totals)
+{
+    constexpr int NK = 2 * MCCNN_VERTICAL_OFFSET_MAX + 1;
+    __shared__ unsigned long long sT[NK];
+    const int nk = 2 * R + 1;
+    if (threadIdx.x < NK) sT[threadIdx.x] = 0ull;
+    __syncthreads();
+    unsigned long long acc[NK];
+#pragma unroll
+    for (int j = 0; j < NK; ++j) acc[j] = 0ull;
+    for (int cell = threadIdx.x; cell < n_cells; cell += 256)
+#pragma unroll
+        for (int j = 0; j < NK; ++j)
+            if (j < nk) acc[j] += votes[(size_t)cell * nk + j];
+#pragma unroll
+    for (int j = 0; j < NK; ++j)
+        if (j < nk && acc[j] != 0ull) atomicAdd(&sT[j], acc[j]);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long best = sT[R];
+        int k0 = 0;
+        for (int c = 1; c < nk; ++c) {
+            const int k = cvp_candidate(c);
+            if (sT[k + R] > best) {
+                best = sT[k + R];
+                k0 = k;
+            }
+        }
+        *offset = k0;
+    }
+    if ((int)threadIdx.x < nk) totals[threadIdx.x] = sT[threadIdx.x];
 }
 
 // ---- MFMA variant ---------------------------------------------------------------------------------------------
@@ -1152,11 +1343,91 @@ extern "C" int mccnn_cost_volume_vertical_hwd(const float *fl, const float *fr, 
     if (vertical_range == 0)      // one candidate: both volumes out of the same products (pf:104), the pairs kernel as it is
         hipLaunchKernelGGL(cost_volume_exact_pairs_kernel, grid, dim3(256), 0, s, fl, fr, H, W, D, lcv_hwd, rcv_hwd, Dp);
     else
-        hipLaunchKernelGGL(cost_volume_vertical_kernel, dim3(grid.x, grid.y, 2), dim3(256), 0, s, fl, fr, H, W, D,
-                           vertical_range, lcv_hwd, rcv_hwd, Dp);
+        hipLaunchKernelGGL(cost_volume_vertical_kernel<false>, dim3(grid.x, grid.y, 2), dim3(256), 0, s, fl, fr, H, W, D,
+                           vertical_range, lcv_hwd, rcv_hwd, Dp, (const int *)nullptr);
     int rc = check_launch("mccnn_cost_volume_vertical_hwd");
     if (rc) return rc;
     return launch_cost_volume_fill_hwd(lcv_hwd, rcv_hwd, D, Dp, H, W, s, "mccnn_cost_volume_vertical_hwd(fill)");
+}
+
+extern "C" int mccnn_cost_volume_offset_hwd(const float *fl, const float *fr, int H, int W, int C, int D,
+                                            const int32_t *row_offset, int vertical_range, float *lcv_hwd, float *rcv_hwd,
+                                            mccnn_stream_t stream)
+{
+    using namespace mccnn;
+    if (!row_offset)              // offset 0: the search as it is, the same launches
+        return mccnn_cost_volume_vertical_hwd(fl, fr, H, W, C, D, vertical_range, lcv_hwd, rcv_hwd, stream);
+    MCCNN_REQUIRE(fl && fr && lcv_hwd && rcv_hwd, MCCNN_E_INVALID, "mccnn_cost_volume_offset_hwd: null pointer");
+    MCCNN_REQUIRE(vertical_range >= 0 && vertical_range <= MCCNN_VERTICAL_RANGE_MAX, MCCNN_E_INVALID,
+                  "mccnn_cost_volume_offset_hwd: vertical_range=%d outside [0, %d]", vertical_range, MCCNN_VERTICAL_RANGE_MAX);
+    MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "mccnn_cost_volume_offset_hwd: non-positive size");
+    MCCNN_REQUIRE(C == CV_C, MCCNN_E_UNSUPPORTED, "mccnn_cost_volume_offset_hwd: C=%d, kernels are built for 64 channels", C);
+    MCCNN_REQUIRE(D >= 2 && D <= 1024, MCCNN_E_UNSUPPORTED, "mccnn_cost_volume_offset_hwd: D=%d outside [2, 1024]", D);
+    MCCNN_REQUIRE(D <= W - 2, MCCNN_E_UNSUPPORTED,
+                  "mccnn_cost_volume_offset_hwd: D=%d needs W >= D+2 (the reference's border recurrence pf:106 is "
+                  "degenerate beyond that), W=%d", D, W);
+    MCCNN_REQUIRE(H <= 65535, MCCNN_E_UNSUPPORTED, "mccnn_cost_volume_offset_hwd: H=%d > 65535 rows exceed the grid", H);
+    const int Dp = mccnn_hwd_pitch(D);
+    MCCNN_REQUIRE((size_t)W * Dp * 4 < ((size_t)1 << 31), MCCNN_E_UNSUPPORTED,
+                  "mccnn_cost_volume_offset_hwd: a %d x %d row exceeds a buffer descriptor's reach", W, D);
+    hipStream_t s = (hipStream_t)stream;
+    // (range 0: one candidate per view, two product sets - the offset is known on the device only, so the pairs kernel,
+    // whose two volumes share their products, cannot serve it)
+    hipLaunchKernelGGL(cost_volume_vertical_kernel<true>, dim3(cdiv(W, CVP_TW), H, 2), dim3(256), 0, s, fl, fr, H, W, D,
+                       vertical_range, lcv_hwd, rcv_hwd, Dp, (const int *)row_offset);
+    int rc = check_launch("mccnn_cost_volume_offset_hwd");
+    if (rc) return rc;
+    return launch_cost_volume_fill_hwd(lcv_hwd, rcv_hwd, D, Dp, H, W, s, "mccnn_cost_volume_offset_hwd(fill)");
+}
+
+extern "C" int mccnn_vertical_profile_rows(int H, int row_step)
+{
+    if (H <= 0 || row_step < 1 || row_step / 2 >= H) return 0;
+    return (H - 1 - row_step / 2) / row_step + 1;
+}
+
+extern "C" int mccnn_vertical_profile(const float *fl, const float *fr, int H, int W, int C, int D, int max_offset,
+                                      int row_step, uint32_t *votes, size_t votes_bytes, mccnn_stream_t stream)
+{
+    using namespace mccnn;
+    MCCNN_REQUIRE(fl && fr, MCCNN_E_INVALID, "mccnn_vertical_profile: null pointer");
+    MCCNN_REQUIRE(max_offset >= 0 && max_offset <= MCCNN_VERTICAL_OFFSET_MAX, MCCNN_E_INVALID,
+                  "mccnn_vertical_profile: max_offset=%d outside [0, %d]", max_offset, MCCNN_VERTICAL_OFFSET_MAX);
+    MCCNN_REQUIRE(row_step >= 1, MCCNN_E_INVALID, "mccnn_vertical_profile: row_step=%d < 1", row_step);
+    MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "mccnn_vertical_profile: non-positive size");
+    MCCNN_REQUIRE(C == CV_C, MCCNN_E_UNSUPPORTED, "mccnn_vertical_profile: C=%d, kernels are built for 64 channels", C);
+    MCCNN_REQUIRE(D >= 2 && D <= 1024, MCCNN_E_UNSUPPORTED, "mccnn_vertical_profile: D=%d outside [2, 1024]", D);
+    MCCNN_REQUIRE(D <= W - 2, MCCNN_E_UNSUPPORTED, "mccnn_vertical_profile: D=%d needs W >= D+2, W=%d", D, W);
+    MCCNN_REQUIRE(H <= 65535, MCCNN_E_UNSUPPORTED, "mccnn_vertical_profile: H=%d > 65535 rows exceed the grid", H);
+    MCCNN_REQUIRE((size_t)W * mccnn_hwd_pitch(D) * 4 < ((size_t)1 << 31), MCCNN_E_UNSUPPORTED,
+                  "mccnn_vertical_profile: a %d x %d row exceeds a buffer descriptor's reach", W, D);
+    const int n_rows = mccnn_vertical_profile_rows(H, row_step), n_blocks = cdiv(W, 64);
+    const size_t need = (size_t)n_rows * n_blocks * (2 * max_offset + 1) * sizeof(uint32_t);
+    MCCNN_REQUIRE(votes_bytes >= need, MCCNN_E_SCRATCH, "mccnn_vertical_profile: the votes need %zu bytes, %zu given", need,
+                  votes_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    if (n_rows == 0) return 0;                       // row_step / 2 >= H: no profiled row, no vote, an empty array
+    MCCNN_REQUIRE(votes, MCCNN_E_INVALID, "mccnn_vertical_profile: null pointer");
+    MCCNN_REQUIRE(hipMemsetAsync(votes, 0, need, s) == hipSuccess, MCCNN_E_INVALID, "mccnn_vertical_profile: memset failed");
+    hipLaunchKernelGGL(vertical_profile_kernel, dim3(cdiv(W, CVP_TW), n_rows, 1), dim3(256), 0, s, fl, fr, H, W, D, max_offset,
+                       row_step, votes, n_blocks);
+    return check_launch("mccnn_vertical_profile");
+}
+
+extern "C" int mccnn_vertical_offset_select(const uint32_t *votes, int n_rows, int n_blocks, int max_offset, int32_t *offset,
+                                            uint64_t *totals, mccnn_stream_t stream)
+{
+    using namespace mccnn;
+    MCCNN_REQUIRE(offset && totals, MCCNN_E_INVALID, "mccnn_vertical_offset_select: null pointer");
+    MCCNN_REQUIRE(max_offset >= 0 && max_offset <= MCCNN_VERTICAL_OFFSET_MAX, MCCNN_E_INVALID,
+                  "mccnn_vertical_offset_select: max_offset=%d outside [0, %d]", max_offset, MCCNN_VERTICAL_OFFSET_MAX);
+    MCCNN_REQUIRE(n_rows >= 0 && n_blocks >= 0 && (long)n_rows * n_blocks <= 0x7fffffffL, MCCNN_E_INVALID,
+                  "mccnn_vertical_offset_select: %d rows x %d blocks", n_rows, n_blocks);
+    // (an empty array - no profiled row - has no address: nothing is read, the offset is 0)
+    MCCNN_REQUIRE(votes || (long)n_rows * n_blocks == 0, MCCNN_E_INVALID, "mccnn_vertical_offset_select: null pointer");
+    hipLaunchKernelGGL(vertical_offset_select_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, votes, n_rows * n_blocks,
+                       max_offset, offset, reinterpret_cast<unsigned long long *>(totals));
+    return check_launch("mccnn_vertical_offset_select");
 }
 
 extern "C" int mccnn_cost_volume_fill(float *lcv, float *rcv, int D, int H, int W, int pixel_major, mccnn_stream_t stream)

@@ -112,6 +112,10 @@ class Middlebury(object):
         1, --views both: disp1MCCNN_s.pfm)."""
         return os.path.join(paths["res_dir"], "disp%dMCCNN_s.pfm" % int(view))
 
+    def vertical_path(self, paths):
+        """match.py --vertical_offset auto: the pair's measured row offset beside disp0MCCNN.pfm."""
+        return os.path.join(paths["res_dir"], "verticalMCCNN.json")
+
     def evaluator(self, thresholds, slots=1, interpolate=False, device=None, quantiles=None):
         import evaluation
         return evaluation.Evaluator(device, thresholds, slots, quantiles=quantiles)
@@ -205,6 +209,12 @@ class Kitti(object):
         root = os.path.dirname(os.path.dirname(paths["out_time"]))
         stem = os.path.splitext(os.path.basename(paths["out"]))[0]
         return os.path.join(root, "conf_%s" % measure, stem + ".pfm")
+
+    def vertical_path(self, paths):
+        """match.py --vertical_offset auto: submit_<tag>/vertical/NNNNNN_10.json."""
+        root = os.path.dirname(os.path.dirname(paths["out_time"]))
+        stem = os.path.splitext(os.path.basename(paths["out"]))[0]
+        return os.path.join(root, "vertical", stem + ".json")
 
     def evaluator(self, thresholds, slots=1, interpolate=False, device=None, quantiles=None):
         import evaluation

@@ -98,6 +98,7 @@ class ListPipeline(object):
                 t1 = time.time()
                 result = self.backend.wait(ticket)
                 t2 = time.time()
+                job.vertical = getattr(ticket, "vertical", None)     # (a repeated pair's ticket brings its own)
                 self.write(job, result, t2 - t0)
                 self.seconds["writer_wait_gpu"] += t2 - t1
                 self.seconds["writer_files"] += time.time() - t2
@@ -256,18 +257,22 @@ def _save_middlebury(result, p):
     util.writePfm(result.map, p["out"])
 
 
-def make_writer(rank=0, log=print, scorer=None, eval_file="evalMCCNN.json", save=_save_middlebury):
+def make_writer(rank=0, log=print, scorer=None, eval_file="evalMCCNN.json", save=_save_middlebury, save_vertical=None):
     """write(job, result, seconds) for ListPipeline: the files of match.py, with the existing util functions; with a
     `scorer` (evaluation.ListScorer, match.py --evaluate) also the evaluation of a pair that was scored (job.scored: of
     the map these files hold, or of the repeat that replaces it), once its bytes are on the host.  `save(result, paths)`
     writes what the PairResult of host arrays holds: the map and its preview (datasets.py: a KITTI layout's is the 16-bit
     plane), the planes (--confidence) and the sparse map (--semi_dense) - a repeated pair's files get the repeated
-    pair's."""
+    pair's.  `save_vertical(offset, totals, paths)` (match.py --vertical_offset auto) writes the measured row offset of a
+    pair whose ticket brought one."""
     from datetime import datetime
 
     def write(job, result, seconds):
         p = job.paths
         save(result, p)
+        vertical = getattr(job, "vertical", None)
+        if save_vertical is not None and vertical is not None:
+            save_vertical(vertical[0].numpy(), vertical[1].numpy(), p)
         util.saveTimeFile(seconds, p["out_time"])
         log("[{}] {}: {:.3f} s -> {}".format(rank, datetime.now(), seconds, p["out"]))
         if scorer is not None and job.scored is not None:
@@ -301,7 +306,8 @@ def slot_comes_round(redo, rematch, scorer, scored, result, slot, slot_stream, s
 # A pair enqueued by MatcherBackend.  host: the PairResult of pinned host tensors its results are copied to; done: the
 # event behind the copies; device: the PairResult on the device, its map what an evaluation scores (a KITTI layout: what
 # the written PNG holds, not the matcher's map).
-Ticket = collections.namedtuple("Ticket", "host done device")
+# vertical: the pinned host tensors (offset, totals) of a matcher that measures the row offset, else None.
+Ticket = collections.namedtuple("Ticket", "host done device vertical", defaults=(None,))
 
 
 class MatcherBackend(object):
@@ -315,7 +321,8 @@ class MatcherBackend(object):
     slot's stream and like the evaluation not inside the graph (a KITTI layout: the 16-bit code, half the bytes, and what
     the file holds); None: the map itself."""
 
-    def __init__(self, matchers, streams, make_library_matcher, rank=0, log=print, scorer=None, device_output=None):
+    def __init__(self, matchers, streams, make_library_matcher, rank=0, log=print, scorer=None, device_output=None,
+                 vertical=False):
         import torch
         import stereo_device
         self.torch = torch
@@ -324,6 +331,7 @@ class MatcherBackend(object):
         self.device = torch.cuda.current_device()
         self.rank, self.log = rank, log
         self.scorer, self.device_output = scorer, device_output
+        self.vertical = bool(vertical)       # the matchers measure the row offset: it crosses with the map
 
     def thread_init(self):
         self.torch.cuda.set_device(self.device)      # the current device is a per-thread setting
@@ -333,8 +341,9 @@ class MatcherBackend(object):
         s = self.streams[slot]
         return self.torch.cuda.stream(s) if s is not None else contextlib.nullcontext()
 
-    def _to_host(self, result):
-        """The PairResult a matcher returned on its way to pinned host memory: map, planes, sparse map, then the event."""
+    def _to_host(self, result, matcher=None, job=None):
+        """The PairResult a matcher returned on its way to pinned host memory: map, planes, sparse map, the measured row
+        offset of `job` on `matcher` where there is one, then the event."""
         torch = self.torch
         crossing = scored = result.map
         if self.device_output is not None:
@@ -344,9 +353,12 @@ class MatcherBackend(object):
             host = torch.empty(tuple(t.shape), dtype=t.dtype, pin_memory=True)
             return host.copy_(t, non_blocking=True)
         host = result._replace(map=crossing).apply(pinned_copy)
+        vertical = None
+        if self.vertical and matcher is not None:
+            vertical = tuple(pinned_copy(b) for b in matcher.vertical_buffers(job.height, job.width, job.ndisp))
         done = torch.cuda.Event()
         done.record()
-        return Ticket(host, done, result._replace(map=scored))
+        return Ticket(host, done, result._replace(map=scored), vertical)
 
     def _truth(self, gt, mask, dev):
         """The reader's pinned ground truth on its way to the device, behind the pair on the slot's stream."""
@@ -360,7 +372,7 @@ class MatcherBackend(object):
         m = self.matchers[slot]
         with self._stream(slot):
             match = m.match_u8 if mode == "eager" else m.match_graph_u8
-            ticket = self._to_host(m.result_of(match(job.left, job.right, job.ndisp)))
+            ticket = self._to_host(m.result_of(match(job.left, job.right, job.ndisp)), m, job)
             if self.scorer is not None:
                 # (the right view's truth crosses only where the pair is scored at all, and in front of the left's)
                 truth_right = self._truth(job.gt_right, job.mask_right, m.device) if job.gt is not None else None
@@ -379,7 +391,7 @@ class MatcherBackend(object):
         def rematch():
             library = self.redo.matcher()
             self.log("[{}] ".format(self.rank) + self.redo.notice(job.paths["out"]))
-            again = self._to_host(library.result_of(library.match_u8(job.left, job.right, job.ndisp)))
+            again = self._to_host(library.result_of(library.match_u8(job.left, job.right, job.ndisp)), library, job)
             return again, again.device
         again = slot_comes_round(self.redo, rematch, self.scorer, job.scored if self.scorer is not None else None,
                                  ticket.device, slot, lambda: self._stream(slot), self.torch.cuda.synchronize)

@@ -22,12 +22,15 @@ conf1MCCNN_<measure>.pfm with --confidence), in all three loops; with --evaluate
 mask1nocc.png) and every evaluation file gains a "right" block.  Middlebury layout only.
 --evaluate --eval_quantiles 50,90,95,99 adds the error quantiles (Middlebury's A50 ... A99) of every scored map, selected
 exactly on the device, and the list's pooled quantiles at 16 bits, in all three loops.  Middlebury layout only.
+--vertical_offset auto|N matches a pair whose right image sits N rows low along that offset; auto measures N per pair on
+the device and writes verticalMCCNN.json beside disp0MCCNN.pfm, the same bytes in all three loops.
 Multi-GPU: launch one process per GPU with different -g / -s / -e, as the reference intends (match.py:17, 26-28),
 or use `torchrun --nproc-per-node N match.py ...`: rank r then takes the pairs i = r (mod N) of the window.
 """
 import argparse
 import collections
 import contextlib
+import json
 import os
 import time
 from datetime import datetime
@@ -132,6 +135,17 @@ parser.add_argument("--vertical_range", type=int, default=0,
                          "unchanged.  0 (default): the reference's row-to-row comparison.  Costs a point or two on "
                          "well-rectified pairs and 4 x range + 2 times the cost volume's products; bit-exact fast "
                          "network only: not with --fast, --separable_cbca, --paper_support_regions or --arch accurate")
+parser.add_argument("--vertical_offset", type=str, default="0", metavar="auto|N",
+                    help="for pairs whose right image sits N rows low (N in -8 .. 8): the cost volume is taken against row "
+                         "h + N of the other view (include/mccnn.h: mccnn_cost_volume_offset_hwd), --vertical_range "
+                         "searched around it.  'auto': N is measured per pair on the device from the pair's features "
+                         "(mccnn_vertical_profile) and written to verticalMCCNN.json beside the map (a KITTI --dataset: "
+                         "submit_<tag>/vertical/NNNNNN_10.json).  0 (default): nothing changes.  Available where "
+                         "--vertical_range is")
+parser.add_argument("--vertical_offset_max", type=int, default=4,
+                    help="--vertical_offset auto: the largest offset that is measured, in rows either way (1 .. 8)")
+parser.add_argument("--vertical_offset_rows", type=int, default=8,
+                    help="--vertical_offset auto: every this many rows one row takes part in the measurement (>= 1)")
 parser.add_argument("--numpy1_promotion", action="store_true",
                     help="evaluate the sub-pixel formula as NumPy < 2 promotes its scalars (float64, rounded once), "
                          "i.e. as the reference's own Python 2.7 environment does; differs by <= 2.5e-5 px")
@@ -222,6 +236,17 @@ out_time_file = datasets.Middlebury.out_time_file
 out_eval_file = datasets.Middlebury.out_eval_file
 
 
+def parse_vertical_offset(text):
+    """--vertical_offset: "auto", or an integer in [-8, 8]; None for anything else."""
+    if text == "auto":
+        return "auto"
+    try:
+        value = int(text)
+    except ValueError:
+        return None
+    return value if -8 <= value <= 8 else None
+
+
 def hyper_parameters(args):
     return dict(cbca_intensity=args.cbca_intensity, cbca_distance=int(args.cbca_distance),
                 cbca_num_iterations1=int(args.cbca_num_iterations1),
@@ -241,13 +266,14 @@ class ListLoop(object):
     and, with --pairs_in_flight N > 1, one stream per slot) and writes its files when the slot comes round again.
 
     layout: datasets.py; redo: stereo_device.SaturationRedo; scorer: evaluation.ListScorer or None (--evaluate);
-    save(PairResult of host arrays, paths): the files of what crossed to the host."""
+    save(PairResult of host arrays, paths): the files of what crossed to the host; save_vertical(offset, totals, paths)
+    (--vertical_offset auto): the file of the pair's measured row offset, copied out behind the pair on its stream."""
 
-    def __init__(self, layout, matchers, streams, redo, scorer, save, rank):
+    def __init__(self, layout, matchers, streams, redo, scorer, save, rank, save_vertical=None):
         import torch
         self.torch = torch
         self.layout, self.matchers, self.streams, self.redo, self.scorer = layout, matchers, streams, redo, scorer
-        self.save, self.rank = save, rank
+        self.save, self.rank, self.save_vertical = save, rank, save_vertical
         self.pending = []            # oldest first
 
     def _stream(self, slot):
@@ -261,11 +287,15 @@ class ListLoop(object):
                 self.torch.from_numpy(truth[1]).cuda() if truth[1] is not None else None)
 
     def _matched(self, matcher, images, scoring):
-        """One pair on `matcher`: (what crosses to the host for its map, its PairResult with the map that is scored) - the
-        map, or a KITTI layout's 16-bit code and what it holds, behind the map on the current stream."""
+        """One pair on `matcher`: ((what crosses to the host for its map, copies of its measured row offset and totals or
+        None), its PairResult with the map that is scored) - the map, or a KITTI layout's 16-bit code and what it holds,
+        behind the map on the current stream."""
         result = matcher.result_of(matcher.match(*images))
         crossing, kept = self.layout.device_output(result.map, scoring)
-        return crossing, result._replace(map=kept)
+        vertical = None
+        if self.save_vertical is not None:       # (the slot's next pair overwrites the workspace's)
+            vertical = tuple(b.clone() for b in matcher.vertical_buffers(images[0].shape[0], images[0].shape[1], images[2]))
+        return (crossing, vertical), result._replace(map=kept)
 
     def launch(self, slot, index, paths, left_image, right_image, ndisp, truth, truth_right):
         """The timed region (match.py:129-179): host arrays in, host array out, device-synchronised - from here to
@@ -297,9 +327,14 @@ class ListLoop(object):
                                                          lambda: self._stream(p.slot),
                                                          self.torch.cuda.synchronize) or (p.crossing, p.result)
         # (the float32 map, or a KITTI layout's 16-bit plane)
+        crossing, vertical = crossing
         host = result._replace(map=crossing).apply(lambda t: t.cpu().numpy())
+        if vertical is not None:
+            vertical = tuple(t.cpu().numpy() for t in vertical)
         seconds = time.time() - p.started
         self.save(host, p.paths)
+        if vertical is not None:
+            self.save_vertical(vertical[0], vertical[1], p.paths)
         util.saveTimeFile(seconds, p.paths["out_time"])
         print("[{}] {}: {:.3f} s -> {}".format(self.rank, datetime.now(), seconds, p.paths["out"]))
         if p.scored is not None:
@@ -367,6 +402,22 @@ def main(argv=None):
                               ("--arch accurate", args.arch == "accurate", "the decision network has no vertical search")):
             if on:
                 parser.error("--vertical_range is not available with %s: %s" % (flag, why))
+    vertical_offset = parse_vertical_offset(args.vertical_offset)
+    if vertical_offset is None:
+        parser.error("--vertical_offset: %r is neither 'auto' nor an integer in [-8, 8]" % args.vertical_offset)
+    if not 1 <= args.vertical_offset_max <= 8:
+        parser.error("--vertical_offset_max: %d outside [1, 8]" % args.vertical_offset_max)
+    if args.vertical_offset_rows < 1:
+        parser.error("--vertical_offset_rows: %d < 1" % args.vertical_offset_rows)
+    if vertical_offset != 0:
+        for flag, on, why in (("--fast", args.fast, "the matrix-core cost volume has no row offset"),
+                              ("--separable_cbca", args.separable_cbca, "the offset cost volume writes pixel-major volumes, "
+                               "the separable aggregation starts plane-major"),
+                              ("--paper_support_regions", args.paper_support_regions, "the offset cost volume writes "
+                               "pixel-major volumes, the two-view support regions start plane-major"),
+                              ("--arch accurate", args.arch == "accurate", "the decision network has no row offset")):
+            if on:
+                parser.error("--vertical_offset is not available with %s: %s" % (flag, why))
     layout = datasets.get(args.dataset)
     try:
         eval_thresholds = layout.parse_thresholds(args.eval_thresholds if args.eval_thresholds is not None
@@ -456,6 +507,20 @@ def main(argv=None):
     net.restore(args.resume)  # loaded once and kept resident (the reference re-restores per pair)
     in_flight = max(1, int(args.pairs_in_flight))
 
+    # --vertical_offset: the extras and the workspace keywords of the same names; nothing without the flag
+    vertical_kw = dict(vertical_offset=vertical_offset, vertical_offset_max=args.vertical_offset_max,
+                       vertical_offset_rows=args.vertical_offset_rows) if vertical_offset != 0 else {}
+
+    def save_vertical(offset, totals, out):
+        """--vertical_offset auto: the pair's measurement (host arrays) as verticalMCCNN.json."""
+        record = dict(sd.vertical_record(offset, totals), max_offset=args.vertical_offset_max,
+                      row_step=args.vertical_offset_rows)
+        path = layout.vertical_path(out)
+        util.recurMk(os.path.abspath(os.path.dirname(path)))
+        with open(path, "w") as f:
+            json.dump(record, f, sort_keys=True)
+            f.write("\n")
+
     def make_matcher(features, decision=args.decision):
         return sd.StereoMatcher(
             net, hyper_parameters(args),
@@ -466,7 +531,7 @@ def main(argv=None):
             extras=dict(both_view_support=args.paper_support_regions,
                         interpolation_directions=16 if args.paper_interpolation else 4,
                         occlusion_from_left=args.paper_interpolation, numpy1_promotion=args.numpy1_promotion,
-                        sgm_independent_directions=args.paper_sgm, vertical_range=args.vertical_range),
+                        sgm_independent_directions=args.paper_sgm, vertical_range=args.vertical_range, **vertical_kw),
             confidence=conf_names, views=args.views, semi_dense=semi_rule)
 
     def save(result, out):
@@ -495,7 +560,7 @@ def main(argv=None):
     matchers = [make_matcher("miopen" if args.features == "library" else "auto") for _ in range(in_flight)]
     footprint_kw = dict(pairs_in_flight=in_flight, arch=args.arch,
                         fc_units=net.num_fc_units if accurate else sd.DECISION_UNITS, confidence=len(conf_names),
-                        views=args.views, **(dict(semi_dense=True) if semi_rule is not None else {}))
+                        views=args.views, **(dict(semi_dense=True) if semi_rule is not None else {}), **vertical_kw)
 
     def footprint(height, width, ndisp):        # refuses a shape outside the envelope, with its message
         return sd.workspace_bytes(height, width, ndisp, matchers[0].pixel_major(),
@@ -524,20 +589,23 @@ def main(argv=None):
     pipeline = None
     if args.pipeline:
         backend = list_matcher.MatcherBackend(matchers, streams, make_library_matcher, rank=rank, scorer=scorer,
-                                              device_output=layout.device_output if layout.kitti else None)
+                                              device_output=layout.device_output if layout.kitti else None,
+                                              vertical=vertical_offset == "auto")
         # a KITTI frame's size is its decoded left image's: the capture policy sees every change through the job's key
         reader = list_matcher.make_reader(
             paths, footprint, truth=layout.load_truth if args.evaluate else None,
             shape=(lambda left, image: layout.shape(left, ndisp_flag, image)) if layout.kitti else None,
             truth_right=layout.load_truth_right if (args.evaluate and both) else None)
-        writer = list_matcher.make_writer(rank, scorer=scorer, eval_file=out_eval_file, save=save)
+        writer = list_matcher.make_writer(rank, scorer=scorer, eval_file=out_eval_file, save=save,
+                                          save_vertical=save_vertical if vertical_offset == "auto" else None)
         pipeline = list_matcher.ListPipeline(reader, backend, writer, slots=in_flight, readers=args.readers)
         try:
             pipeline.run(indices)
         finally:
             print("[{}] {}".format(rank, pipeline.summary()))
     else:
-        loop = ListLoop(layout, matchers, streams, sd.SaturationRedo(matchers, make_library_matcher), scorer, save, rank)
+        loop = ListLoop(layout, matchers, streams, sd.SaturationRedo(matchers, make_library_matcher), scorer, save, rank,
+                        save_vertical=save_vertical if vertical_offset == "auto" else None)
         loop.run(indices, paths, lambda left_path: layout.shape(left_path, ndisp_flag), footprint)
     if scorer is not None:
         scorer.report.write(eval_path)

@@ -30,6 +30,9 @@ Opt-in departures from the reference's results (defaults reproduce it):
     VERTICAL_RANGE           0 | 1 .. 4    - compute_cost_volume for imperfectly rectified pairs: every pixel keeps, per
                                              disparity, its best score over the other view's rows h - R .. h + R
                                              (include/mccnn.h: mccnn_cost_volume_vertical_hwd; "exact" mode, ndisp <= 1024)
+    VERTICAL_OFFSET          0 | -8 .. 8   - compute_cost_volume along a row offset: the volumes against row h + offset of
+                                             the other view, VERTICAL_RANGE searched around it (include/mccnn.h:
+                                             mccnn_cost_volume_offset_hwd; "exact" mode); vertical_profile() measures it
     NUMPY1_PROMOTION         False | True  - sub-pixel formula evaluated as NumPy < 2 promotes its scalars (float64,
                                              rounded once): what the reference's own Python 2.7 + NumPy 1.14 computes;
                                              the default is NumPy >= 2's float32 chain, which the golden vectors pin
@@ -53,6 +56,7 @@ OCCLUSION_FROM_LEFT = False
 NUMPY1_PROMOTION = False
 SGM_INDEPENDENT_DIRECTIONS = False
 VERTICAL_RANGE = 0
+VERTICAL_OFFSET = 0
 
 _CV_MODES = {"exact": hip.MCCNN_CV_EXACT, "mfma": hip.MCCNN_CV_MFMA}
 _CBCA_ORDERS = {"separable": hip.MCCNN_CBCA_SEPARABLE, "reference": hip.MCCNN_CBCA_REFERENCE_ORDER,
@@ -61,7 +65,7 @@ _CBCA_ORDERS = {"separable": hip.MCCNN_CBCA_SEPARABLE, "reference": hip.MCCNN_CB
 __all__ = ["compute_features", "compute_cost_volume", "compute_cost_volume_accurate", "cost_volume_aggregation", "SGM_average",
            "disparity_prediction", "interpolation", "subpixel_enhance", "median_filter", "bilateral_filter",
            "semi_global_matching", "compute_cross_region", "confidence_measures", "interpolation_right", "semi_dense",
-           "speckle_filter"]
+           "speckle_filter", "vertical_profile"]
 
 
 def _dev(x, dtype=torch.float32):
@@ -119,6 +123,16 @@ def compute_cost_volume(featuresl, featuresr, ndisp):
     """pf:78-113."""
     fl, was_np = _dev(featuresl)
     fr, _ = _dev(featuresr)
+    if VERTICAL_OFFSET:
+        if isinstance(VERTICAL_OFFSET, bool) or not isinstance(VERTICAL_OFFSET, int) \
+                or abs(VERTICAL_OFFSET) > sd.VERTICAL_OFFSET_MAX:
+            raise ValueError("VERTICAL_OFFSET=%r: an integer in [-%d, %d]" % (VERTICAL_OFFSET, sd.VERTICAL_OFFSET_MAX,
+                                                                            sd.VERTICAL_OFFSET_MAX))
+        if COST_VOLUME_MODE != "exact":
+            raise ValueError("VERTICAL_OFFSET=%r: the row offset exists for COST_VOLUME_MODE 'exact' only" % VERTICAL_OFFSET)
+        k0 = torch.tensor([VERTICAL_OFFSET], dtype=torch.int32, device=fl.device)
+        hl, hr = sd.cost_volume_offset_hwd(fl, fr, int(ndisp), k0, VERTICAL_RANGE)
+        return _ret(sd.hwd_to_dhw(hl, int(ndisp)), was_np), _ret(sd.hwd_to_dhw(hr, int(ndisp)), was_np)
     if VERTICAL_RANGE:
         if COST_VOLUME_MODE != "exact":
             raise ValueError("VERTICAL_RANGE=%r: the vertical search exists for COST_VOLUME_MODE 'exact' only" % VERTICAL_RANGE)
@@ -126,6 +140,17 @@ def compute_cost_volume(featuresl, featuresr, ndisp):
         return _ret(sd.hwd_to_dhw(hl, int(ndisp)), was_np), _ret(sd.hwd_to_dhw(hr, int(ndisp)), was_np)
     lcv, rcv = sd.cost_volume(fl, fr, int(ndisp), _CV_MODES[COST_VOLUME_MODE])
     return _ret(lcv, was_np), _ret(rcv, was_np)
+
+
+def vertical_profile(featuresl, featuresr, ndisp, max_offset, row_step):
+    """The row offset of a pair, measured from its features (include/mccnn.h: mccnn_vertical_profile and
+    mccnn_vertical_offset_select): NumPy in, (offset int, totals uint64 [2 max_offset + 1], votes uint32 [n_rows,
+    ceil(W / 64), 2 max_offset + 1]) out."""
+    fl, _ = _dev(featuresl)
+    fr, _ = _dev(featuresr)
+    votes = sd.vertical_profile(fl, fr, int(ndisp), int(max_offset), int(row_step))
+    offset, totals = sd.vertical_offset_select(votes, int(max_offset))
+    return (int(offset.cpu().numpy()[0]), totals.cpu().numpy().view(np.uint64), votes.cpu().numpy().view(np.uint32))
 
 
 _DECISION_NETS = {}

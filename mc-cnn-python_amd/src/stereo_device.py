@@ -205,6 +205,78 @@ def cost_volume_vertical_hwd(fl, fr, ndisp, vertical_range, out=None):
     return lcv, rcv
 
 
+VERTICAL_OFFSET_MAX = 8        # mccnn_vertical_profile, mccnn_cost_volume_offset_hwd
+VERTICAL_OFFSET_BLOCK = 64     # pixels per vote block
+
+
+def vertical_profile_shape(H, W, max_offset, row_step):
+    """(n_rows, n_blocks, 2R + 1): the votes array of vertical_profile for an H x W pair."""
+    return (int(hip.load().mccnn_vertical_profile_rows(int(H), int(row_step))),
+            (int(W) + VERTICAL_OFFSET_BLOCK - 1) // VERTICAL_OFFSET_BLOCK, 2 * int(max_offset) + 1)
+
+
+def vertical_record(offset, totals):
+    """{offset, totals, share} of a measurement on the host: the offset, the votes per candidate -max .. +max and the
+    winner's share of all votes (0.0 without votes)."""
+    offset = int(np.asarray(offset).reshape(-1)[0])
+    totals = [int(t) for t in np.asarray(totals).reshape(-1)]
+    n, k = sum(totals), offset + (len(totals) - 1) // 2
+    return dict(offset=offset, totals=totals, share=(float(totals[k]) / n if n and 0 <= k < len(totals) else 0.0))
+
+
+def vertical_profile(fl, fr, ndisp, max_offset, row_step, out=None):
+    """The row-offset votes of a pair's features (include/mccnn.h: mccnn_vertical_profile has the definition): int32
+    [n_rows, ceil(W / 64), 2 max_offset + 1] holding the uint32 counts, overwritten whatever `out` held."""
+    H, W, C = fl.shape
+    if not 0 <= int(max_offset) <= VERTICAL_OFFSET_MAX or int(row_step) < 1:       # (the shape below needs them sane)
+        raise ValueError("vertical_profile: max_offset=%r outside [0, %d] or row_step=%r < 1"
+                         % (max_offset, VERTICAL_OFFSET_MAX, row_step))
+    shape = vertical_profile_shape(H, W, max_offset, row_step)
+    votes = torch.empty(shape, dtype=torch.int32, device=fl.device) if out is None else out
+    hip.check(hip.load().mccnn_vertical_profile(hip.ptr(fl), hip.ptr(fr), H, W, C, int(ndisp), int(max_offset), int(row_step),
+                                                hip.ptr(votes), votes.numel() * votes.element_size(), hip.stream()),
+              "mccnn_vertical_profile")
+    return votes
+
+
+def vertical_offset_select(votes, max_offset, out=None):
+    """(offset int32 [1], totals int64 [2 max_offset + 1]) of a votes array, on the device (mccnn_vertical_offset_select):
+    the offset with the most votes, ties to the smaller |k|, then to the negative one; no votes give 0."""
+    nk = 2 * int(max_offset) + 1
+    if out is None:
+        offset = torch.empty((1,), dtype=torch.int32, device=votes.device)
+        totals = torch.empty((nk,), dtype=torch.int64, device=votes.device)
+    else:
+        offset, totals = out
+    if votes.dim() != 3 or votes.shape[2] != nk or totals.numel() < nk:
+        raise ValueError("vertical_offset_select: votes %s / totals %s do not belong to max_offset=%d"
+                         % (tuple(votes.shape), tuple(totals.shape), int(max_offset)))
+    hip.check(hip.load().mccnn_vertical_offset_select(hip.ptr(votes), int(votes.shape[0]), int(votes.shape[1]),
+                                                      int(max_offset), hip.ptr(offset), hip.ptr(totals), hip.stream()),
+              "mccnn_vertical_offset_select")
+    return offset, totals
+
+
+def cost_volume_offset_hwd(fl, fr, ndisp, row_offset, vertical_range, out=None):
+    """The bit-exact pixel-major volumes [H,W,Dp] taken along a row offset (include/mccnn.h: mccnn_cost_volume_offset_hwd):
+    the search of +-vertical_range rows around row h + k0 of the other view.  row_offset: a device int32 tensor the
+    kernel reads k0 from (clamped to +-8), or None for 0 - then the launches of cost_volume_vertical_hwd."""
+    H, W, C = fl.shape
+    dp = hwd_pitch(ndisp)
+    if out is None:
+        lcv = torch.zeros((H, W, dp), dtype=torch.float32, device=fl.device)
+        rcv = torch.zeros((H, W, dp), dtype=torch.float32, device=fl.device)
+    else:
+        lcv, rcv = out
+    if row_offset is not None and (row_offset.dtype != torch.int32 or row_offset.numel() < 1):
+        raise ValueError("cost_volume_offset_hwd: row_offset must be a device int32 tensor or None")
+    hip.check(hip.load().mccnn_cost_volume_offset_hwd(hip.ptr(fl), hip.ptr(fr), H, W, C, int(ndisp),
+                                                      hip.ptr(row_offset) if row_offset is not None else None,
+                                                      int(vertical_range), hip.ptr(lcv), hip.ptr(rcv), hip.stream()),
+              "mccnn_cost_volume_offset_hwd")
+    return lcv, rcv
+
+
 # ---- a2 for the accurate network: the decision MLP per (pixel, disparity) ------------------------------------------
 DECISION_UNITS = 384                     # csrc/decision_mfma.hip
 DECISION_MAPS = (64, 112)
@@ -1576,7 +1648,8 @@ def check_envelope(H, W, D):
 
 
 def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flight=1, arch="fast",
-                    fc_units=DECISION_UNITS, confidence=0, views="left", semi_dense=False):
+                    fc_units=DECISION_UNITS, confidence=0, views="left", semi_dense=False, vertical_offset=0,
+                    vertical_offset_max=4, vertical_offset_rows=8):
     """Device bytes StereoMatcher.workspace(H, W, D) allocates, times `pairs_in_flight` (match.py --pairs_in_flight:
     one matcher per pair in flight): four volumes of H*W*Dp*4 bytes (Dp = hwd_pitch(D)), the SGM scratch and the flag
     planes of the four directions, both support planes, the status and map planes, and - on pixel-major volumes with
@@ -1588,7 +1661,10 @@ def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flig
     views="both" (StereoMatcher(views="both")): plus the right view's status plane, its three intermediate maps, the
     [2,H,W] result and a second set of confidence planes.
     semi_dense (StereoMatcher(semi_dense=...)): plus, per view, two [H,W] float32 maps (the selection and the sparse map),
-    the labelling scratch (mccnn_speckle_scratch_bytes) and a [H,W] size plane; False (default): none."""
+    the labelling scratch (mccnn_speckle_scratch_bytes) and a [H,W] size plane; False (default): none.
+    vertical_offset, vertical_offset_max, vertical_offset_rows (the StereoMatcher extras of these names): with an offset
+    other than 0 plus the offset (int32 [1]), the totals (int64 [2 max + 1]) and the votes (int32 [n_rows, ceil(W / 64),
+    2 max + 1]); 0 (default): none."""
     check_envelope(H, W, D)
     if views not in VIEWS:
         raise ValueError("views must be 'left' or 'both'")
@@ -1610,6 +1686,9 @@ def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flig
         n += (1 + 3 + 2 + int(confidence)) * H * W * 4
     if semi_dense:
         n += (2 if views == "both" else 1) * (3 * H * W * 4 + int(lib.mccnn_speckle_scratch_bytes(H, W)))
+    if vertical_offset != 0:
+        rows, blocks, nk = vertical_profile_shape(H, W, vertical_offset_max, vertical_offset_rows)
+        n += 4 + 8 * nk + 4 * rows * blocks * nk
     return n * max(1, int(pairs_in_flight))
 
 
@@ -1712,7 +1791,8 @@ class StereoMatcher(object):
         # sgm_independent_directions: the paper's SGM - the four directions each from the same volume, averaged
         # (sgm_average_independent_hwd) - instead of the reference's four passes composed on one array
         self.extras = dict(both_view_support=False, interpolation_directions=4, occlusion_from_left=False,
-                           numpy1_promotion=False, sgm_independent_directions=False, vertical_range=0)
+                           numpy1_promotion=False, sgm_independent_directions=False, vertical_range=0,
+                           vertical_offset=0, vertical_offset_max=4, vertical_offset_rows=8)
         if extras:
             unknown = set(extras) - set(self.extras)
             if unknown:
@@ -1722,6 +1802,12 @@ class StereoMatcher(object):
         # in the place of cost_volume_hwd; every later stage is the same.  0 (default): nothing changes - the same
         # launches, workspace and graphs.  Only where the bit-exact dot-product volume is written pixel-major.
         self._check_vertical_range()
+        # vertical_offset: the cost volume taken along a row offset of the pair (cost_volume_offset_hwd), vertical_range
+        # searched around it.  An integer in [-8, 8] is placed in the workspace once; "auto" measures it per pair on the
+        # pair's stream (vertical_profile of +-vertical_offset_max rows on every vertical_offset_rows-th row ->
+        # vertical_offset_select -> the volume; no host round trip, capturable); vertical_report() reads the measurement
+        # back.  0 (default): nothing changes - no launch, no buffer.  Refused where vertical_range > 0 is.
+        self._check_vertical_offset()
         # confidence measures of the returned map (CONFIDENCE_MEASURES; names in any order, planes in that order): one
         # more launch per pair behind the post-processing, and every match entry returns (map, planes [K,H,W]).
         # Empty (default): nothing changes - no launch, no buffer, the map alone is returned.
@@ -1765,6 +1851,46 @@ class StereoMatcher(object):
                              "cost volume starts plane-major (layout='plane_major', the separable aggregation order or "
                              "both_view_support)" % r)
 
+    def _check_vertical_offset(self):
+        v, R, step = (self.extras[k] for k in ("vertical_offset", "vertical_offset_max", "vertical_offset_rows"))
+        if v != "auto" and (isinstance(v, bool) or not isinstance(v, int) or abs(v) > VERTICAL_OFFSET_MAX):
+            raise ValueError("vertical_offset must be 'auto' or an integer in [-%d, %d], not %r"
+                             % (VERTICAL_OFFSET_MAX, VERTICAL_OFFSET_MAX, v))
+        if isinstance(R, bool) or not isinstance(R, int) or not 1 <= R <= VERTICAL_OFFSET_MAX:
+            raise ValueError("vertical_offset_max must be an integer in [1, %d], not %r" % (VERTICAL_OFFSET_MAX, R))
+        if isinstance(step, bool) or not isinstance(step, int) or step < 1:
+            raise ValueError("vertical_offset_rows must be an integer >= 1, not %r" % (step,))
+        if v == 0:
+            return
+        if self.accurate:
+            raise ValueError("vertical_offset=%r: the accurate network's decision stage has no row offset" % (v,))
+        if self.cv_mode != hip.MCCNN_CV_EXACT:
+            raise ValueError("vertical_offset=%r: the matrix-core cost volume (MCCNN_CV_MFMA) has no row offset" % (v,))
+        if not self.pixel_major():
+            raise ValueError("vertical_offset=%r: the offset cost volume writes pixel-major volumes, and this "
+                             "configuration's cost volume starts plane-major (layout='plane_major', the separable "
+                             "aggregation order or both_view_support)" % (v,))
+
+    def _vertical_offset_on(self):
+        return self.extras["vertical_offset"] != 0
+
+    def vertical_report(self, H, W, D):
+        """The row offset the last pair on the workspace of this shape was matched along: {offset, totals, share} -
+        the offset, the votes per candidate -max .. +max and the winner's share of them (an integer vertical_offset has
+        no votes: zeros and 0.0).  Synchronises the device; never call it inside a capture."""
+        buffers = self.vertical_buffers(H, W, D)
+        if buffers is None:
+            raise ValueError("vertical_report: no pair of %dx%d, ndisp=%d has been matched with vertical_offset on"
+                             % (W, H, D))
+        torch.cuda.synchronize()
+        return vertical_record(buffers[0].cpu().numpy(), buffers[1].cpu().numpy())
+
+    def vertical_buffers(self, H, W, D):
+        """(offset int32 [1], totals int64 [2 max + 1]) of the resident workspace of this shape - what vertical_report()
+        reads, for a caller that copies them out in stream order itself (the list loops) - or None."""
+        ws = self._ws.get((int(H), int(W), int(D)))
+        return (ws["v_offset"], ws["v_totals"]) if ws is not None and "v_offset" in ws else None
+
     def _right_stream(self):
         """The stream of the right volume's chain of aggregation launches: this matcher's own (like its side stream), so
         that a stream never meets the captures of two different graphs - a module-wide stream that had been part of
@@ -1798,7 +1924,9 @@ class StereoMatcher(object):
                                    arch="accurate" if self.accurate else "fast",
                                    fc_units=self.net.num_fc_units if self.accurate else DECISION_UNITS,
                                    confidence=len(self.confidence), views=self.views,
-                                   semi_dense=self.semi_dense is not None)
+                                   semi_dense=self.semi_dense is not None,
+                                   **{k: self.extras[k] for k in ("vertical_offset", "vertical_offset_max",
+                                                                  "vertical_offset_rows") if self._vertical_offset_on()})
             self._ws, self._graphs = {}, {}          # one shape resident at a time: the previous one goes first
             _require_device_memory(need, "StereoMatcher: the workspace of a %dx%d pair with ndisp=%d" % (W, H, D))
             dp = hwd_pitch(D)
@@ -1828,6 +1956,12 @@ class StereoMatcher(object):
                 ws["semi_selected"] = torch.empty(lead + (H, W), dtype=torch.float32, device=dev)
                 ws["semi_sizes"] = torch.empty(lead + (H, W), dtype=torch.int32, device=dev)
                 ws["semi_scratch"] = [speckle_scratch(H, W, dev) for _ in range(2 if self.both else 1)]
+            if self._vertical_offset_on():
+                v, R = self.extras["vertical_offset"], self.extras["vertical_offset_max"]
+                ws["v_offset"] = torch.full((1,), 0 if v == "auto" else v, dtype=torch.int32, device=dev)
+                ws["v_totals"] = torch.zeros((2 * R + 1,), dtype=torch.int64, device=dev)
+                ws["v_votes"] = torch.zeros(vertical_profile_shape(H, W, R, self.extras["vertical_offset_rows"]),
+                                            dtype=torch.int32, device=dev)
             ws["progs"] = None
             # (distances above CBCA_HWD_MAX_DISTANCE: the aggregation programs do not encode such arms - the joined
             # two-volume path of mccnn_cbca_iter_hwd_long_pair runs, as for shapes the programs do not encode)
@@ -1969,8 +2103,18 @@ class StereoMatcher(object):
         if vertical and not direct:
             raise ValueError("vertical_range=%d: the vertical search writes pixel-major volumes of at most %d disparities, "
                              "not %d" % (vertical, COST_VOLUME_HWD_MAX_D, D))
+        offset = self.extras["vertical_offset"]
+        if offset != 0 and not direct:
+            raise ValueError("vertical_offset=%r: the offset cost volume writes pixel-major volumes of at most %d "
+                             "disparities, not %d" % (offset, COST_VOLUME_HWD_MAX_D, D))
         timer.start("cost_volume")
-        if vertical:
+        if offset != 0:
+            if offset == "auto":      # measured from this pair's features, on this stream; the kernel reads the result
+                votes = vertical_profile(fl, fr, D, self.extras["vertical_offset_max"],
+                                         self.extras["vertical_offset_rows"], out=ws["v_votes"])
+                vertical_offset_select(votes, self.extras["vertical_offset_max"], out=(ws["v_offset"], ws["v_totals"]))
+            left, right = cost_volume_offset_hwd(fl, fr, D, ws["v_offset"], vertical, out=(hwd[2], hwd[3]))
+        elif vertical:
             left, right = cost_volume_vertical_hwd(fl, fr, D, vertical, out=(hwd[2], hwd[3]))
         elif direct:
             left, right = cost_volume_hwd(fl, fr, D, out=(hwd[2], hwd[3]), mode=self.cv_mode)
