@@ -618,6 +618,37 @@ size_t mccnn_speckle_scratch_bytes(int H, int W);   /* 0 for non-positive sizes 
 int mccnn_speckle_filter(const float *disp, int H, int W, float max_diff, unsigned min_size, float *out /* or NULL */,
                          uint32_t *sizes /* or NULL */, void *scratch, size_t scratch_bytes, mccnn_stream_t stream);
 
+/* ---- metric outputs: the depth plane and the ordered point cloud of a disparity map (csrc/reproject.hip) ---------------
+ * Still ABI version 7: purely additive, nothing that existed changed.
+ * Definitions (binding).  The relation is Middlebury 2014's, Z = baseline * f / (d + doffs), Z in the unit of the
+ *   baseline.  All arithmetic is float32 and every operation below is one correctly rounded IEEE operation, never fused,
+ *   never a reciprocal.  The caller rounds the host scalars once from float64: fb = f32(fx * baseline) (the product in
+ *   float64), and fx, fy, cx, cy, doffs, max_depth each on their own.
+ *   den = d + doffs.  A pixel has a depth iff d is finite and den > 0; then Z = fb / den, otherwise Z = +inf (bits
+ *   0x7F800000, PFM's "unknown": the convention of the sparse maps).  NaN, +-inf and d = -doffs exactly all give +inf;
+ *   -0.0 is an ordinary zero; subnormal d, den and Z are kept, not flushed; Z may overflow to +inf or underflow to 0.
+ *   The point of pixel (h, w):  X = (((float)w - cx) * Z) / fx,  Y = (((float)h - cy) * Z) / fy  - sub, mul, div.
+ *   A pixel becomes a point iff Z is finite and Z <= max_depth (+inf keeps every finite Z; a Z equal to it is kept).
+ * mccnn_depth, one streaming launch: depth[h][w] = Z.  map and depth need 4-byte alignment and must not overlap.
+ * mccnn_reproject_points, an ordered stream compaction: points holds the kept pixels in raster order as 16-byte records
+ *   (X, Y, Z, the bits of the uint32 h * W + w) - the fourth word lets the host colour a point from the image it has -
+ *   and *n_points (one device uint32) their number.  Records at index >= n_points are NOT written.  points: H * W * 16
+ *   bytes, 16-byte aligned (MCCNN_E_INVALID otherwise); scratch: mccnn_points_scratch_bytes(H, W) bytes, 16-byte aligned,
+ *   private to one call in flight, and every word the call reads of it it has written before on the stream, so calls may
+ *   follow each other on one scratch.  H * W <= 2^31 - 1, beyond that MCCNN_E_UNSUPPORTED.
+ *   Four launches - block counts, two levels of an exclusive prefix sum, the ranked write - whose number and sizes depend
+ *   on H and W alone: no read-back, no allocation, no synchronisation, no atomics, and no wait on another workgroup (a
+ *   scan level is a launch): capturable.  A pixel's rank is a sum of counts plus its place in a wave's ballot, so the
+ *   order and the bytes are a function of the map and the scalars alone, on every run and every replay.
+ * Refused before any HIP call (MCCNN_E_INVALID), naming the argument: null pointers, non-positive sizes, fx, fy or fb that
+ *   is not finite and > 0, a non-finite cx, cy or doffs, a NaN max_depth, overlapping buffers; a misaligned or short
+ *   scratch is MCCNN_E_SCRATCH.  A refused call writes nothing. */
+int mccnn_depth(const float *map, int H, int W, float fb, float doffs, float *depth, mccnn_stream_t stream);
+size_t mccnn_points_scratch_bytes(int H, int W);    /* 0 for non-positive sizes and beyond the pixel limit */
+int mccnn_reproject_points(const float *map, int H, int W, float fx, float fy, float cx, float cy, float fb, float doffs,
+                           float max_depth, float *points /* [H*W][4] */, uint32_t *n_points, void *scratch,
+                           size_t scratch_bytes, mccnn_stream_t stream);
+
 /* ---- a10 median_filter (pf:403-421): clipped fh x fw window (odd sizes, fh*fw <= 49), np.median -------------
  * np.median to the bit: NaN in the window gives NaN, and a median of -0.0 is +0.0 (np.mean's sum starts from +0).
  * Other window sizes and H > 65535 (rows go on grid.y): MCCNN_E_UNSUPPORTED. */

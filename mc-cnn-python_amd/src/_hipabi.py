@@ -88,6 +88,9 @@ SIGNATURES = {
     "mccnn_semi_dense_select": (_i, [_vp, _vp, _vp, _i, _i, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(_f), _i, _vp, _vp]),
     "mccnn_speckle_scratch_bytes": (_sz, [_i, _i]),
     "mccnn_speckle_filter": (_i, [_vp, _i, _i, _f, ctypes.c_uint, _vp, _vp, _vp, _sz, _vp]),
+    "mccnn_depth": (_i, [_vp, _i, _i, _f, _f, _vp, _vp]),
+    "mccnn_points_scratch_bytes": (_sz, [_i, _i]),
+    "mccnn_reproject_points": (_i, [_vp, _i, _i, _f, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _sz, _vp]),
     "mccnn_hwd_pitch": (_i, [_i]),
     "mccnn_dhw_to_hwd": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "mccnn_hwd_to_dhw": (_i, [_vp, _vp, _i, _i, _i, _vp]),

@@ -112,6 +112,14 @@ class Middlebury(object):
         1, --views both: disp1MCCNN_s.pfm)."""
         return os.path.join(paths["res_dir"], "disp%dMCCNN_s.pfm" % int(view))
 
+    def depth_path(self, paths):
+        """match.py --depth: the left view's depth plane beside disp0MCCNN.pfm, unknown pixels as inf."""
+        return os.path.join(paths["res_dir"], "depth0MCCNN.pfm")
+
+    def points_path(self, paths):
+        """match.py --point_cloud: the left view's point cloud beside disp0MCCNN.pfm."""
+        return os.path.join(paths["res_dir"], "points0MCCNN.ply")
+
     def vertical_path(self, paths):
         """match.py --vertical_offset auto: the pair's measured row offset beside disp0MCCNN.pfm."""
         return os.path.join(paths["res_dir"], "verticalMCCNN.json")

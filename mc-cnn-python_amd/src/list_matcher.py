@@ -206,7 +206,7 @@ def pinned(a):
     return torch.from_numpy(np.ascontiguousarray(a)).pin_memory()
 
 
-def make_reader(paths, check_shape, to_host_buffer=pinned_u8, truth=None, shape=None, truth_right=None):
+def make_reader(paths, check_shape, to_host_buffer=pinned_u8, truth=None, shape=None, truth_right=None, calibration=None):
     """read(index) for ListPipeline on top of match.py's file layout.  `paths(index)` -> dict(left, right, calib, out,
     out_time, out_img, res_dir, img_dir[, dirs: every directory the outputs need]); `check_shape(H, W, ndisp)` raises for
     a pair outside the envelope - before anything of that pair reaches the GPU.  `shape`: None - the size and ndisp are
@@ -214,7 +214,9 @@ def make_reader(paths, check_shape, to_host_buffer=pinned_u8, truth=None, shape=
     for a data set whose size is the decoded left image's (datasets.py: the KITTI layouts).  `truth(left_path)` (match.py
     --evaluate: the layout's load_truth) -> (ground truth, mask or None) or None: read here as well, into pinned memory
     beside the images (job.gt, job.mask; job.gt None = a pair without ground truth).  `truth_right` (--views both): the
-    same for the right view's ground truth (job.gt_right, job.mask_right)."""
+    same for the right view's ground truth (job.gt_right, job.mask_right).  `calibration(paths)` (match.py --depth /
+    --point_cloud) -> the pair's calibration (hashable): read here as well (job.calib) and appended to the job's key, since
+    a captured graph holds it by value - the capture policy then replays a pair only where shape and calibration repeat."""
     def read(index):
         p = paths(index)
         if shape is None:
@@ -246,9 +248,11 @@ def make_reader(paths, check_shape, to_host_buffer=pinned_u8, truth=None, shape=
 
         gt, mask = pinned_truth(truth, "ground truth")
         gt_right, mask_right = pinned_truth(truth_right, "right view's ground truth")
-        return Job(index, p["left"], (height, width, ndisp, channels), height=height, width=width, ndisp=ndisp,
+        calib = calibration(p) if calibration is not None else None
+        key = (height, width, ndisp, channels) + ((calib,) if calib is not None else ())
+        return Job(index, p["left"], key, height=height, width=width, ndisp=ndisp,
                    left=to_host_buffer(left), right=to_host_buffer(right), paths=p, gt=gt, mask=mask, gt_right=gt_right,
-                   mask_right=mask_right)
+                   mask_right=mask_right, calib=calib)
     return read
 
 
@@ -370,6 +374,8 @@ class MatcherBackend(object):
         self.log("[{}] pair {}: {}  ({}x{}, ndisp {}, {} byte(s) per pixel, {})".format(
             self.rank, job.index, job.name, job.width, job.height, job.ndisp, job.key[3], mode))
         m = self.matchers[slot]
+        if getattr(job, "calib", None) is not None:      # a launch argument of the metric outputs, and part of the graph's key
+            m.set_calibration(job.calib)
         with self._stream(slot):
             match = m.match_u8 if mode == "eager" else m.match_graph_u8
             ticket = self._to_host(m.result_of(match(job.left, job.right, job.ndisp)), m, job)
@@ -391,6 +397,8 @@ class MatcherBackend(object):
         def rematch():
             library = self.redo.matcher()
             self.log("[{}] ".format(self.rank) + self.redo.notice(job.paths["out"]))
+            if getattr(job, "calib", None) is not None:
+                library.set_calibration(job.calib)
             again = self._to_host(library.result_of(library.match_u8(job.left, job.right, job.ndisp)), library, job)
             return again, again.device
         again = slot_comes_round(self.redo, rematch, self.scorer, job.scored if self.scorer is not None else None,

@@ -24,6 +24,9 @@ mask1nocc.png) and every evaluation file gains a "right" block.  Middlebury layo
 exactly on the device, and the list's pooled quantiles at 16 bits, in all three loops.  Middlebury layout only.
 --vertical_offset auto|N matches a pair whose right image sits N rows low along that offset; auto measures N per pair on
 the device and writes verticalMCCNN.json beside disp0MCCNN.pfm, the same bytes in all three loops.
+--depth writes the left view's depth plane, depth0MCCNN.pfm, and --point_cloud [--max_depth Z] its ordered point cloud,
+points0MCCNN.ply, beside disp0MCCNN.pfm from the pair's calib.txt (cam0, doffs, baseline; --calib overrides it), computed
+on the device behind the map, the same bytes in all three loops.  Middlebury layout only.
 Multi-GPU: launch one process per GPU with different -g / -s / -e, as the reference intends (match.py:17, 26-28),
 or use `torchrun --nproc-per-node N match.py ...`: rank r then takes the pairs i = r (mod N) of the window.
 """
@@ -41,6 +44,7 @@ import datasets
 import evaluation          # (neither module touches torch or the GPU on import: util.pin_gpu comes first, in main)
 import list_matcher
 import util
+from calibration import Calibration, point_pixels, write_ply
 from semi_dense_rule import SemiDenseRule
 
 # Flag names, types and defaults are the reference's command line (match.py:15-43) - that is the drop-in contract;
@@ -209,6 +213,23 @@ parser.add_argument("--semi_dense", type=str, default=None, metavar="RULE",
                          "density and the bad share among the kept pixels) in evalMCCNN.json and eval.json; "
                          "--eval_quantiles and the sparsification stay figures of the dense map.  Not with a KITTI "
                          "--dataset.  Without it every file keeps its bytes")
+parser.add_argument("--depth", action="store_true",
+                    help="the left view's depth plane beside every map, depth0MCCNN.pfm: Z = baseline * f / (d + doffs) of "
+                         "the pair's calib.txt (cam0, doffs, baseline; Middlebury 2014's relation, Z in the unit of the "
+                         "baseline, mm there), pixels without a depth as inf; one more launch per pair on the device "
+                         "(include/mccnn.h: mccnn_depth).  Always of the dense map.  Not with a KITTI --dataset.  Without it "
+                         "every file keeps its bytes")
+parser.add_argument("--point_cloud", action="store_true",
+                    help="the left view's point cloud beside every map, points0MCCNN.ply: binary little-endian PLY, x y z "
+                         "float32 and the grey value of the left image as intensity uchar, one vertex per pixel with a "
+                         "depth in raster order (include/mccnn.h: mccnn_reproject_points, an ordered compaction on the "
+                         "device).  With --semi_dense the cloud is the sparse map's: dropped pixels are no points.  Not "
+                         "with a KITTI --dataset.  Without it every file keeps its bytes")
+parser.add_argument("--max_depth", type=float, default=None, metavar="Z",
+                    help="with --point_cloud: only pixels with a depth of at most Z become points (default: every pixel with "
+                         "a finite depth)")
+parser.add_argument("--calib", type=str, default=None, metavar="fx,fy,cx,cy,baseline[,doffs]",
+                    help="with --depth / --point_cloud: this calibration for every pair, instead of each pair's calib.txt")
 
 CONFIDENCE_MEASURES = ("msm", "mmn", "cur", "lrc")      # stereo_device.CONFIDENCE_MEASURES (not imported before the GPU is pinned)
 
@@ -269,11 +290,12 @@ class ListLoop(object):
     save(PairResult of host arrays, paths): the files of what crossed to the host; save_vertical(offset, totals, paths)
     (--vertical_offset auto): the file of the pair's measured row offset, copied out behind the pair on its stream."""
 
-    def __init__(self, layout, matchers, streams, redo, scorer, save, rank, save_vertical=None):
+    def __init__(self, layout, matchers, streams, redo, scorer, save, rank, save_vertical=None, calibration=None):
         import torch
         self.torch = torch
         self.layout, self.matchers, self.streams, self.redo, self.scorer = layout, matchers, streams, redo, scorer
         self.save, self.rank, self.save_vertical = save, rank, save_vertical
+        self.calibration = calibration      # --depth / --point_cloud: paths -> the pair's Calibration, a launch argument
         self.pending = []            # oldest first
 
     def _stream(self, slot):
@@ -286,10 +308,12 @@ class ListLoop(object):
         return (self.torch.from_numpy(truth[0]).cuda(),
                 self.torch.from_numpy(truth[1]).cuda() if truth[1] is not None else None)
 
-    def _matched(self, matcher, images, scoring):
+    def _matched(self, matcher, images, scoring, paths):
         """One pair on `matcher`: ((what crosses to the host for its map, copies of its measured row offset and totals or
         None), its PairResult with the map that is scored) - the map, or a KITTI layout's 16-bit code and what it holds,
         behind the map on the current stream."""
+        if self.calibration is not None:
+            matcher.set_calibration(self.calibration(paths))
         result = matcher.result_of(matcher.match(*images))
         crossing, kept = self.layout.device_output(result.map, scoring)
         vertical = None
@@ -304,7 +328,7 @@ class ListLoop(object):
         started = time.time()
         with self._stream(slot):
             images = (torch.from_numpy(left_image).cuda(), torch.from_numpy(right_image).cuda(), ndisp)
-            crossing, result = self._matched(self.matchers[slot], images, truth is not None)
+            crossing, result = self._matched(self.matchers[slot], images, truth is not None, paths)
             scored = None                    # the evaluation: behind the map and what is scored, on this stream
             if self.scorer is not None:
                 scored = self.scorer.begin(index, paths["left"], self._to_device(truth), self._to_device(truth_right))
@@ -322,7 +346,7 @@ class ListLoop(object):
         def rematch():
             library = self.redo.matcher()
             print("[{}] ".format(self.rank) + self.redo.notice(p.paths["out"]))
-            return self._matched(library, p.images, p.scored is not None)
+            return self._matched(library, p.images, p.scored is not None, p.paths)
         crossing, result = list_matcher.slot_comes_round(self.redo, rematch, self.scorer, p.scored, p.result, p.slot,
                                                          lambda: self._stream(p.slot),
                                                          self.torch.cuda.synchronize) or (p.crossing, p.result)
@@ -462,6 +486,26 @@ def main(argv=None):
         if missing:
             parser.error("--semi_dense reads the confidence measure %s, which --confidence does not name"
                          % ", ".join(missing))
+    geometry = None
+    if args.depth or args.point_cloud:
+        if layout.kitti:
+            parser.error("%s is not available with --dataset %s: the development kit's calibration format is not at hand"
+                         % ("--depth" if args.depth else "--point_cloud", args.dataset))
+        geometry = dict(depth=args.depth, points=args.point_cloud)
+    if args.max_depth is not None:
+        if not args.point_cloud:
+            parser.error("--max_depth goes with --point_cloud")
+        if args.max_depth != args.max_depth:
+            parser.error("--max_depth: NaN")
+        geometry["max_depth"] = args.max_depth
+    calib_override = None
+    if args.calib is not None:
+        if geometry is None:
+            parser.error("--calib goes with --depth or --point_cloud")
+        try:
+            calib_override = Calibration.parse(args.calib)
+        except ValueError as e:
+            parser.error("--calib: %s" % e)
     both = args.views == "both"
     if both and layout.kitti:
         parser.error("--views both is not available with --dataset %s: the KITTI development kit has neither right-view "
@@ -532,7 +576,22 @@ def main(argv=None):
                         interpolation_directions=16 if args.paper_interpolation else 4,
                         occlusion_from_left=args.paper_interpolation, numpy1_promotion=args.numpy1_promotion,
                         sgm_independent_directions=args.paper_sgm, vertical_range=args.vertical_range, **vertical_kw),
-            confidence=conf_names, views=args.views, semi_dense=semi_rule)
+            confidence=conf_names, views=args.views, semi_dense=semi_rule, geometry=geometry)
+
+    def calibration(p):
+        """--depth / --point_cloud: the pair's calibration, its calib.txt read by key unless --calib overrides it."""
+        return calib_override if calib_override is not None else Calibration.from_middlebury(p["calib"])
+
+    def save_geometry(result, out):
+        """The left view's depth plane and cloud.  The whole record buffer crossed (nothing is read back to size the copy):
+        the first n_points records are the cloud, in the device's order; a vertex takes its intensity from the grey left
+        image through the record's pixel index."""
+        if result.depth is not None:
+            util.writePfm(result.depth, layout.depth_path(out))
+        if result.points is not None:
+            records = result.points[:int(np.asarray(result.n_points).view(np.uint32)[0])]
+            grey = util.read_gray(out["left"]).reshape(-1)
+            write_ply(layout.points_path(out), records, grey[point_pixels(records)])
 
     def save(result, out):
         """The files of a pair from the PairResult of host arrays that crossed: the map's (--views both: [2,H,W], the right
@@ -549,6 +608,7 @@ def main(argv=None):
         for v, r in views:
             if r.sparse is not None:
                 util.writePfm(r.sparse, layout.sparse_path(out, v))
+        save_geometry(result, out)
 
     def paths(index):
         # Middlebury: outputs mirror the input tree under the two roots (match.py:99-110): <root>/<dir of im0.png relative
@@ -560,7 +620,8 @@ def main(argv=None):
     matchers = [make_matcher("miopen" if args.features == "library" else "auto") for _ in range(in_flight)]
     footprint_kw = dict(pairs_in_flight=in_flight, arch=args.arch,
                         fc_units=net.num_fc_units if accurate else sd.DECISION_UNITS, confidence=len(conf_names),
-                        views=args.views, **(dict(semi_dense=True) if semi_rule is not None else {}), **vertical_kw)
+                        views=args.views, **(dict(semi_dense=True) if semi_rule is not None else {}), **vertical_kw,
+                        **(dict(depth=args.depth, points=args.point_cloud) if geometry is not None else {}))
 
     def footprint(height, width, ndisp):        # refuses a shape outside the envelope, with its message
         return sd.workspace_bytes(height, width, ndisp, matchers[0].pixel_major(),
@@ -591,11 +652,14 @@ def main(argv=None):
         backend = list_matcher.MatcherBackend(matchers, streams, make_library_matcher, rank=rank, scorer=scorer,
                                               device_output=layout.device_output if layout.kitti else None,
                                               vertical=vertical_offset == "auto")
+        # (--depth / --point_cloud: the calibration joins the job's key - a graph is good for the calibration it was
+        # captured with, so a pair is replayed only where shape AND calibration repeat; Middlebury's differ pair by pair)
         # a KITTI frame's size is its decoded left image's: the capture policy sees every change through the job's key
         reader = list_matcher.make_reader(
             paths, footprint, truth=layout.load_truth if args.evaluate else None,
             shape=(lambda left, image: layout.shape(left, ndisp_flag, image)) if layout.kitti else None,
-            truth_right=layout.load_truth_right if (args.evaluate and both) else None)
+            truth_right=layout.load_truth_right if (args.evaluate and both) else None,
+            calibration=calibration if geometry is not None else None)
         writer = list_matcher.make_writer(rank, scorer=scorer, eval_file=out_eval_file, save=save,
                                           save_vertical=save_vertical if vertical_offset == "auto" else None)
         pipeline = list_matcher.ListPipeline(reader, backend, writer, slots=in_flight, readers=args.readers)
@@ -605,7 +669,8 @@ def main(argv=None):
             print("[{}] {}".format(rank, pipeline.summary()))
     else:
         loop = ListLoop(layout, matchers, streams, sd.SaturationRedo(matchers, make_library_matcher), scorer, save, rank,
-                        save_vertical=save_vertical if vertical_offset == "auto" else None)
+                        save_vertical=save_vertical if vertical_offset == "auto" else None,
+                        calibration=calibration if geometry is not None else None)
         loop.run(indices, paths, lambda left_path: layout.shape(left_path, ndisp_flag), footprint)
     if scorer is not None:
         scorer.report.write(eval_path)

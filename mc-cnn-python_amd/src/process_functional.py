@@ -65,7 +65,7 @@ _CBCA_ORDERS = {"separable": hip.MCCNN_CBCA_SEPARABLE, "reference": hip.MCCNN_CB
 __all__ = ["compute_features", "compute_cost_volume", "compute_cost_volume_accurate", "cost_volume_aggregation", "SGM_average",
            "disparity_prediction", "interpolation", "subpixel_enhance", "median_filter", "bilateral_filter",
            "semi_global_matching", "compute_cross_region", "confidence_measures", "interpolation_right", "semi_dense",
-           "speckle_filter", "vertical_profile"]
+           "speckle_filter", "vertical_profile", "depth_from_disparity", "reproject"]
 
 
 def _dev(x, dtype=torch.float32):
@@ -405,3 +405,20 @@ def speckle_filter(disparity_map, min_size, max_diff=1.0, return_sizes=False):
     if not return_sizes:
         return _ret(out, was_np)
     return _ret(out, was_np), (sizes.cpu().numpy().view(np.uint32) if was_np else sizes)
+
+
+def depth_from_disparity(disparity_map, calib):
+    """Not in the reference: the depth plane of `disparity_map` under `calib` (a calibration.Calibration or its text
+    "fx,fy,cx,cy,baseline[,doffs]"; include/mccnn.h has the definitions): Z = fx * baseline / (d + doffs) in the unit of
+    the baseline, +inf where the pixel has no depth."""
+    d, was_np = _dev(disparity_map)
+    return _ret(sd.depth(d, calib), was_np)
+
+
+def reproject(disparity_map, calib, max_depth=float("inf")):
+    """Not in the reference: the ordered point cloud of `disparity_map` under `calib`: float32 [n,4], one record (X, Y, Z,
+    the bits of the uint32 pixel index h * W + w) per pixel with a finite Z <= max_depth, in raster order.  Reads the
+    number of points back: one host synchronisation."""
+    d, was_np = _dev(disparity_map)
+    points, n = sd.reproject(d, calib, max_depth)
+    return _ret(points[:int(n.cpu().numpy().view(np.uint32)[0])], was_np)

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 import _hipabi as hip
+from calibration import Calibration
 from pair_result import PairResult
 from semi_dense_rule import SemiDenseRule  # noqa: F401  (host-only: match.py parses it before the GPU is pinned)
 
@@ -1577,6 +1578,82 @@ def semi_dense(disp, rule, status=None, planes=None, plane_names=(), out=None, s
     return speckle_filter(selected, rule.speckle[0], rule.speckle[1], out=out, sizes=sizes, scratch=scratch)[0]
 
 
+# ---- metric outputs: the depth plane and the ordered point cloud (include/mccnn.h has the definitions; csrc/reproject.hip)
+def depth(disp, calib, out=None):
+    """mccnn_depth: Z = f32(fx * baseline) / (disp + doffs) where disp is finite and the denominator positive, +inf
+    elsewhere.  calib: a calibration.Calibration or its text."""
+    who = "depth"
+    _check_map(disp, who)
+    H, W = disp.shape
+    _fx, _fy, _cx, _cy, fb, doffs = Calibration.parse(calib).scalars()
+    if out is None:
+        out = torch.empty_like(disp)
+    elif tuple(out.shape) != (H, W) or out.dtype != torch.float32:
+        raise ValueError("%s: `out` must be a float32 [%d,%d] tensor" % (who, H, W))
+    hip.check(hip.load().mccnn_depth(hip.ptr(disp), H, W, fb, doffs, hip.ptr(out), hip.stream()), "mccnn_depth")
+    return out
+
+
+def points_scratch(H, W, device):
+    """Scratch of one reproject() in flight (block counts and their totals): mccnn_points_scratch_bytes(H, W) bytes."""
+    nbytes = int(hip.load().mccnn_points_scratch_bytes(H, W))
+    if not nbytes:
+        raise ValueError("points_scratch: %d x %d is not a size the compaction takes (H*W <= 2^31 - 1)" % (H, W))
+    return torch.empty((nbytes // 4,), dtype=torch.int32, device=device)
+
+
+def reproject(disp, calib, max_depth=float("inf"), out=None, n_out=None, scratch=None):
+    """mccnn_reproject_points: -> (points, n_points).  points: float32 [H*W,4]; its first n_points records are the pixels
+    with a finite Z <= max_depth in raster order, (X, Y, Z, the bits of the uint32 h*W + w); the records behind them are
+    not written.  n_points: int32 [1] on the device (the bits are uint32): nothing is read back here.  `scratch`: a
+    points_scratch()."""
+    who = "reproject"
+    _check_map(disp, who)
+    H, W = disp.shape
+    fx, fy, cx, cy, fb, doffs = Calibration.parse(calib).scalars()
+    max_depth = _f32(max_depth)
+    if math.isnan(max_depth):
+        raise ValueError("%s: max_depth is NaN" % who)
+    if out is None:
+        out = torch.empty((H * W, 4), dtype=torch.float32, device=disp.device)
+    elif tuple(out.shape) != (H * W, 4) or out.dtype != torch.float32:
+        raise ValueError("%s: `out` must be a float32 [%d,4] tensor" % (who, H * W))
+    if n_out is None:
+        n_out = torch.empty((1,), dtype=torch.int32, device=disp.device)
+    elif tuple(n_out.shape) != (1,) or n_out.dtype != torch.int32:
+        raise ValueError("%s: `n_out` must be an int32 [1] tensor (the bits are uint32)" % who)
+    scratch = scratch if scratch is not None else points_scratch(H, W, disp.device)
+    hip.check(hip.load().mccnn_reproject_points(
+        hip.ptr(disp), H, W, fx, fy, cx, cy, fb, doffs, max_depth, hip.ptr(out), hip.ptr(n_out), hip.ptr(scratch),
+        scratch.numel() * scratch.element_size(), hip.stream()), "mccnn_reproject_points")
+    return out, n_out
+
+
+GEOMETRY_KEYS = ("calib", "depth", "points", "max_depth")
+
+
+def parse_geometry(geometry):
+    """StereoMatcher(geometry=...) -> dict(calib: Calibration or None, depth, points: bool, max_depth: float) or None.
+    Unknown keys, a request for neither output and a NaN max_depth are refused; the calibration may be handed in later
+    (set_calibration) but must be there when a pair is matched."""
+    if geometry is None:
+        return None
+    unknown = set(geometry) - set(GEOMETRY_KEYS)
+    if unknown:
+        raise ValueError("unknown geometry keys: %s" % sorted(unknown))
+    g = dict(calib=None, depth=False, points=False, max_depth=float("inf"))
+    g.update(geometry)
+    g["depth"], g["points"] = bool(g["depth"]), bool(g["points"])
+    if not (g["depth"] or g["points"]):
+        raise ValueError("geometry= asks for neither depth nor points")
+    g["max_depth"] = float(g["max_depth"])
+    if math.isnan(g["max_depth"]):
+        raise ValueError("geometry: max_depth is NaN")
+    if g["calib"] is not None:
+        g["calib"] = Calibration.parse(g["calib"])
+    return g
+
+
 def bilateral_table(filter_height, filter_width, mean, std_dev):
     """The reference's spatial kernel (pf:428-436, util.normal util.py:45-48): float64 evaluation, float32 storage."""
     constant1 = 1. / (np.sqrt(2 * np.pi) * std_dev)
@@ -1649,7 +1726,7 @@ def check_envelope(H, W, D):
 
 def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flight=1, arch="fast",
                     fc_units=DECISION_UNITS, confidence=0, views="left", semi_dense=False, vertical_offset=0,
-                    vertical_offset_max=4, vertical_offset_rows=8):
+                    vertical_offset_max=4, vertical_offset_rows=8, depth=False, points=False):
     """Device bytes StereoMatcher.workspace(H, W, D) allocates, times `pairs_in_flight` (match.py --pairs_in_flight:
     one matcher per pair in flight): four volumes of H*W*Dp*4 bytes (Dp = hwd_pitch(D)), the SGM scratch and the flag
     planes of the four directions, both support planes, the status and map planes, and - on pixel-major volumes with
@@ -1664,7 +1741,10 @@ def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flig
     the labelling scratch (mccnn_speckle_scratch_bytes) and a [H,W] size plane; False (default): none.
     vertical_offset, vertical_offset_max, vertical_offset_rows (the StereoMatcher extras of these names): with an offset
     other than 0 plus the offset (int32 [1]), the totals (int64 [2 max + 1]) and the votes (int32 [n_rows, ceil(W / 64),
-    2 max + 1]); 0 (default): none."""
+    2 max + 1]); 0 (default): none.
+    depth, points (StereoMatcher(geometry=dict(depth=..., points=...))): plus the [H,W] float32 depth plane; plus the
+    [H*W,4] float32 records, the compaction's scratch (mccnn_points_scratch_bytes) and the 4 bytes of their number; False
+    (default): none.  Left view only, whatever `views` is."""
     check_envelope(H, W, D)
     if views not in VIEWS:
         raise ValueError("views must be 'left' or 'both'")
@@ -1689,6 +1769,10 @@ def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flig
     if vertical_offset != 0:
         rows, blocks, nk = vertical_profile_shape(H, W, vertical_offset_max, vertical_offset_rows)
         n += 4 + 8 * nk + 4 * rows * blocks * nk
+    if depth:
+        n += H * W * 4
+    if points:
+        n += H * W * 16 + int(lib.mccnn_points_scratch_bytes(H, W)) + 4
     return n * max(1, int(pairs_in_flight))
 
 
@@ -1722,7 +1806,7 @@ class StereoMatcher(object):
     def __init__(self, net, hp=None, cv_mode=hip.MCCNN_CV_EXACT, cbca_order=hip.MCCNN_CBCA_REFERENCE_ORDER,
                  feature_tile_rows=None, extras=None, features="auto", layout="auto", cbca_kernel="auto",
                  on_saturation="fallback", skip_unit_regions=True, two_chains=True, free_chains=True, refresh_first=True,
-                 sgm_flags_once=True, decision="auto", confidence=(), views="left", semi_dense=None):
+                 sgm_flags_once=True, decision="auto", confidence=(), views="left", semi_dense=None, geometry=None):
         self.device = hip.require_device()
         self.net = net
         self.hp = dict(DEFAULT_HP)
@@ -1830,11 +1914,32 @@ class StereoMatcher(object):
             if missing:
                 raise ValueError("semi_dense=%r reads the confidence measure %s, which confidence=%r does not produce"
                                  % (self.semi_dense.describe(), ", ".join(missing), self.confidence))
+        # dict(calib=a Calibration or its text, depth=bool, points=bool, max_depth=float): the metric outputs of the LEFT
+        # view behind everything else on the pair's stream - the depth plane of the dense map (one launch) and / or the
+        # ordered point cloud (four launches) of the sparse map where the matcher has a semi-dense rule, of the dense one
+        # otherwise; every match entry returns them behind what it returns today: [, depth][, points, n_points].  The
+        # calibration is a launch argument: set_calibration() replaces it, and a captured graph is good for the
+        # calibration it was captured with (its key carries the scalars).  None (default): nothing changes - no launch,
+        # no buffer, the results as they were.
+        self.geometry = parse_geometry(geometry)
         self._ws = {}
         self._graphs = {}
         self._side = None
         self._right = None
         self._ingest = None
+
+    def set_calibration(self, calib):
+        """The calibration of the pairs that follow (a Calibration or its text): a launch argument of the metric outputs.
+        Graphs captured under another calibration stay resident for as long as the shape does and are replayed when that
+        calibration comes back; a new one is captured on its first match_graph*()."""
+        if self.geometry is None:
+            raise ValueError("set_calibration: this matcher has no geometry=")
+        self.geometry["calib"] = Calibration.parse(calib)
+
+    def _geometry_kw(self):
+        """The workspace_bytes keywords of this matcher's geometry=; empty without it."""
+        g = self.geometry
+        return dict(depth=g["depth"], points=g["points"]) if g is not None else {}
 
     def _check_vertical_range(self):
         r = self.extras["vertical_range"]
@@ -1924,7 +2029,7 @@ class StereoMatcher(object):
                                    arch="accurate" if self.accurate else "fast",
                                    fc_units=self.net.num_fc_units if self.accurate else DECISION_UNITS,
                                    confidence=len(self.confidence), views=self.views,
-                                   semi_dense=self.semi_dense is not None,
+                                   semi_dense=self.semi_dense is not None, **self._geometry_kw(),
                                    **{k: self.extras[k] for k in ("vertical_offset", "vertical_offset_max",
                                                                   "vertical_offset_rows") if self._vertical_offset_on()})
             self._ws, self._graphs = {}, {}          # one shape resident at a time: the previous one goes first
@@ -1956,6 +2061,12 @@ class StereoMatcher(object):
                 ws["semi_selected"] = torch.empty(lead + (H, W), dtype=torch.float32, device=dev)
                 ws["semi_sizes"] = torch.empty(lead + (H, W), dtype=torch.int32, device=dev)
                 ws["semi_scratch"] = [speckle_scratch(H, W, dev) for _ in range(2 if self.both else 1)]
+            if self.geometry is not None and self.geometry["depth"]:
+                ws["depth"] = torch.empty((H, W), dtype=torch.float32, device=dev)
+            if self.geometry is not None and self.geometry["points"]:
+                ws["points"] = torch.empty((H * W, 4), dtype=torch.float32, device=dev)
+                ws["n_points"] = torch.empty((1,), dtype=torch.int32, device=dev)
+                ws["points_scratch"] = points_scratch(H, W, dev)
             if self._vertical_offset_on():
                 v, R = self.extras["vertical_offset"], self.extras["vertical_offset_max"]
                 ws["v_offset"] = torch.full((1,), 0 if v == "auto" else v, dtype=torch.int32, device=dev)
@@ -1993,7 +2104,8 @@ class StereoMatcher(object):
 
     def result_of(self, value):
         """What a match entry of this matcher returned, as a PairResult: decoded by the matcher's own configuration."""
-        return PairResult.decode(value, bool(self.confidence), self.semi_dense is not None)
+        g = self.geometry or dict(depth=False, points=False)
+        return PairResult.decode(value, bool(self.confidence), self.semi_dense is not None, g["depth"], g["points"])
 
     def _saturated_pair(self, left_image, right_image, ndisp, given, keep=None):
         """on_saturation for the pair that has just been launched: None when its features were fine (or nobody is to
@@ -2014,13 +2126,15 @@ class StereoMatcher(object):
                                                extras=self.extras, features="miopen", layout=self.layout,
                                                cbca_kernel=self.cbca_kernel, on_saturation="ignore", decision="library",
                                                confidence=self.confidence, views=self.views,
-                                               semi_dense=self.semi_dense)
+                                               semi_dense=self.semi_dense, geometry=self.geometry)
+        if self.geometry is not None:
+            self._library_twin.geometry["calib"] = self.geometry["calib"]
         if keep is not None:
             keep.clear()
         return self._library_twin._match(left_image, right_image, ndisp, given, keep=keep)   # (it never repeats a pair)
 
     def match(self, left_image, right_image, ndisp, timer=_NO_TIMER, keep=None, _static_out=False, out=None,
-              confidence_out=None, semi_out=None):
+              confidence_out=None, semi_out=None, depth_out=None, points_out=None):
         """_match() + the on_saturation policy (class docstring): a pair whose hand-written features were clamped is
         matched again with the library convolutions unless the caller asked to be left alone.  With `keep` the stages
         handed out are those of the map that is returned: the repeated pair's where the pair was repeated.
@@ -2028,8 +2142,10 @@ class StereoMatcher(object):
         or `confidence_out` (a contiguous float32 [K,H,W] device tensor) where one is given, next to `out`.
         A matcher with a semi-dense rule returns the sparse map as the last element - (map, sparse) or (map, planes,
         sparse) - by the same rules, with `semi_out` (shaped like `out`) in the place of `confidence_out`.
+        A matcher with geometry= returns behind those the depth plane ([H,W]; `depth_out`) and / or the cloud's records and
+        their number ([H*W,4] float32 and int32 [1] on the device; `points_out` takes the records) - the left view's.
         (PairResult.public() is that shape; result_of() reads it back.)"""
-        given = PairResult(out, confidence_out, semi_out)
+        given = PairResult(out, confidence_out, semi_out, depth_out, points_out)
         res = self._match(left_image, right_image, ndisp, given, timer=timer, keep=keep, _static_out=_static_out)
         redo = None if _static_out else self._saturated_pair(left_image, right_image, ndisp, given, keep)
         return (res if redo is None else redo).public()
@@ -2307,12 +2423,13 @@ class StereoMatcher(object):
         if keep is not None:
             keep.update((name + v.suffix, t) for name, t in stages.items())
 
-    def _check_given(self, t, shape, name, dims, like):
+    def _check_given(self, t, shape, name, dims, like, both=None):
         """Refuses a caller's `out` / `confidence_out` that the last kernel of a view could not write."""
+        both = self.both if both is None else both
         if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous()
                               or t.device != like.device):
             raise ValueError("match: %s`%s` must be a contiguous float32 [%s%s] tensor on the images' device" % (
-                "with views='both' " if self.both else "", name, "2," if self.both else "", dims))
+                "with views='both' " if both else "", name, "2," if both else "", dims))
 
     @staticmethod
     def _hand_out(t, given, handed):
@@ -2401,6 +2518,18 @@ class StereoMatcher(object):
             if spare is not None or (both and name == "confidence_out"):
                 self._check_given(t, lead + shape, name, dims, L)
             res.append(dest(t, spare) if spare is not None else None)
+        # the metric outputs: the left view's, no leading axis (no keyword hands in the number of points: the workspace's,
+        # or a replayed graph's static word when its pair is repeated)
+        geo = self.geometry
+        if geo is not None:
+            if geo["calib"] is None:
+                raise ValueError("match: geometry= without a calibration (geometry=dict(calib=...) or set_calibration())")
+            for t, name, key, shape, dims in ((given.depth, "depth_out", "depth", (H, W), "H,W"),
+                                              (given.points, "points_out", "points", (H * W, 4), "H*W,4")):
+                if geo[key]:
+                    self._check_given(t, shape, name, dims, L, both=False)
+                res.append(dest(t, ws[key]) if geo[key] else None)
+            res.append(dest(given.n_points, ws["n_points"]) if geo["points"] else None)
         res = PairResult(*res)
         if semi:
             # the selection and the size plane, one [H,W] per view, and each view's labelling scratch
@@ -2429,6 +2558,20 @@ class StereoMatcher(object):
         view = PostView("left", "", L, dl, dr, left_volume, None if fresh else ws["status"], m[2:5], stream=main_s,
                         **results_of(0))
         self._post_view(view, D, pm, timer, keep)
+        if geo is not None:
+            # behind the left view's post-processing and semi-dense stage, on the pair's stream: the depth of the dense
+            # map, the cloud of the sparse map where there is one
+            left = res.view(0, both)
+            timer.start("geometry")
+            if geo["depth"]:
+                depth(left.map, geo["calib"], out=res.depth)
+            if geo["points"]:
+                reproject(left.sparse if semi else left.map, geo["calib"], geo["max_depth"], out=res.points,
+                          n_out=res.n_points, scratch=torch.empty_like(ws["points_scratch"]) if fresh else ws["points_scratch"])
+            timer.stop()
+            if fresh:
+                keep.update((k, t) for k, t in (("depth", res.depth), ("points", res.points), ("n_points", res.n_points))
+                            if t is not None)
         if fork:
             main_s.wait_stream(right_s)
         if fresh:
@@ -2447,7 +2590,8 @@ class StereoMatcher(object):
             self._ingest = b
         return b[1:]
 
-    def match_u8(self, left_u8, right_u8, ndisp, out=None, confidence_out=None, semi_out=None):
+    def match_u8(self, left_u8, right_u8, ndisp, out=None, confidence_out=None, semi_out=None, depth_out=None,
+                 points_out=None):
         """match() straight from the decoded bytes of the two PNGs: uint8 device tensors [H,W] or [H,W,C] (C = 1, 3, 4;
         see ingest_u8), or pinned host tensors, which are copied in stream order without blocking.  The standardisation runs on the device, bit-identical to match.py's on the host, so the map is
         what match() returns on the host-standardised images."""
@@ -2456,7 +2600,8 @@ class StereoMatcher(object):
         left_u8 = left_u8.to(self.device, non_blocking=True).contiguous()
         right_u8 = right_u8.to(self.device, non_blocking=True).contiguous()
         ingest_u8_pair(left_u8, right_u8, sl, sr, scratch)
-        return self.match(sl, sr, ndisp, out=out, confidence_out=confidence_out, semi_out=semi_out)
+        return self.match(sl, sr, ndisp, out=out, confidence_out=confidence_out, semi_out=semi_out, depth_out=depth_out,
+                          points_out=points_out)
 
     def _graph_key(self, key):
         """The key of a pair's captured graph.  An accurate network's graph holds the ADDRESS of the packed decision
@@ -2464,6 +2609,10 @@ class StereoMatcher(object):
         so its key carries the network's decision_weights_key(): after an optimiser step or a load_state the pair is
         captured again, and the graphs of the weights before are dropped (a replay of one would read the earlier
         weights' buffer, or memory the allocator has handed on).  The tower's weights are read in place and need none."""
+        if self.geometry is not None:
+            # the calibration and max_depth are launch arguments held by value: one graph per calibration of a shape
+            calib = self.geometry["calib"]
+            key = key + (("geometry", calib.scalars() if calib is not None else None, _f32(self.geometry["max_depth"])),)
         if not self.accurate:
             return key
         key = key + (self.net.decision_weights_key(),)
