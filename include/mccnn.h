@@ -166,6 +166,45 @@ int mccnn_vertical_offset_select(const uint32_t *votes, int n_rows, int n_blocks
 int mccnn_cost_volume_offset_hwd(const float *fl, const float *fr, int H, int W, int C, int D, const int32_t *row_offset,
                                  int vertical_range, float *lcv_hwd, float *rcv_hwd, mccnn_stream_t stream);
 
+/* ---- a FIELD of row offsets: one per cell of a coarse grid (not in the reference) ---------------------------------------
+ * One offset models a right camera that sits low; a rolled rig or two unequal focal lengths leave a residual that grows
+ * with the column or with the row and averages to nothing.  P(k; d,h,w), the maximum rule, the vote, the profiled rows
+ * h_i and the votes array are those above, untouched.
+ *
+ * Grid: gh x gw cells, 1 <= gh, gw <= 8, gh <= H, gw <= nb = ceil(W / 64).  Integer divisions throughout:
+ *   row band of image row h      h * gh / H
+ *   column band of column x      (x / 64) * gw / nb
+ * A cell that contains no profiled row has no votes.
+ *
+ * mccnn_vertical_field_select: votes as written by mccnn_vertical_profile for (H, row_step, R = max_offset); n_rows must
+ * be mccnn_vertical_profile_rows(H, row_step), n_blocks = nb.  All outputs are device buffers:
+ *   totals          uint64 [gh][gw][2R + 1]: totals[a][b][k + R] = the sum of votes[i][blk][k + R] over the profiled rows
+ *                   h_i of row band a and the blocks blk of column band b
+ *   field           int32 [gh][gw]: the winner of the cell's totals by the rule of the vote (candidates 0, -1, +1, ...,
+ *                   only a strictly greater total replaces); a cell without a single vote takes the global winner
+ *   offset, global_totals   int32, uint64 [2R + 1]: exactly what mccnn_vertical_offset_select returns for these votes
+ * One small launch, integer atomics only (deterministic), no allocation, no synchronisation: capturable.
+ * MCCNN_E_INVALID: a null pointer, max_offset outside [0, 8], row_step < 1, H <= 0, n_rows other than the profile's,
+ * n_blocks < 1, gh or gw outside [1, 8], gh > H, gw > n_blocks - each message names its argument.
+ *
+ * mccnn_cost_volume_field_hwd: the pixel-major volumes along the field.  field: DEVICE int32 [gh][gw], read by the kernel.
+ *   F(h, x)    = the word of field at (row band of h, column band of min(x, W - 1)), clamped to +-8 whatever it holds
+ *   S_L(d,h,w) = mccnn_cost_volume_offset_hwd's S_L with k0 = F(h, w)
+ *   S_R(d,h,w) = its S_R with k0 = F(h, w + d): the cell at the right pixel's own row and at the column of its left
+ *                partner, so that both views agree on which left column owns the offset
+ * vertical_range and the nearest-image-row rule are applied per entry; then the unchanged fill launch.  Pads are not
+ * written.  A field whose cells all hold k gives the bits of mccnn_cost_volume_offset_hwd with *row_offset = k at every
+ * range; a 1 x 1 grid is that call.  Refusals as for mccnn_cost_volume_offset_hwd (field must not be null), and
+ * MCCNN_E_INVALID for gh or gw outside [1, 8], gw > ceil(W / 64), gh > H; a refused call writes nothing.  Cost: per
+ * workgroup and disparity tile one product set for every candidate that one of the tile's entries selects - 2 (2r + 1)
+ * sets per pixel where the cells agree, more only along a cell border.  Capturable. */
+#define MCCNN_VERTICAL_FIELD_MAX 8
+int mccnn_vertical_field_select(const uint32_t *votes, int n_rows, int n_blocks, int H, int row_step, int max_offset, int gh,
+                                int gw, int32_t *field, uint64_t *totals, int32_t *offset, uint64_t *global_totals,
+                                mccnn_stream_t stream);
+int mccnn_cost_volume_field_hwd(const float *fl, const float *fr, int H, int W, int C, int D, const int32_t *field, int gh,
+                                int gw, int vertical_range, float *lcv_hwd, float *rcv_hwd, mccnn_stream_t stream);
+
 /* ---- a2 for the "accurate" network (Zbontar & LeCun 2016, sec. 3.2): the decision MLP on the matrix cores -----------
  * s(h,w,d) = sigmoid(wf . relu(W_n ... relu(W_2 . relu(aL[h,w] + aR[h,w-d]) + b_2) ... + b_n) + bf) for w >= d;
  * lcv = -s at (h,w,d), rcv = -s at (h,w-d,d); the border columns are filled by the same recurrences, the same kernels,

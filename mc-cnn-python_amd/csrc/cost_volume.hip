@@ -471,7 +471,34 @@ __device__ __forceinline__ void cvv_take(float *best, float s, bool first)
 // OFFSET (include/mccnn.h: mccnn_cost_volume_offset_hwd): the candidates lie around k0 = *row_offset clamped to +-8
 // instead of around 0 - only klo / khi differ; a row none of whose candidates lies inside the image takes the one
 // candidate nearest to k0 that does.  The search itself (OFFSET = false) is the kernel as it was.
-template <bool OFFSET>
+//
+// FIELD (include/mccnn.h: mccnn_cost_volume_field_hwd): the offset is a word of a gh x gw grid, F, chosen per ENTRY - by
+// the pixel's own column in the left view, by its partner's column w + d in the right view - so the entries of one score
+// tile may lie around different offsets.  The candidates of a disparity tile are then a SET (cvf_tile: the union, over
+// the at most three 64-column blocks the tile's entries choose from, of the candidates around each block's offset),
+// walked in ascending order like klo .. khi, and an entry's running maximum takes candidate k only where k is one of the
+// entry's own - its range is contiguous and part of the set, so it meets them in the definition's order.  A tile whose
+// blocks agree (nearly all of them) takes the comparisons of OFFSET: one range for every entry.  `vrange` carries the
+// grid: range | gh << 8 | gw << 16; `row_offset` is the field.  Every candidate of the set lies in [kmin, kmax] by
+// construction, whatever the field's words hold, so no row index leaves the image.
+struct cvf_tile_t {
+    unsigned mask;          // bit k + CVF_BIAS: candidate k is some entry's
+    int blo;                // the first block of image columns the tile's entries choose from
+    int f0, f1, f2;         // the clamped field words of blocks blo, blo + 1, blo + 2
+    int lo, hi;             // block blo's candidates: every entry's where `same`
+    int same;               // the blocks in use agree (an int: the struct has no padding to copy)
+};
+constexpr int CVF_BIAS = MCCNN_VERTICAL_OFFSET_MAX + MCCNN_VERTICAL_RANGE_MAX;
+
+// the candidates around offset f: k = f - r .. f + r inside [kmin, kmax], else the one nearest to f
+__device__ __forceinline__ void cvf_range(int f, int r, int kmin, int kmax, int &lo, int &hi)
+{
+    lo = max(f - r, kmin);
+    hi = min(f + r, kmax);
+    if (lo > hi) lo = hi = min(max(f, kmin), kmax);
+}
+
+template <bool OFFSET, bool FIELD = false>
 __global__ __launch_bounds__(256, 3) void cost_volume_vertical_kernel(const float *__restrict__ fl,
                                                                       const float *__restrict__ fr, int H, int W, int D,
                                                                       int vrange, float *__restrict__ lcv,
@@ -487,9 +514,51 @@ __global__ __launch_bounds__(256, 3) void cost_volume_vertical_kernel(const floa
     const int mir = right ? W - 1 : 0, sgn = right ? -1 : 1;   // image column of search column c: mir + sgn * c
     const int w0 = (int)blockIdx.x * CVP_TW - 1, h = blockIdx.y;   // lane 0: search column w0 (ghost)
     const int tid = threadIdx.x;
+    const int gh = FIELD ? (vrange >> 8) & 0xff : 1, gw = FIELD ? (vrange >> 16) & 0xff : 1;
+    if (FIELD) vrange &= 0xff;
     // the candidates k = klo .. khi, ascending: the other view's row h + sgn * k lies inside the image (k = 0 always does)
     int klo = right ? max(-vrange, h - (H - 1)) : max(-vrange, -h);
     int khi = right ? min(vrange, h) : min(vrange, H - 1 - h);
+    // FIELD: what disparity tile d0 of this workgroup meets.  Its entries (ww, d) - search column ww = w0 + 1 .. w0 + 63
+    // inside the image, d = d0 .. min(d0 + 63, D - 1), d <= ww - choose by image column ww (left view) or by the image
+    // column of search column ww - d (right view): an interval of at most 126 columns, three blocks.
+    const int nb = (W + 63) >> 6;
+    const int kmin = right ? h - (H - 1) : -h, kmax = right ? h : H - 1 - h;     // the k whose row is an image row
+    const int *const frow = FIELD ? row_offset + (h * gh / H) * gw : nullptr;     // the row band of h: gw words
+    auto cvf_tile = [&](int d0) {
+        cvf_tile_t t;
+        const int whi = min(w0 + CV_TW - 1, W - 1);
+        int clo = max(w0 + 1, d0), chi = whi;                                     // left view: the columns with an entry
+        if (right) {
+            clo = max(w0 + 1 - min(d0 + CV_DT - 1, D - 1), 0);
+            chi = whi - d0;
+        }
+        const int xlo = right ? W - 1 - chi : clo, xhi = right ? W - 1 - clo : chi;
+        t.blo = min(max(xlo, 0), W - 1) >> 6;
+        const int nblk = clo > chi ? 0 : (min(max(xhi, 0), W - 1) >> 6) - t.blo + 1;
+        t.mask = 0u;
+        t.same = 1;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int word = frow[min(t.blo + j, nb - 1) * gw / nb];
+            const int f = min(max(word, -MCCNN_VERTICAL_OFFSET_MAX), MCCNN_VERTICAL_OFFSET_MAX);   // any stored value is safe
+            int lo, hi;
+            cvf_range(f, vrange, kmin, kmax, lo, hi);
+            if (j == 0) {
+                t.f0 = f;
+                t.lo = lo;
+                t.hi = hi;
+            }
+            if (j == 1) t.f1 = f;
+            if (j == 2) t.f2 = f;
+            if (j < nblk) {
+                t.mask |= (2u << (hi + CVF_BIAS)) - (1u << (lo + CVF_BIAS));
+                t.same &= f == t.f0;
+            }
+        }
+        if (t.mask == 0u) t.mask = 1u << CVF_BIAS;      // no entry at all: k = 0 runs, nothing is kept or stored
+        return t;
+    };
     if (OFFSET) {
         const int k0 = min(max(*row_offset, -MCCNN_VERTICAL_OFFSET_MAX), MCCNN_VERTICAL_OFFSET_MAX);   // any stored value is safe
         const int kmin = right ? h - (H - 1) : -h, kmax = right ? h : H - 1 - h;     // the k whose row is an image row
@@ -497,6 +566,7 @@ __global__ __launch_bounds__(256, 3) void cost_volume_vertical_kernel(const floa
         khi = min(k0 + vrange, kmax);
         if (klo > khi) klo = khi = min(max(k0, kmin), kmax);
     }
+    if (FIELD) klo = __builtin_ctz(cvf_tile(0).mask) - CVF_BIAS;      // the first candidate of the first tile
     // the 16 bytes at channels 4 c4 .. of search column c (clamped: kept as it comes, never part of a stored score)
     auto at = [&](const float *f, int row, int c, int c4) {
         return reinterpret_cast<const cv_f4 *>(f + ((size_t)row * W + (mir + sgn * min(max(c, 0), W - 1))) * CV_C + c4 * 4);
@@ -548,6 +618,93 @@ __global__ __launch_bounds__(256, 3) void cost_volume_vertical_kernel(const floa
     const unsigned vo = (unsigned)((mir + sgn * (w0 + 1 + sub)) * Dp + q4) * 4u;
     char *const vrow = reinterpret_cast<char *>((right ? rcv : lcv) + (size_t)h * W * Dp);
     __syncthreads();
+    if constexpr (FIELD) {
+        // the search's loops over a SET of candidates per tile; an entry takes candidate k only where k is its own
+        cvf_tile_t cur = cvf_tile(0);                   // (klo: its first candidate - the prologue staged that row)
+#pragma unroll 1
+        for (int d0 = 0; d0 < D && w0 + CV_TW - 1 >= d0; d0 += CV_DT) {
+            const bool more = d0 + CV_DT < D && w0 + CV_TW - 1 >= d0 + CV_DT;
+            const cvf_tile_t nxt = more ? cvf_tile(d0 + CV_DT) : cur;     // (behind the last tile: fetched for nothing)
+#pragma unroll 1
+            for (unsigned m = cur.mask; m;) {           // ascending
+                const int k = __builtin_ctz(m) - CVF_BIAS;
+                m &= m - 1;
+                const bool last = m == 0u;
+                const int nd0 = last ? d0 + CV_DT : d0, nrow = h + sgn * (__builtin_ctz(last ? nxt.mask : m) - CVF_BIAS);
+                cv_f4 nx[4], ny[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int i = tid + q * 256;
+                    nx[q] = *at(fb, nrow, w0 - nd0 - (CV_DT - 1) + (i >> 4), i & 15);
+                }
+#pragma unroll 1
+                for (int kk = 0; kk < 8; ++kk) {
+                    const int dloc = dq * 16 + 2 * kk;                   // the even disparity of the pair (tile-relative)
+                    const int r = (w - d0 - dloc) & (RING - 1);          // ring row of search column w - d_even
+                    float s, sn;
+                    cvv_pair_scores(a, &sR[r * CV_LD], s, sn);
+                    const int d = d0 + dloc;
+                    int lo = cur.lo, hi = cur.hi, lon = lo, hin = hi;       // this entry's candidates, and d + 1's
+                    if (!cur.same) {                     // (uniform) the entries choose by their columns
+                        const int x = right ? W - 1 - (w - d) : w;
+                        const int b = min(max((x >> 6) - cur.blo, 0), 2);
+                        const int bn = right ? min(max(((x + 1) >> 6) - cur.blo, 0), 2) : b;    // its partner: one column on
+                        cvf_range(b == 0 ? cur.f0 : (b == 1 ? cur.f1 : cur.f2), vrange, kmin, kmax, lo, hi);
+                        cvf_range(bn == 0 ? cur.f0 : (bn == 1 ? cur.f1 : cur.f2), vrange, kmin, kmax, lon, hin);
+                    }
+                    if (wl >= 1 && w < W) {
+                        if (d < D && w >= d && k >= lo && k <= hi) cvv_take(&sT[wl * TP + dloc], s, k == lo);
+                        if (d + 1 < D && w >= d + 1 && k >= lon && k <= hin) cvv_take(&sT[wl * TP + dloc + 1], sn, k == lon);
+                    }
+                }
+                __syncthreads();                         // this candidate's products are done: the ring is free
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int i = tid + (q + 4) * 256;
+                    ny[q] = *at(fb, nrow, w0 - nd0 - (CV_DT - 1) + (i >> 4), i & 15);
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int i = tid + q * 256, x = w0 - nd0 - (CV_DT - 1) + (i >> 4);
+                    *reinterpret_cast<cv_f4 *>(&sR[(x & (RING - 1)) * CV_LD + (i & 15) * 4]) = nx[q];
+                }
+                if (last) {                            // the score tile holds the maxima: negate (pf:111-112) and store
+                    const int d = d0 + q4;               // the first disparity of this thread's quads
+                    unsigned rag = 0;
+                    cv_f4 v[4];
+                    int lim[4];                          // (worked out per tile: four registers less across the products)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int px = 1 + sub + 16 * j, ww = w0 + px;
+                        lim[j] = (px < CV_TW && ww < W) ? min(ww, dlast) : -1;
+                        v[j] = *reinterpret_cast<const cv_f4 *>(&sT[min(px, CV_TW - 1) * TP + q4]);
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const bool full = d + 3 <= lim[j];
+                        if (__builtin_expect(full, 1))
+                            cvp_store16(vrow + (vo + (unsigned)(d0 * 4 + sgn * j * 16 * Dp4)), -1.f * v[j]);
+                        rag |= (d <= lim[j] && !full) ? 1u << j : 0u;
+                    }
+                    for (unsigned m = rag; m; m &= m - 1) {
+                        const int j = __builtin_ctz(m), px = 1 + sub + 16 * j;
+                        float *dst = reinterpret_cast<float *>(vrow + (vo + (unsigned)(d0 * 4 + sgn * j * 16 * Dp4)));
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (d + e <= lim[j]) dst[e] = -1.f * sT[px * TP + q4 + e];
+                    }
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int i = tid + (q + 4) * 256, x = w0 - nd0 - (CV_DT - 1) + (i >> 4);
+                    *reinterpret_cast<cv_f4 *>(&sR[(x & (RING - 1)) * CV_LD + (i & 15) * 4]) = ny[q];
+                }
+                __syncthreads();                    // the ring holds the next candidate's rows, the score tile has been read
+            }
+            cur = nxt;
+        }
+        return;
+    }
 #pragma unroll 1
     for (int d0 = 0; d0 < D && w0 + CV_TW - 1 >= d0; d0 += CV_DT) {   // beyond: every (w, d) has w < d (border fill)
 #pragma unroll 1
@@ -800,6 +957,68 @@ __global__ __launch_bounds__(256) void vertical_offset_select_kernel(const unsig
         *offset = k0;
     }
     if ((int)threadIdx.x < nk) totals[threadIdx.x] = sT[threadIdx.x];
+}
+
+// The same selection per cell of a gh x gw grid (include/mccnn.h: mccnn_vertical_field_select): profiled row i belongs
+// to row band h_i gh / H, block blk to column band blk gw / n_blocks.  One workgroup; the cells' totals are summed in LDS
+// by integer atomics (at most 64 cells, 17 candidates each), so the result depends on no order; the whole image's are the
+// cells' sums.  A cell without a vote takes the whole image's winner, which is mccnn_vertical_offset_select's.
+__device__ __forceinline__ int cvp_winner(const unsigned long long *t, int R)
+{
+    unsigned long long best = t[R];
+    int k0 = 0;
+    for (int c = 1; c < 2 * R + 1; ++c) {
+        const int k = cvp_candidate(c);
+        if (t[k + R] > best) {
+            best = t[k + R];
+            k0 = k;
+        }
+    }
+    return k0;
+}
+
+__global__ __launch_bounds__(256) void vertical_field_select_kernel(const unsigned *__restrict__ votes, int n_rows,
+                                                                    int n_blocks, int H, int row_step, int R, int gh, int gw,
+                                                                    int *__restrict__ field,
+                                                                    unsigned long long *__restrict__ totals,
+                                                                    int *__restrict__ offset,
+                                                                    unsigned long long *__restrict__ global_totals)
+{
+    constexpr int NK = 2 * MCCNN_VERTICAL_OFFSET_MAX + 1, CELLS = MCCNN_VERTICAL_FIELD_MAX * MCCNN_VERTICAL_FIELD_MAX;
+    __shared__ unsigned long long sT[(CELLS + 1) * NK];       // [cell][k + R]; the last one: the whole image
+    __shared__ int sG;
+    const int nk = 2 * R + 1, cells = gh * gw, tid = threadIdx.x;
+    for (int i = tid; i < (cells + 1) * NK; i += 256) sT[i] = 0ull;
+    __syncthreads();
+    for (int v = tid; v < n_rows * n_blocks; v += 256) {
+        const int i = v / n_blocks, blk = v - i * n_blocks;
+        const long long hi = (long long)(row_step / 2) + (long long)i * row_step;                  // h_i < H
+        const int a = min(H < (1 << 27) ? (int)((unsigned)hi * (unsigned)gh / (unsigned)H) : (int)(hi * gh / H), gh - 1);
+        const int cell = a * gw + blk * gw / n_blocks;
+        unsigned n[NK];                          // the loads first, all in flight; then the cell's atomics
+#pragma unroll
+        for (int j = 0; j < NK; ++j) n[j] = j < nk ? votes[(size_t)v * nk + j] : 0u;
+#pragma unroll
+        for (int j = 0; j < NK; ++j)
+            if (n[j] != 0u) atomicAdd(&sT[cell * NK + j], (unsigned long long)n[j]);
+    }
+    __syncthreads();
+    if (tid < nk) {                              // the whole image: the sum of the cells, beside them (no contended word)
+        unsigned long long all = 0ull;
+        for (int c = 0; c < cells; ++c) all += sT[c * NK + tid];
+        sT[cells * NK + tid] = all;
+    }
+    __syncthreads();
+    if (tid == 0) sG = cvp_winner(&sT[cells * NK], R);
+    __syncthreads();
+    if (tid < cells) {
+        unsigned long long any = 0ull;
+        for (int j = 0; j < nk; ++j) any |= sT[tid * NK + j];
+        field[tid] = any != 0ull ? cvp_winner(&sT[tid * NK], R) : sG;
+    }
+    for (int i = tid; i < cells * nk; i += 256) totals[i] = sT[(i / nk) * NK + i % nk];
+    if (tid < nk) global_totals[tid] = sT[cells * NK + tid];
+    if (tid == 0) *offset = sG;
 }
 
 // ---- MFMA variant ---------------------------------------------------------------------------------------------
@@ -1428,6 +1647,70 @@ extern "C" int mccnn_vertical_offset_select(const uint32_t *votes, int n_rows, i
     hipLaunchKernelGGL(vertical_offset_select_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, votes, n_rows * n_blocks,
                        max_offset, offset, reinterpret_cast<unsigned long long *>(totals));
     return check_launch("mccnn_vertical_offset_select");
+}
+
+extern "C" int mccnn_vertical_field_select(const uint32_t *votes, int n_rows, int n_blocks, int H, int row_step,
+                                           int max_offset, int gh, int gw, int32_t *field, uint64_t *totals, int32_t *offset,
+                                           uint64_t *global_totals, mccnn_stream_t stream)
+{
+    using namespace mccnn;
+    MCCNN_REQUIRE(field && totals && offset && global_totals, MCCNN_E_INVALID, "mccnn_vertical_field_select: null pointer");
+    MCCNN_REQUIRE(max_offset >= 0 && max_offset <= MCCNN_VERTICAL_OFFSET_MAX, MCCNN_E_INVALID,
+                  "mccnn_vertical_field_select: max_offset=%d outside [0, %d]", max_offset, MCCNN_VERTICAL_OFFSET_MAX);
+    MCCNN_REQUIRE(H > 0, MCCNN_E_INVALID, "mccnn_vertical_field_select: H=%d is not positive", H);
+    MCCNN_REQUIRE(row_step >= 1, MCCNN_E_INVALID, "mccnn_vertical_field_select: row_step=%d < 1", row_step);
+    MCCNN_REQUIRE(n_rows == mccnn_vertical_profile_rows(H, row_step), MCCNN_E_INVALID,
+                  "mccnn_vertical_field_select: n_rows=%d, but H=%d at row_step=%d profiles %d rows", n_rows, H, row_step,
+                  mccnn_vertical_profile_rows(H, row_step));
+    MCCNN_REQUIRE(n_blocks >= 1 && (long)n_rows * n_blocks <= 0x7fffffffL, MCCNN_E_INVALID,
+                  "mccnn_vertical_field_select: %d rows x n_blocks=%d", n_rows, n_blocks);
+    MCCNN_REQUIRE(gh >= 1 && gh <= MCCNN_VERTICAL_FIELD_MAX, MCCNN_E_INVALID,
+                  "mccnn_vertical_field_select: gh=%d outside [1, %d]", gh, MCCNN_VERTICAL_FIELD_MAX);
+    MCCNN_REQUIRE(gw >= 1 && gw <= MCCNN_VERTICAL_FIELD_MAX, MCCNN_E_INVALID,
+                  "mccnn_vertical_field_select: gw=%d outside [1, %d]", gw, MCCNN_VERTICAL_FIELD_MAX);
+    MCCNN_REQUIRE(gh <= H, MCCNN_E_INVALID, "mccnn_vertical_field_select: gh=%d exceeds the H=%d rows", gh, H);
+    MCCNN_REQUIRE(gw <= n_blocks, MCCNN_E_INVALID, "mccnn_vertical_field_select: gw=%d exceeds the n_blocks=%d blocks", gw,
+                  n_blocks);
+    // (no profiled row: an empty array has no address - nothing is read, every cell takes 0)
+    MCCNN_REQUIRE(votes || n_rows == 0, MCCNN_E_INVALID, "mccnn_vertical_field_select: null pointer");
+    hipLaunchKernelGGL(vertical_field_select_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, votes, n_rows, n_blocks, H,
+                       row_step, max_offset, gh, gw, field, reinterpret_cast<unsigned long long *>(totals), offset,
+                       reinterpret_cast<unsigned long long *>(global_totals));
+    return check_launch("mccnn_vertical_field_select");
+}
+
+extern "C" int mccnn_cost_volume_field_hwd(const float *fl, const float *fr, int H, int W, int C, int D, const int32_t *field,
+                                           int gh, int gw, int vertical_range, float *lcv_hwd, float *rcv_hwd,
+                                           mccnn_stream_t stream)
+{
+    using namespace mccnn;
+    MCCNN_REQUIRE(fl && fr && field && lcv_hwd && rcv_hwd, MCCNN_E_INVALID, "mccnn_cost_volume_field_hwd: null pointer");
+    MCCNN_REQUIRE(vertical_range >= 0 && vertical_range <= MCCNN_VERTICAL_RANGE_MAX, MCCNN_E_INVALID,
+                  "mccnn_cost_volume_field_hwd: vertical_range=%d outside [0, %d]", vertical_range, MCCNN_VERTICAL_RANGE_MAX);
+    MCCNN_REQUIRE(H > 0 && W > 0, MCCNN_E_INVALID, "mccnn_cost_volume_field_hwd: non-positive size");
+    MCCNN_REQUIRE(C == CV_C, MCCNN_E_UNSUPPORTED, "mccnn_cost_volume_field_hwd: C=%d, kernels are built for 64 channels", C);
+    MCCNN_REQUIRE(D >= 2 && D <= 1024, MCCNN_E_UNSUPPORTED, "mccnn_cost_volume_field_hwd: D=%d outside [2, 1024]", D);
+    MCCNN_REQUIRE(D <= W - 2, MCCNN_E_UNSUPPORTED,
+                  "mccnn_cost_volume_field_hwd: D=%d needs W >= D+2 (the reference's border recurrence pf:106 is "
+                  "degenerate beyond that), W=%d", D, W);
+    MCCNN_REQUIRE(H <= 65535, MCCNN_E_UNSUPPORTED, "mccnn_cost_volume_field_hwd: H=%d > 65535 rows exceed the grid", H);
+    const int Dp = mccnn_hwd_pitch(D);
+    MCCNN_REQUIRE((size_t)W * Dp * 4 < ((size_t)1 << 31), MCCNN_E_UNSUPPORTED,
+                  "mccnn_cost_volume_field_hwd: a %d x %d row exceeds a buffer descriptor's reach", W, D);
+    MCCNN_REQUIRE(gh >= 1 && gh <= MCCNN_VERTICAL_FIELD_MAX, MCCNN_E_INVALID,
+                  "mccnn_cost_volume_field_hwd: gh=%d outside [1, %d]", gh, MCCNN_VERTICAL_FIELD_MAX);
+    MCCNN_REQUIRE(gw >= 1 && gw <= MCCNN_VERTICAL_FIELD_MAX, MCCNN_E_INVALID,
+                  "mccnn_cost_volume_field_hwd: gw=%d outside [1, %d]", gw, MCCNN_VERTICAL_FIELD_MAX);
+    MCCNN_REQUIRE(gh <= H, MCCNN_E_INVALID, "mccnn_cost_volume_field_hwd: gh=%d exceeds the H=%d rows", gh, H);
+    MCCNN_REQUIRE(gw <= cdiv(W, 64), MCCNN_E_INVALID, "mccnn_cost_volume_field_hwd: gw=%d exceeds the %d blocks of W=%d", gw,
+                  cdiv(W, 64), W);
+    hipStream_t s = (hipStream_t)stream;
+    // (the grid travels in the range's argument, so the shipped instantiations keep their signature and their code)
+    hipLaunchKernelGGL((cost_volume_vertical_kernel<false, true>), dim3(cdiv(W, CVP_TW), H, 2), dim3(256), 0, s, fl, fr, H, W,
+                       D, vertical_range | gh << 8 | gw << 16, lcv_hwd, rcv_hwd, Dp, (const int *)field);
+    int rc = check_launch("mccnn_cost_volume_field_hwd");
+    if (rc) return rc;
+    return launch_cost_volume_fill_hwd(lcv_hwd, rcv_hwd, D, Dp, H, W, s, "mccnn_cost_volume_field_hwd(fill)");
 }
 
 extern "C" int mccnn_cost_volume_fill(float *lcv, float *rcv, int D, int H, int W, int pixel_major, mccnn_stream_t stream)

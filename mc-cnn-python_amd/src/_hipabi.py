@@ -50,6 +50,8 @@ SIGNATURES = {
     "mccnn_vertical_profile": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "mccnn_vertical_offset_select": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "mccnn_cost_volume_offset_hwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "mccnn_vertical_field_select": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mccnn_cost_volume_field_hwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "mccnn_cost_volume_fill": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "mccnn_decision_pack_bytes": (_sz, [_i, _i, _i]),
     "mccnn_decision_pack": (_i, [_vp, _i, _i, _f, _i, _vp, _vp]),

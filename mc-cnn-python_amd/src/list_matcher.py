@@ -267,8 +267,8 @@ def make_writer(rank=0, log=print, scorer=None, eval_file="evalMCCNN.json", save
     the map these files hold, or of the repeat that replaces it), once its bytes are on the host.  `save(result, paths)`
     writes what the PairResult of host arrays holds: the map and its preview (datasets.py: a KITTI layout's is the 16-bit
     plane), the planes (--confidence) and the sparse map (--semi_dense) - a repeated pair's files get the repeated
-    pair's.  `save_vertical(offset, totals, paths)` (match.py --vertical_offset auto) writes the measured row offset of a
-    pair whose ticket brought one."""
+    pair's.  `save_vertical(offset, totals, paths[, field, cell_totals])` (match.py --vertical_offset auto | grid) writes
+    the measured row offset, and the field, of a pair whose ticket brought them."""
     from datetime import datetime
 
     def write(job, result, seconds):
@@ -276,7 +276,7 @@ def make_writer(rank=0, log=print, scorer=None, eval_file="evalMCCNN.json", save
         save(result, p)
         vertical = getattr(job, "vertical", None)
         if save_vertical is not None and vertical is not None:
-            save_vertical(vertical[0].numpy(), vertical[1].numpy(), p)
+            save_vertical(vertical[0].numpy(), vertical[1].numpy(), p, *(v.numpy() for v in vertical[2:]))
         util.saveTimeFile(seconds, p["out_time"])
         log("[{}] {}: {:.3f} s -> {}".format(rank, datetime.now(), seconds, p["out"]))
         if scorer is not None and job.scored is not None:

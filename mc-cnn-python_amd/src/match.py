@@ -24,6 +24,8 @@ mask1nocc.png) and every evaluation file gains a "right" block.  Middlebury layo
 exactly on the device, and the list's pooled quantiles at 16 bits, in all three loops.  Middlebury layout only.
 --vertical_offset auto|N matches a pair whose right image sits N rows low along that offset; auto measures N per pair on
 the device and writes verticalMCCNN.json beside disp0MCCNN.pfm, the same bytes in all three loops.
+--vertical_offset grid measures one offset per cell of --vertical_offset_grid GHxGW cells instead (a rolled rig, unequal
+focal lengths); verticalMCCNN.json then also carries grid, offsets, cell_totals and cell_shares.
 --depth writes the left view's depth plane, depth0MCCNN.pfm, and --point_cloud [--max_depth Z] its ordered point cloud,
 points0MCCNN.ply, beside disp0MCCNN.pfm from the pair's calib.txt (cam0, doffs, baseline; --calib overrides it), computed
 on the device behind the map, the same bytes in all three loops.  Middlebury layout only.
@@ -139,13 +141,18 @@ parser.add_argument("--vertical_range", type=int, default=0,
                          "unchanged.  0 (default): the reference's row-to-row comparison.  Costs a point or two on "
                          "well-rectified pairs and 4 x range + 2 times the cost volume's products; bit-exact fast "
                          "network only: not with --fast, --separable_cbca, --paper_support_regions or --arch accurate")
-parser.add_argument("--vertical_offset", type=str, default="0", metavar="auto|N",
+parser.add_argument("--vertical_offset", type=str, default="0", metavar="auto|grid|N",
                     help="for pairs whose right image sits N rows low (N in -8 .. 8): the cost volume is taken against row "
                          "h + N of the other view (include/mccnn.h: mccnn_cost_volume_offset_hwd), --vertical_range "
                          "searched around it.  'auto': N is measured per pair on the device from the pair's features "
                          "(mccnn_vertical_profile) and written to verticalMCCNN.json beside the map (a KITTI --dataset: "
-                         "submit_<tag>/vertical/NNNNNN_10.json).  0 (default): nothing changes.  Available where "
-                         "--vertical_range is")
+                         "submit_<tag>/vertical/NNNNNN_10.json).  'grid': one N per cell of --vertical_offset_grid, measured "
+                         "the same way, for a residual that grows with the column or the row and averages to nothing "
+                         "(mccnn_vertical_field_select, mccnn_cost_volume_field_hwd).  0 (default): nothing changes.  "
+                         "Available where --vertical_range is")
+parser.add_argument("--vertical_offset_grid", type=str, default="3x4", metavar="GHxGW",
+                    help="--vertical_offset grid: the cells down and across (1 .. 8 each); clamped per pair to the image's "
+                         "64-column blocks and to row bands of at least 8 measured rows, and written back as 'grid'")
 parser.add_argument("--vertical_offset_max", type=int, default=4,
                     help="--vertical_offset auto: the largest offset that is measured, in rows either way (1 .. 8)")
 parser.add_argument("--vertical_offset_rows", type=int, default=8,
@@ -258,14 +265,23 @@ out_eval_file = datasets.Middlebury.out_eval_file
 
 
 def parse_vertical_offset(text):
-    """--vertical_offset: "auto", or an integer in [-8, 8]; None for anything else."""
-    if text == "auto":
-        return "auto"
+    """--vertical_offset: "auto", "grid", or an integer in [-8, 8]; None for anything else."""
+    if text in ("auto", "grid"):
+        return text
     try:
         value = int(text)
     except ValueError:
         return None
     return value if -8 <= value <= 8 else None
+
+
+def parse_vertical_offset_grid(text):
+    """--vertical_offset_grid: "GHxGW" with both in [1, 8] as (gh, gw); None for anything else."""
+    try:
+        grid = tuple(int(p) for p in text.lower().split("x"))
+    except ValueError:
+        return None
+    return grid if len(grid) == 2 and all(1 <= g <= 8 for g in grid) else None
 
 
 def hyper_parameters(args):
@@ -287,8 +303,9 @@ class ListLoop(object):
     and, with --pairs_in_flight N > 1, one stream per slot) and writes its files when the slot comes round again.
 
     layout: datasets.py; redo: stereo_device.SaturationRedo; scorer: evaluation.ListScorer or None (--evaluate);
-    save(PairResult of host arrays, paths): the files of what crossed to the host; save_vertical(offset, totals, paths)
-    (--vertical_offset auto): the file of the pair's measured row offset, copied out behind the pair on its stream."""
+    save(PairResult of host arrays, paths): the files of what crossed to the host; save_vertical(offset, totals, paths[,
+    field, cell_totals]) (--vertical_offset auto | grid): the file of the pair's measured row offset, copied out behind
+    the pair on its stream."""
 
     def __init__(self, layout, matchers, streams, redo, scorer, save, rank, save_vertical=None, calibration=None):
         import torch
@@ -358,7 +375,7 @@ class ListLoop(object):
         seconds = time.time() - p.started
         self.save(host, p.paths)
         if vertical is not None:
-            self.save_vertical(vertical[0], vertical[1], p.paths)
+            self.save_vertical(vertical[0], vertical[1], p.paths, *vertical[2:])
         util.saveTimeFile(seconds, p.paths["out_time"])
         print("[{}] {}: {:.3f} s -> {}".format(self.rank, datetime.now(), seconds, p.paths["out"]))
         if p.scored is not None:
@@ -428,7 +445,10 @@ def main(argv=None):
                 parser.error("--vertical_range is not available with %s: %s" % (flag, why))
     vertical_offset = parse_vertical_offset(args.vertical_offset)
     if vertical_offset is None:
-        parser.error("--vertical_offset: %r is neither 'auto' nor an integer in [-8, 8]" % args.vertical_offset)
+        parser.error("--vertical_offset: %r is neither 'auto' nor an integer in [-8, 8], nor 'grid'" % args.vertical_offset)
+    vertical_grid = parse_vertical_offset_grid(args.vertical_offset_grid)
+    if vertical_grid is None:
+        parser.error("--vertical_offset_grid: %r is not GHxGW with both in [1, 8]" % args.vertical_offset_grid)
     if not 1 <= args.vertical_offset_max <= 8:
         parser.error("--vertical_offset_max: %d outside [1, 8]" % args.vertical_offset_max)
     if args.vertical_offset_rows < 1:
@@ -554,11 +574,15 @@ def main(argv=None):
     # --vertical_offset: the extras and the workspace keywords of the same names; nothing without the flag
     vertical_kw = dict(vertical_offset=vertical_offset, vertical_offset_max=args.vertical_offset_max,
                        vertical_offset_rows=args.vertical_offset_rows) if vertical_offset != 0 else {}
+    if vertical_offset == "grid":
+        vertical_kw["vertical_offset_grid"] = vertical_grid
+    measured = vertical_offset in ("auto", "grid")      # the pair's measurement crosses and is written
 
-    def save_vertical(offset, totals, out):
-        """--vertical_offset auto: the pair's measurement (host arrays) as verticalMCCNN.json."""
-        record = dict(sd.vertical_record(offset, totals), max_offset=args.vertical_offset_max,
-                      row_step=args.vertical_offset_rows)
+    def save_vertical(offset, totals, out, field=None, cell_totals=None):
+        """--vertical_offset auto | grid: the pair's measurement (host arrays) as verticalMCCNN.json."""
+        record = sd.vertical_record(offset, totals) if field is None \
+            else sd.vertical_field_record(offset, totals, field, cell_totals)
+        record = dict(record, max_offset=args.vertical_offset_max, row_step=args.vertical_offset_rows)
         path = layout.vertical_path(out)
         util.recurMk(os.path.abspath(os.path.dirname(path)))
         with open(path, "w") as f:
@@ -651,7 +675,7 @@ def main(argv=None):
     if args.pipeline:
         backend = list_matcher.MatcherBackend(matchers, streams, make_library_matcher, rank=rank, scorer=scorer,
                                               device_output=layout.device_output if layout.kitti else None,
-                                              vertical=vertical_offset == "auto")
+                                              vertical=measured)
         # (--depth / --point_cloud: the calibration joins the job's key - a graph is good for the calibration it was
         # captured with, so a pair is replayed only where shape AND calibration repeat; Middlebury's differ pair by pair)
         # a KITTI frame's size is its decoded left image's: the capture policy sees every change through the job's key
@@ -661,7 +685,7 @@ def main(argv=None):
             truth_right=layout.load_truth_right if (args.evaluate and both) else None,
             calibration=calibration if geometry is not None else None)
         writer = list_matcher.make_writer(rank, scorer=scorer, eval_file=out_eval_file, save=save,
-                                          save_vertical=save_vertical if vertical_offset == "auto" else None)
+                                          save_vertical=save_vertical if measured else None)
         pipeline = list_matcher.ListPipeline(reader, backend, writer, slots=in_flight, readers=args.readers)
         try:
             pipeline.run(indices)
@@ -669,7 +693,7 @@ def main(argv=None):
             print("[{}] {}".format(rank, pipeline.summary()))
     else:
         loop = ListLoop(layout, matchers, streams, sd.SaturationRedo(matchers, make_library_matcher), scorer, save, rank,
-                        save_vertical=save_vertical if vertical_offset == "auto" else None,
+                        save_vertical=save_vertical if measured else None,
                         calibration=calibration if geometry is not None else None)
         loop.run(indices, paths, lambda left_path: layout.shape(left_path, ndisp_flag), footprint)
     if scorer is not None:

@@ -33,6 +33,10 @@ Opt-in departures from the reference's results (defaults reproduce it):
     VERTICAL_OFFSET          0 | -8 .. 8   - compute_cost_volume along a row offset: the volumes against row h + offset of
                                              the other view, VERTICAL_RANGE searched around it (include/mccnn.h:
                                              mccnn_cost_volume_offset_hwd; "exact" mode); vertical_profile() measures it
+                             | "grid"      - ... along a field of offsets, one per cell of VERTICAL_OFFSET_GRID = (gh, gw)
+                                             cells (clamped per shape), measured from the pair's own features at
+                                             VERTICAL_OFFSET_PROFILE = (max_offset, row_step) (include/mccnn.h:
+                                             mccnn_vertical_field_select, mccnn_cost_volume_field_hwd)
     NUMPY1_PROMOTION         False | True  - sub-pixel formula evaluated as NumPy < 2 promotes its scalars (float64,
                                              rounded once): what the reference's own Python 2.7 + NumPy 1.14 computes;
                                              the default is NumPy >= 2's float32 chain, which the golden vectors pin
@@ -57,6 +61,8 @@ NUMPY1_PROMOTION = False
 SGM_INDEPENDENT_DIRECTIONS = False
 VERTICAL_RANGE = 0
 VERTICAL_OFFSET = 0
+VERTICAL_OFFSET_GRID = (3, 4)
+VERTICAL_OFFSET_PROFILE = (4, 8)
 
 _CV_MODES = {"exact": hip.MCCNN_CV_EXACT, "mfma": hip.MCCNN_CV_MFMA}
 _CBCA_ORDERS = {"separable": hip.MCCNN_CBCA_SEPARABLE, "reference": hip.MCCNN_CBCA_REFERENCE_ORDER,
@@ -123,6 +129,15 @@ def compute_cost_volume(featuresl, featuresr, ndisp):
     """pf:78-113."""
     fl, was_np = _dev(featuresl)
     fr, _ = _dev(featuresr)
+    if VERTICAL_OFFSET == "grid":
+        if COST_VOLUME_MODE != "exact":
+            raise ValueError("VERTICAL_OFFSET='grid': the row offset exists for COST_VOLUME_MODE 'exact' only")
+        R, step = (int(v) for v in VERTICAL_OFFSET_PROFILE)
+        grid = sd.vertical_field_grid(fl.shape[0], fl.shape[1], VERTICAL_OFFSET_GRID, step)
+        votes = sd.vertical_profile(fl, fr, int(ndisp), R, step)
+        field = sd.vertical_field_select(votes, fl.shape[0], step, R, grid)[0]
+        hl, hr = sd.cost_volume_field_hwd(fl, fr, int(ndisp), field, VERTICAL_RANGE)
+        return _ret(sd.hwd_to_dhw(hl, int(ndisp)), was_np), _ret(sd.hwd_to_dhw(hr, int(ndisp)), was_np)
     if VERTICAL_OFFSET:
         if isinstance(VERTICAL_OFFSET, bool) or not isinstance(VERTICAL_OFFSET, int) \
                 or abs(VERTICAL_OFFSET) > sd.VERTICAL_OFFSET_MAX:

@@ -278,6 +278,87 @@ def cost_volume_offset_hwd(fl, fr, ndisp, row_offset, vertical_range, out=None):
     return lcv, rcv
 
 
+VERTICAL_FIELD_MAX = 8         # mccnn_vertical_field_select, mccnn_cost_volume_field_hwd: cells either way
+VERTICAL_FIELD_MIN_ROWS = 8    # vertical_field_grid: profiled rows a row band keeps at least
+
+
+def vertical_field_grid(H, W, grid, row_step):
+    """The (gh, gw) a requested grid becomes for an H x W pair profiled on every row_step-th row: gw at most the
+    ceil(W / 64) vote blocks, gh at most n_rows // 8 so that a row band holds at least 8 profiled rows (cells of a few
+    hundred votes select noise), either at least 1."""
+    gh, gw = (int(g) for g in grid)
+    rows, blocks, _ = vertical_profile_shape(H, W, 0, row_step)
+    return max(1, min(gh, rows // VERTICAL_FIELD_MIN_ROWS)), max(1, min(gw, blocks))
+
+
+def vertical_field_record(offset, totals, field, cell_totals):
+    """vertical_record's {offset, totals, share} of the whole image plus the field's: grid [gh, gw], offsets [gh][gw],
+    cell_totals [gh][gw][2 max + 1] and cell_shares [gh][gw] (the winner's share of its cell's votes; 0.0 for a cell
+    without votes, which holds the global offset)."""
+    field = np.asarray(field)
+    cells = np.asarray(cell_totals).reshape(field.shape + (-1,))
+    record = vertical_record(offset, totals)
+    R = (cells.shape[2] - 1) // 2
+    shares = []
+    for a in range(field.shape[0]):
+        shares.append([])
+        for b in range(field.shape[1]):
+            n, k = int(cells[a, b].sum()), int(field[a, b]) + R
+            shares[a].append(float(int(cells[a, b, k])) / n if n and 0 <= k < cells.shape[2] else 0.0)
+    record.update(grid=[int(field.shape[0]), int(field.shape[1])], offsets=[[int(v) for v in row] for row in field],
+                  cell_totals=[[[int(v) for v in cell] for cell in row] for row in cells], cell_shares=shares)
+    return record
+
+
+def vertical_field_select(votes, H, row_step, max_offset, grid, out=None):
+    """(field int32 [gh, gw], cell totals int64 [gh, gw, 2 max_offset + 1], offset int32 [1], totals int64 [2 max_offset
+    + 1]) of the votes vertical_profile wrote for an image of H rows at this row_step, on the device
+    (mccnn_vertical_field_select): per cell of the grid the offset with the most votes, by vertical_offset_select's rule;
+    a cell without votes takes the whole image's, which with its totals is what vertical_offset_select returns."""
+    nk = 2 * int(max_offset) + 1
+    gh, gw = (int(g) for g in grid)
+    if out is None:
+        if not (1 <= gh <= VERTICAL_FIELD_MAX and 1 <= gw <= VERTICAL_FIELD_MAX):      # (the shapes below need them sane)
+            raise ValueError("vertical_field_select: grid %dx%d outside [1, %d]" % (gh, gw, VERTICAL_FIELD_MAX))
+        field = torch.empty((gh, gw), dtype=torch.int32, device=votes.device)
+        cells = torch.empty((gh, gw, nk), dtype=torch.int64, device=votes.device)
+        offset = torch.empty((1,), dtype=torch.int32, device=votes.device)
+        totals = torch.empty((nk,), dtype=torch.int64, device=votes.device)
+    else:
+        field, cells, offset, totals = out
+    if votes.dim() != 3 or votes.shape[2] != nk or totals.numel() < nk or field.numel() < gh * gw \
+            or cells.numel() < gh * gw * nk:
+        raise ValueError("vertical_field_select: votes %s / field %s / totals %s, %s do not belong to max_offset=%d and a "
+                         "%dx%d grid" % (tuple(votes.shape), tuple(field.shape), tuple(cells.shape), tuple(totals.shape),
+                                         int(max_offset), gh, gw))
+    hip.check(hip.load().mccnn_vertical_field_select(hip.ptr(votes) if votes.numel() else None, int(votes.shape[0]),
+                                                     int(votes.shape[1]), int(H), int(row_step), int(max_offset), gh, gw,
+                                                     hip.ptr(field), hip.ptr(cells), hip.ptr(offset), hip.ptr(totals),
+                                                     hip.stream()),
+              "mccnn_vertical_field_select")
+    return field, cells, offset, totals
+
+
+def cost_volume_field_hwd(fl, fr, ndisp, field, vertical_range, out=None):
+    """The bit-exact pixel-major volumes [H,W,Dp] taken along a field of row offsets (include/mccnn.h:
+    mccnn_cost_volume_field_hwd): field is a device int32 tensor [gh, gw] the kernel reads (every word clamped to +-8); a
+    left pixel takes the word of its own cell, a right pixel that of its row band and of its left partner's column."""
+    H, W, C = fl.shape
+    dp = hwd_pitch(ndisp)
+    if out is None:
+        lcv = torch.zeros((H, W, dp), dtype=torch.float32, device=fl.device)
+        rcv = torch.zeros((H, W, dp), dtype=torch.float32, device=fl.device)
+    else:
+        lcv, rcv = out
+    if field is None or field.dtype != torch.int32 or field.dim() != 2 or not field.is_contiguous():
+        raise ValueError("cost_volume_field_hwd: field must be a contiguous device int32 tensor [gh, gw]")
+    hip.check(hip.load().mccnn_cost_volume_field_hwd(hip.ptr(fl), hip.ptr(fr), H, W, C, int(ndisp), hip.ptr(field),
+                                                     int(field.shape[0]), int(field.shape[1]), int(vertical_range),
+                                                     hip.ptr(lcv), hip.ptr(rcv), hip.stream()),
+              "mccnn_cost_volume_field_hwd")
+    return lcv, rcv
+
+
 # ---- a2 for the accurate network: the decision MLP per (pixel, disparity) ------------------------------------------
 DECISION_UNITS = 384                     # csrc/decision_mfma.hip
 DECISION_MAPS = (64, 112)
@@ -1726,7 +1807,7 @@ def check_envelope(H, W, D):
 
 def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flight=1, arch="fast",
                     fc_units=DECISION_UNITS, confidence=0, views="left", semi_dense=False, vertical_offset=0,
-                    vertical_offset_max=4, vertical_offset_rows=8, depth=False, points=False):
+                    vertical_offset_max=4, vertical_offset_rows=8, depth=False, points=False, vertical_offset_grid=(3, 4)):
     """Device bytes StereoMatcher.workspace(H, W, D) allocates, times `pairs_in_flight` (match.py --pairs_in_flight:
     one matcher per pair in flight): four volumes of H*W*Dp*4 bytes (Dp = hwd_pitch(D)), the SGM scratch and the flag
     planes of the four directions, both support planes, the status and map planes, and - on pixel-major volumes with
@@ -1741,7 +1822,8 @@ def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flig
     the labelling scratch (mccnn_speckle_scratch_bytes) and a [H,W] size plane; False (default): none.
     vertical_offset, vertical_offset_max, vertical_offset_rows (the StereoMatcher extras of these names): with an offset
     other than 0 plus the offset (int32 [1]), the totals (int64 [2 max + 1]) and the votes (int32 [n_rows, ceil(W / 64),
-    2 max + 1]); 0 (default): none.
+    2 max + 1]); 0 (default): none.  vertical_offset="grid" with vertical_offset_grid=(gh, gw): plus the field (int32) and
+    the cells' totals (int64 [2 max + 1] each) of the grid as vertical_field_grid clamps it for this shape.
     depth, points (StereoMatcher(geometry=dict(depth=..., points=...))): plus the [H,W] float32 depth plane; plus the
     [H*W,4] float32 records, the compaction's scratch (mccnn_points_scratch_bytes) and the 4 bytes of their number; False
     (default): none.  Left view only, whatever `views` is."""
@@ -1769,6 +1851,9 @@ def workspace_bytes(H, W, D, pixel_major=True, cbca_kernel="auto", pairs_in_flig
     if vertical_offset != 0:
         rows, blocks, nk = vertical_profile_shape(H, W, vertical_offset_max, vertical_offset_rows)
         n += 4 + 8 * nk + 4 * rows * blocks * nk
+        if vertical_offset == "grid":
+            gh, gw = vertical_field_grid(H, W, vertical_offset_grid, vertical_offset_rows)
+            n += gh * gw * (4 + 8 * nk)
     if depth:
         n += H * W * 4
     if points:
@@ -1876,7 +1961,8 @@ class StereoMatcher(object):
         # (sgm_average_independent_hwd) - instead of the reference's four passes composed on one array
         self.extras = dict(both_view_support=False, interpolation_directions=4, occlusion_from_left=False,
                            numpy1_promotion=False, sgm_independent_directions=False, vertical_range=0,
-                           vertical_offset=0, vertical_offset_max=4, vertical_offset_rows=8)
+                           vertical_offset=0, vertical_offset_max=4, vertical_offset_rows=8,
+                           vertical_offset_grid=(3, 4))
         if extras:
             unknown = set(extras) - set(self.extras)
             if unknown:
@@ -1891,6 +1977,9 @@ class StereoMatcher(object):
         # pair's stream (vertical_profile of +-vertical_offset_max rows on every vertical_offset_rows-th row ->
         # vertical_offset_select -> the volume; no host round trip, capturable); vertical_report() reads the measurement
         # back.  0 (default): nothing changes - no launch, no buffer.  Refused where vertical_range > 0 is.
+        # "grid": one offset per cell of vertical_offset_grid = (gh, gw) cells, clamped per shape (vertical_field_grid),
+        # for a rolled rig or unequal focal lengths, whose residual averages to nothing: vertical_profile ->
+        # vertical_field_select -> cost_volume_field_hwd, on the pair's stream like "auto".
         self._check_vertical_offset()
         # confidence measures of the returned map (CONFIDENCE_MEASURES; names in any order, planes in that order): one
         # more launch per pair behind the post-processing, and every match entry returns (map, planes [K,H,W]).
@@ -1958,9 +2047,14 @@ class StereoMatcher(object):
 
     def _check_vertical_offset(self):
         v, R, step = (self.extras[k] for k in ("vertical_offset", "vertical_offset_max", "vertical_offset_rows"))
-        if v != "auto" and (isinstance(v, bool) or not isinstance(v, int) or abs(v) > VERTICAL_OFFSET_MAX):
-            raise ValueError("vertical_offset must be 'auto' or an integer in [-%d, %d], not %r"
+        if v not in ("auto", "grid") and (isinstance(v, bool) or not isinstance(v, int) or abs(v) > VERTICAL_OFFSET_MAX):
+            raise ValueError("vertical_offset must be 'auto' or an integer in [-%d, %d] (or 'grid'), not %r"
                              % (VERTICAL_OFFSET_MAX, VERTICAL_OFFSET_MAX, v))
+        grid = self.extras["vertical_offset_grid"]
+        if not isinstance(grid, (tuple, list)) or len(grid) != 2 or any(
+                isinstance(g, bool) or not isinstance(g, int) or not 1 <= g <= VERTICAL_FIELD_MAX for g in grid):
+            raise ValueError("vertical_offset_grid must be two integers (gh, gw) in [1, %d], not %r"
+                             % (VERTICAL_FIELD_MAX, grid))
         if isinstance(R, bool) or not isinstance(R, int) or not 1 <= R <= VERTICAL_OFFSET_MAX:
             raise ValueError("vertical_offset_max must be an integer in [1, %d], not %r" % (VERTICAL_OFFSET_MAX, R))
         if isinstance(step, bool) or not isinstance(step, int) or step < 1:
@@ -1979,22 +2073,39 @@ class StereoMatcher(object):
     def _vertical_offset_on(self):
         return self.extras["vertical_offset"] != 0
 
+    def _vertical_field_on(self):
+        return self.extras["vertical_offset"] == "grid"
+
+    def vertical_grid(self, H, W):
+        """The (gh, gw) cells vertical_offset="grid" uses for an H x W pair: vertical_offset_grid as vertical_field_grid
+        clamps it for the shape."""
+        return vertical_field_grid(H, W, self.extras["vertical_offset_grid"], self.extras["vertical_offset_rows"])
+
     def vertical_report(self, H, W, D):
         """The row offset the last pair on the workspace of this shape was matched along: {offset, totals, share} -
         the offset, the votes per candidate -max .. +max and the winner's share of them (an integer vertical_offset has
-        no votes: zeros and 0.0).  Synchronises the device; never call it inside a capture."""
+        no votes: zeros and 0.0).  vertical_offset="grid": plus grid [gh, gw] (as clamped for the shape), offsets
+        [gh][gw], cell_totals and cell_shares (vertical_field_record).  Synchronises the device; never call it inside a
+        capture."""
         buffers = self.vertical_buffers(H, W, D)
         if buffers is None:
             raise ValueError("vertical_report: no pair of %dx%d, ndisp=%d has been matched with vertical_offset on"
                              % (W, H, D))
         torch.cuda.synchronize()
+        if len(buffers) == 4:
+            return vertical_field_record(*(b.cpu().numpy() for b in buffers))
         return vertical_record(buffers[0].cpu().numpy(), buffers[1].cpu().numpy())
 
     def vertical_buffers(self, H, W, D):
         """(offset int32 [1], totals int64 [2 max + 1]) of the resident workspace of this shape - what vertical_report()
-        reads, for a caller that copies them out in stream order itself (the list loops) - or None."""
+        reads, for a caller that copies them out in stream order itself (the list loops) - or None.
+        vertical_offset="grid": (offset, totals, field int32 [gh, gw], cell totals int64 [gh, gw, 2 max + 1])."""
         ws = self._ws.get((int(H), int(W), int(D)))
-        return (ws["v_offset"], ws["v_totals"]) if ws is not None and "v_offset" in ws else None
+        if ws is None or "v_offset" not in ws:
+            return None
+        if "v_field" in ws:
+            return (ws["v_offset"], ws["v_totals"], ws["v_field"], ws["v_cells"])
+        return (ws["v_offset"], ws["v_totals"])
 
     def _right_stream(self):
         """The stream of the right volume's chain of aggregation launches: this matcher's own (like its side stream), so
@@ -2031,7 +2142,9 @@ class StereoMatcher(object):
                                    confidence=len(self.confidence), views=self.views,
                                    semi_dense=self.semi_dense is not None, **self._geometry_kw(),
                                    **{k: self.extras[k] for k in ("vertical_offset", "vertical_offset_max",
-                                                                  "vertical_offset_rows") if self._vertical_offset_on()})
+                                                                  "vertical_offset_rows") if self._vertical_offset_on()},
+                                   **(dict(vertical_offset_grid=tuple(self.extras["vertical_offset_grid"]))
+                                      if self._vertical_field_on() else {}))
             self._ws, self._graphs = {}, {}          # one shape resident at a time: the previous one goes first
             _require_device_memory(need, "StereoMatcher: the workspace of a %dx%d pair with ndisp=%d" % (W, H, D))
             dp = hwd_pitch(D)
@@ -2069,10 +2182,14 @@ class StereoMatcher(object):
                 ws["points_scratch"] = points_scratch(H, W, dev)
             if self._vertical_offset_on():
                 v, R = self.extras["vertical_offset"], self.extras["vertical_offset_max"]
-                ws["v_offset"] = torch.full((1,), 0 if v == "auto" else v, dtype=torch.int32, device=dev)
+                ws["v_offset"] = torch.full((1,), 0 if v in ("auto", "grid") else v, dtype=torch.int32, device=dev)
                 ws["v_totals"] = torch.zeros((2 * R + 1,), dtype=torch.int64, device=dev)
                 ws["v_votes"] = torch.zeros(vertical_profile_shape(H, W, R, self.extras["vertical_offset_rows"]),
                                             dtype=torch.int32, device=dev)
+                if self._vertical_field_on():
+                    grid = self.vertical_grid(H, W)
+                    ws["v_field"] = torch.zeros(grid, dtype=torch.int32, device=dev)
+                    ws["v_cells"] = torch.zeros(grid + (2 * R + 1,), dtype=torch.int64, device=dev)
             ws["progs"] = None
             # (distances above CBCA_HWD_MAX_DISTANCE: the aggregation programs do not encode such arms - the joined
             # two-volume path of mccnn_cbca_iter_hwd_long_pair runs, as for shapes the programs do not encode)
@@ -2225,11 +2342,17 @@ class StereoMatcher(object):
                              "disparities, not %d" % (offset, COST_VOLUME_HWD_MAX_D, D))
         timer.start("cost_volume")
         if offset != 0:
-            if offset == "auto":      # measured from this pair's features, on this stream; the kernel reads the result
-                votes = vertical_profile(fl, fr, D, self.extras["vertical_offset_max"],
-                                         self.extras["vertical_offset_rows"], out=ws["v_votes"])
-                vertical_offset_select(votes, self.extras["vertical_offset_max"], out=(ws["v_offset"], ws["v_totals"]))
-            left, right = cost_volume_offset_hwd(fl, fr, D, ws["v_offset"], vertical, out=(hwd[2], hwd[3]))
+            R, step = self.extras["vertical_offset_max"], self.extras["vertical_offset_rows"]
+            if offset in ("auto", "grid"):   # measured from this pair's features, on this stream; the kernel reads the result
+                votes = vertical_profile(fl, fr, D, R, step, out=ws["v_votes"])
+            if offset == "grid":             # ... per cell of the grid the workspace was sized for
+                vertical_field_select(votes, fl.shape[0], step, R, tuple(ws["v_field"].shape),
+                                      out=(ws["v_field"], ws["v_cells"], ws["v_offset"], ws["v_totals"]))
+                left, right = cost_volume_field_hwd(fl, fr, D, ws["v_field"], vertical, out=(hwd[2], hwd[3]))
+            else:
+                if offset == "auto":
+                    vertical_offset_select(votes, R, out=(ws["v_offset"], ws["v_totals"]))
+                left, right = cost_volume_offset_hwd(fl, fr, D, ws["v_offset"], vertical, out=(hwd[2], hwd[3]))
         elif vertical:
             left, right = cost_volume_vertical_hwd(fl, fr, D, vertical, out=(hwd[2], hwd[3]))
         elif direct:
